@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: stochastic-map realisations/s (branch x site paths sampled per second).
 
-Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches one rank per GPU with
+Contract: `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]`; for N > 1 the driver launches one rank per GPU with
 torch.distributed.run.  A *step* is one full MCMC sweep (pruning + node sampling + branch path resampling +
 sufficient statistics) over every replica resident on the GPU.
 
@@ -18,6 +18,12 @@ kernel of the sweep nested under it (`kernels`; `dominant_kernel` names the larg
 the rate of ONE chain on the headline configuration (what the R call gets), one block per other BASELINE configuration
 (C2 streaming layout, C4 dense 61 states in the n + n^2 counting layout, C5 sparse 20 states, sumstatEXP on C1 and on a
 1 000-tip tree), the batched expm rates, and the CPU oracle timed on this box's host cores.
+
+`--dump-outputs DIR` writes, after the timed sweeps, what the headline path handed its caller for the LAST timed sweep:
+DIR/stats_last_step.npy, the float64 row of sufficient statistics summed over all replicas (n dwell sums, then the n (n - 1)
+transition counts; at N > 1 the all-reduced row).  Tree, Q, seeds and replica count are fixed by the arguments (the replica
+count is sized from free HBM up to a cap; pass --replicas to pin it on a card that other work shares), so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -203,6 +209,7 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline line only (skip the C2/C4/C5/EXP/expm blocks)")
     ap.add_argument("--force-collective", action="store_true", help="exercise the statistics hand-over to torch at N=1")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the headline path's output of its last timed sweep to DIR/*.npy")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -257,9 +264,10 @@ def main():
         return max(64, S // 1024 * 1024 if S >= 1024 else S // 64 * 64)
 
     def measure(cfg, mapping, S, K, W, seed, ipl=8, storage=0, collective=False, offset=0, variant=_lib.PHM_MCMC_BIGTREE, tkey=None, max_iters=0,
-                problem=None):
+                problem=None, outputs=None):
         """K timed sweeps of configuration `cfg` after args.burnin + W untimed sweeps; returns (block, wall seconds).
-        max_iters > K + W: the engine is provisioned for a run of that length (slots, statistics rows), of which K + W sweeps run."""
+        max_iters > K + W: the engine is provisioned for a run of that length (slots, statistics rows), of which K + W sweeps run.
+        outputs: a dict that receives the caller's statistics row of the last timed sweep (all-reduced when collective)."""
         W = W + args.burnin
         z, Q, pid, Omega = problem or synth.config_problem(cfg)
         n, E = Q.shape[0], z["edge"].shape[0]
@@ -304,6 +312,8 @@ def main():
         assert np.allclose(stats[:, :n].sum(1), S * z["edge.length"].sum(), rtol=1e-9)
         if total is not None and world == 1:
             assert np.array_equal(total, stats)
+        if outputs is not None:
+            outputs["stats_last_step"] = np.array((total if total is not None else stats)[K - 1], dtype=np.float64)
         tr = traffic.get(tkey or f"C{cfg}", {})
         per = E * S                                          # units of one sweep
         blk = {"workload": tkey or f"C{cfg}", "n_states": n, "n_tips": int(z["states"].size), "branches": E, "replicas": S, "mapping": mapping,
@@ -413,8 +423,15 @@ def main():
             pos += s_
         if pos != S_total:
             raise SystemExit(f"bench.py: ranks disagree on the replica sharding: {spans} does not tile [0, {S_total})")
+    if args.dump_outputs and args.replicas <= 0 and S_req < cap and rank == 0:
+        print(f"bench.py: free HBM sized the run to {S_req} < {cap} replicas; pass --replicas to compare dumps across runs", file=sys.stderr)
+    dumped = {}
     head, dt = measure(cfg, mapping, S, K, W, 0x5EED0000 + cfg, ipl=args.ipl, storage=sto,
-                       collective=(world > 1 or args.force_collective), offset=offset)
+                       collective=(world > 1 or args.force_collective), offset=offset, outputs=dumped)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -222,14 +222,16 @@ def test_newick_parser_numbers_nodes_like_ape_and_prunes():
     assert eng_orders[2] == 4
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/inst/extdata/Squamate/squamate.phy"), reason="reference data only in the build container")
 def test_newick_reader_reproduces_the_reference_prepared_squamate_tree():
     """inst/extdata/Squamate/squamate.phy through phylomap_amd/newick.py equals the tree the reference prepared in R
     (R/Squamate_tree_setup.R -> phylomap_compatible_squamate_tree.RData): same tip labels, the same ape node numbering and
     edge order, the same branch lengths, the same 100-segment initial paths."""
+    import gzip
     from phylomap_amd import newick, rds
-    t = newick.read_newick(open("/root/reference/inst/extdata/Squamate/squamate.phy").read())
-    z = rds.read_rds("/root/reference/inst/extdata/Squamate/phylomap_compatible_squamate_tree.RData")
+    sq = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "squamate")     # the reference's two data files, stored as fixtures
+    with gzip.open(os.path.join(sq, "squamate.phy.gz"), "rt") as f:
+        t = newick.read_newick(f.read())
+    z = rds.read_rds(os.path.join(sq, "phylomap_compatible_squamate_tree.RData"))
     assert t["tip.label"] == list(z["tip.label"]) and t["Nnode"] == 3950
     np.testing.assert_array_equal(t["edge"], np.asarray(z["edge"]).astype(np.int32))
     np.testing.assert_allclose(t["edge.length"], np.asarray(z["edge.length"]), rtol=0, atol=1e-12)

@@ -528,10 +528,9 @@ def test_multitree_oracle_structure():
     assert rc & O.ERR_BAD_INPUT
 
 
-SQUAMATE_RDS = "/root/reference/inst/extdata/Squamate/phylomap_compatible_squamate_tree.RData"
+SQUAMATE_RDS = os.path.join(GOLDEN, "squamate", "phylomap_compatible_squamate_tree.RData")     # the reference's data file, stored as a fixture
 
 
-@pytest.mark.skipif(not os.path.exists(SQUAMATE_RDS), reason="the reference's data file is only present in the build container")
 def test_known_answer_squamate_seed_101_tip_simulation():
     """The reference's own known answer for its data pipeline: R/simulate_2_state_tree.R:11 notes "n01 is 21" for
     set.seed(101) on the shipped 3 951-tip squamate tree.  Reproducing it takes the RDS reader, the R random stream of the
