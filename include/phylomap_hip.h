@@ -211,7 +211,8 @@ const char* phm_last_error(void);
 const char* phm_status_string(int32_t status);
 /* measurement / test aids of this thread -- see the phm_debug_options struct; NULL = defaults */
 int32_t     phm_set_debug_options(const phm_debug_options* dbg);
-/* measurement aid: HIP-event milliseconds of the sampling kernel of this thread's last phm_maketreelistEXP call */
+/* measurement aid: HIP-event milliseconds of the sampling kernel of this thread's last phm_maketreelistEXP call (or of the
+ * simulation kernel of its last forward simulation) */
 double      phm_last_kernel_ms(void);
 
 /* ---- reference-shaped one-shot entry points (what the Rcpp shim binds) ----
@@ -289,6 +290,24 @@ int32_t phm_maketreelistEXP(          /* src/phylomap.cpp:3001, src/RcppExports.
     const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
     const double* lefts, const double* rights, const double* d,
     const phm_options* opt, double* out);
+
+/* ---- forward simulation: data for the samplers ----
+ * Forward simulation of the chain along the tree (R/sourceme.R:346-414, sample2statehistory / samplethebranch), n_replicas
+ * independent histories.  Reads x->edge, x->edge_length, n_tips, n_node only (states / maps may be NULL).
+ * observe: NULL = identity, else n values in 1..n: the tip state reported for each true state (simulate_4_state_tree's
+ * parity map is {1,2,1,2}).  tips: n_replicas x n_tips, REPLICA-major, 1-based (the layout of x->states with
+ * tips_per_replica = 1).  nodes: NULL, or n_replicas x (n_tips + n_node), replica-major, 1-based true states by ape node id.
+ * stats: n_replicas x (n + n*n + 1) column-major: dwell per state, jump counts n x n row-major (from,to) with zero diagonal,
+ * root state (0-based).
+ * Options: seed, n_replicas, replica_offset, device, n_devices / devices[] (sharded by global replica id); reduce must be 0;
+ * mapping is ignored.  2 <= n <= 64; Q with finite off-diagonal entries >= 0 and rows summing to 0 (1e-12 max|q|); pid >= 0
+ * with a positive sum (else PHM_ERR_ZERO_PROB).  A branch that needs more than 9 999 jumps (where samplethebranch stops,
+ * R/sourceme.R:356) fails with PHM_ERR_CAPACITY naming its edge row; an absorbing state (q_ss = 0) keeps the rest of the
+ * branch.  Random numbers: DESIGN.md section 12 (Philox iteration word 0xFFFFFFFF, which no MCMC sweep reaches).
+ * phm_last_kernel_ms gives the simulation kernel's time. */
+int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
+                               const int32_t* observe, const phm_options* opt,
+                               int32_t* tips, int32_t* nodes, double* stats);
 
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q

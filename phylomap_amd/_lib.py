@@ -24,7 +24,7 @@ EXPORTS = [
     "phm_engine_info", "phm_engine_destroy", "phm_engine_reduced_stats_device",
     "phm_engine_time_pruning", "phm_tree_orders",
     "phm_engine_create_multi", "phm_maketreelistMCMCmt", "phm_maketreelistMCMCksmt", "phm_engine_phase_ms",
-    "phm_last_kernel_ms", "phm_set_debug_options", "phm_sparse_kernel_source",
+    "phm_last_kernel_ms", "phm_set_debug_options", "phm_sparse_kernel_source", "phm_simulate_histories",
 ]
 
 
@@ -144,6 +144,9 @@ def load():
         L.phm_expm_pade.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32,
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.phm_set_debug_options.argtypes = [C.POINTER(DebugOptions)]
+        L.phm_simulate_histories.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_double)]
         L.phm_sparse_kernel_source.argtypes = [C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]
         for which, mirror in enumerate((Options, Info, Tree, Model, DebugOptions)):      # the ctypes mirrors must match the C layout
             if L.phm_struct_size(which) != C.sizeof(mirror):

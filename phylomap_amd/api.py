@@ -218,3 +218,45 @@ def expm_pade(Q, t, device=-1, mfma=False):
     _lib.check(fn(n, _lib._p(Q, C.c_double), _lib._p(t, C.c_double), int(t.size), int(device),
                                _lib._p(out, C.c_double), C.byref(ms)))
     return out, ms.value
+
+
+def simulate_histories(z, Q, pid, R, observe=None, nodes=False, **opt):
+    """``R`` independent forward simulations of the chain along the tree of ``z`` (sample2statehistory, R/sourceme.R:346-414)
+    -> phm_simulate_histories.  Reads ``z['edge']``, ``z['edge.length']`` and ``z['Nnode']`` only.  ``observe``: n values in
+    1..n, the tip state reported for each true state (simulate_4_state_tree's parity map is (1, 2, 1, 2)).
+    Returns ``(tips, stats)`` or, with ``nodes=True``, ``(tips, stats, nodes)``: tips [R, n_tips] 1-based (ready for the
+    samplers' ``sites=``), stats [R, n + n*n + 1] (dwell per state, jump counts n x n row-major (from, to), root state 0-based),
+    nodes [R, n_tips + Nnode] 1-based true states by ape node id.  Options: seed, replica_offset, device, devices."""
+    L = _lib.load()
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+    n = Q.shape[0]
+    pid = np.ascontiguousarray(pid, dtype=np.float64)
+    edge = np.asarray(z["edge"], dtype=np.int32)
+    E = edge.shape[0]
+    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
+    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
+    Nn = int(z["Nnode"])
+    T = E - Nn + 1
+    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
+    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
+    if obs is not None and obs.size != n:
+        raise ValueError("observe must have one entry per state")
+    R = int(R)
+    o = _lib.make_options(n_replicas=R, **opt)
+    tips = np.zeros((max(R, 1), T), dtype=np.int32)
+    nst = np.zeros((max(R, 1), T + Nn), dtype=np.int32) if nodes else None
+    stats = np.zeros((max(R, 1), n + n * n + 1), order="F")
+    _lib.check(L.phm_simulate_histories(C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
+                                        _lib._p(obs, C.c_int32), C.byref(o), _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32),
+                                        _lib._p(stats, C.c_double)))
+    return (tips, stats, nst) if nodes else (tips, stats)
+
+
+def simulate_state_tree(z, Q, pid, observe=None, **opt):
+    """simulate_2_state_tree / simulate_4_state_tree (R/simulate_2_state_tree.R, R/simulate_4_state_tree.R) for any tree and
+    model: one simulated history, and ``z`` returned with its tips replaced by the simulated (observed) states and its tip
+    branches re-initialised to two half-length pieces (synth.with_tip_states).  ``observe=(1, 2, 1, 2)`` is the 4-state
+    function's parity map."""
+    from . import synth
+    tips, _ = simulate_histories(z, Q, pid, 1, observe=observe, **opt)
+    return synth.with_tip_states(z, tips[0])

@@ -1,0 +1,171 @@
+// phm_sim_api.cpp -- C-ABI of the forward simulation of character histories (phm_simulate_histories): sample2statehistory /
+// samplethebranch (R/sourceme.R:346-414), simulate_2_state_tree / simulate_4_state_tree (R/simulate_*_state_tree.R) for many
+// replicas in one call.  Validation on the host, one kernel launch per device, a transposing epilogue for the state matrices.
+#include "phm_internal.h"
+#include "phm_sim.h"
+
+#include <thread>
+
+namespace {
+
+// What every device of a call shares, checked and derived once on the host.
+struct SimInput {
+  int n = 0, T = 0, Nn = 0, E = 0;
+  phm::Schedule sched;
+  std::vector<double> qoff, inv_rate, pid, edge_length;
+  std::vector<int32_t> tip_map, node_map;      // 0-based state -> reported 1-based state
+};
+
+int32_t sim_validate(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* observe, const phm_options& o,
+                     const int32_t* tips, const double* stats, SimInput& in) {
+  if (!x || !Q || !pid || !tips || !stats) return fail(PHM_ERR_BAD_INPUT, "phm_simulate_histories: NULL argument (only `nodes` may be NULL)");
+  if (n < 2 || n > phm::SIM_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, "phm_simulate_histories: n_states must be in 2..64");
+  if (o.reduce != 0) return fail(PHM_ERR_BAD_INPUT, "phm_simulate_histories: reduce must be 0 (statistics are per replica)");
+  if (o.n_replicas < 0 || o.n_replicas > (1 << 22)) return fail(PHM_ERR_BAD_INPUT, "phm_simulate_histories: n_replicas must be in 0..4194304");
+  if (!x->edge || !x->edge_length) return fail(PHM_ERR_BAD_INPUT, "phm_simulate_histories: x$edge and x$edge.length are required");
+  std::string serr;
+  if (!phm::build_schedule(x->n_tips, x->n_node, x->n_edge, x->edge, in.sched, serr)) return fail(PHM_ERR_BAD_INPUT, "tree: " + serr);
+  in.n = n; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge;
+  for (int b = 0; b < in.E; ++b)
+    if (!std::isfinite(x->edge_length[b]) || x->edge_length[b] < 0.0)
+      return fail(PHM_ERR_BAD_INPUT, "edge.length must be finite and non-negative (edge row " + std::to_string(b + 1) + ")");
+  in.edge_length.assign(x->edge_length, x->edge_length + in.E);
+  double qmax = 0.0;
+  for (int i = 0; i < n * n; ++i) {
+    if (!std::isfinite(Q[i])) return fail(PHM_ERR_BAD_INPUT, "Q must be finite");
+    qmax = std::max(qmax, std::fabs(Q[i]));
+  }
+  in.qoff.assign((size_t)n * n, 0.0);
+  in.inv_rate.assign(n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    double row = 0.0, off = 0.0;
+    for (int j = 0; j < n; ++j) {
+      const double q = Q[i + (size_t)j * n];                        // column-major
+      row += q;
+      if (j == i) continue;
+      if (q < 0.0) return fail(PHM_ERR_BAD_INPUT, "Q: off-diagonal entries must be >= 0 (row " + std::to_string(i + 1) + ")");
+      in.qoff[(size_t)i * n + j] = q;
+      off += q;
+    }
+    if (std::fabs(row) > 1e-12 * qmax) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " does not sum to 0");
+    const double qii = Q[i + (size_t)i * n];
+    if (qii < 0.0 && !(off > 0.0)) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " leaves its state but has no target");
+    in.inv_rate[i] = qii < 0.0 ? 1.0 / (-qii) : 0.0;                  // 0: absorbing (q_ss = 0)
+  }
+  double psum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    if (!(pid[i] >= 0.0) || !std::isfinite(pid[i])) return fail(PHM_ERR_ZERO_PROB, "pid must be finite and non-negative");
+    psum += pid[i];
+  }
+  if (!(psum > 0.0)) return fail(PHM_ERR_ZERO_PROB, "pid sums to zero");
+  in.pid.assign(pid, pid + n);
+  in.tip_map.resize(n);
+  in.node_map.resize(n);
+  for (int i = 0; i < n; ++i) {
+    in.node_map[i] = i + 1;
+    in.tip_map[i] = observe ? observe[i] : i + 1;
+    if (in.tip_map[i] < 1 || in.tip_map[i] > n) return fail(PHM_ERR_BAD_INPUT, "observe: values must be in 1..n");
+  }
+  return PHM_OK;
+}
+
+// Replicas [first, first + R) of the call on one device.  tips / nodes / stats point at the caller's full matrices; stats has
+// ld_stats rows (the call's replica count).
+int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device, int64_t first, int32_t R, int32_t* tips, int32_t* nodes,
+                       double* stats, int64_t ld_stats, double* kernel_ms) {
+  int32_t st = select_device(device);
+  if (st) return st;
+  const int n = in.n, T = in.T, E = in.E, rows = in.T + in.Nn, cols = n + n * n + 1;
+  const int pad = (R + 63) / 64 * 64;
+  DevBuf ddown, dq, dinv, dpid, dlen, dns, dstats, derr, dmap, dout;
+  HIPCHK(ddown.alloc(sizeof(phm::DownStep) * E)); HIPCHK(dq.alloc(sizeof(double) * n * n)); HIPCHK(dinv.alloc(sizeof(double) * n));
+  HIPCHK(dpid.alloc(sizeof(double) * n)); HIPCHK(dlen.alloc(sizeof(double) * E)); HIPCHK(dns.alloc((size_t)rows * pad));
+  HIPCHK(dstats.alloc(sizeof(double) * cols * (size_t)pad)); HIPCHK(derr.alloc(2 * sizeof(uint32_t)));
+  HIPCHK(dmap.alloc(sizeof(int32_t) * 2 * n));
+  HIPCHK(dout.alloc(sizeof(int32_t) * (size_t)R * (nodes ? rows : T)));
+  std::vector<int32_t> maps(in.tip_map);
+  maps.insert(maps.end(), in.node_map.begin(), in.node_map.end());
+  const uint32_t err_init[2] = {0u, 0xFFFFFFFFu};
+  HIPCHK(hipMemcpy(ddown.p, in.sched.down.data(), ddown.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dq.p, in.qoff.data(), dq.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dinv.p, in.inv_rate.data(), dinv.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dpid.p, in.pid.data(), dpid.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dlen.p, in.edge_length.data(), dlen.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(derr.p, err_init, derr.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dmap.p, maps.data(), dmap.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dstats.p, 0, dstats.bytes));
+  phm::SimParams p;
+  p.n_states = n; p.n_tips = T; p.n_node = in.Nn; p.n_edge = E; p.root = in.sched.root;
+  p.n_rep = R; p.n_rep_pad = pad; p.replica_offset = (uint32_t)((int64_t)o.replica_offset + first);
+  p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
+  p.down = ddown.as<phm::DownStep>(); p.qoff = dq.as<double>(); p.inv_rate = dinv.as<double>(); p.pid = dpid.as<double>();
+  p.edge_length = dlen.as<double>(); p.nstate = dns.as<uint8_t>(); p.stats = dstats.as<double>(); p.err = derr.as<uint32_t>();
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIPCHK(hipEventCreate(&ev0));
+  if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(PHM_ERR_NO_DEVICE, "hipEventCreate failed"); }
+  hipError_t le = hipEventRecord(ev0, nullptr);
+  if (le == hipSuccess) le = phm::launch_simulate(p, nullptr);
+  if (le == hipSuccess) le = hipEventRecord(ev1, nullptr);
+  if (le == hipSuccess) le = hipEventSynchronize(ev1);
+  float ms = 0.f;
+  if (le == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && kernel_ms) *kernel_ms = ms;
+  (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+  HIPCHK(le);
+  uint32_t errh[2];
+  HIPCHK(hipMemcpy(errh, derr.p, sizeof errh, hipMemcpyDeviceToHost));
+  if (errh[0] & phm::DERR_CAPACITY)
+    return fail(PHM_ERR_CAPACITY, "more than " + std::to_string(phm::SIM_MAX_JUMPS) + " jumps on edge row " + std::to_string(errh[1] + 1) +
+                                      " (samplethebranch stops there, R/sourceme.R:356)");
+  st = device_status(errh[0]);
+  if (st) return st;
+  // statistics: [col][pad] -> the caller's column-major ld_stats x cols matrix, rows first .. first + R - 1
+  HIPCHK(hipMemcpy2D(stats + first, sizeof(double) * ld_stats, dstats.p, sizeof(double) * pad, sizeof(double) * R, cols,
+                     hipMemcpyDeviceToHost));
+  HIPCHK(phm::launch_sim_transpose(dns.as<uint8_t>(), T, R, pad, dmap.as<int32_t>(), dout.as<int32_t>(), nullptr));
+  HIPCHK(hipMemcpy(tips + first * T, dout.p, sizeof(int32_t) * (size_t)R * T, hipMemcpyDeviceToHost));
+  if (nodes) {
+    HIPCHK(phm::launch_sim_transpose(dns.as<uint8_t>(), rows, R, pad, dmap.as<int32_t>() + n, dout.as<int32_t>(), nullptr));
+    HIPCHK(hipMemcpy(nodes + first * rows, dout.p, sizeof(int32_t) * (size_t)R * rows, hipMemcpyDeviceToHost));
+  }
+  return PHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Replicas are independent given (seed, global replica id): with phm_options.n_devices > 1 device d simulates a contiguous range
+// of them (phm_plan_shards, one host thread per device); every output row is the one-device row bit for bit.
+int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double* Q, const double* pid, const int32_t* observe,
+                               const phm_options* opt, int32_t* tips, int32_t* nodes, double* stats) {
+  phm_options o;
+  std::memset(&o, 0, sizeof(o));
+  o.device = -1;
+  if (opt) o = *opt;
+  SimInput in;
+  int32_t st = sim_validate(x, n_states, Q, pid, observe, o, tips, stats, in);
+  if (st) return st;
+  const int32_t R = std::max(1, (int)o.n_replicas);
+  std::vector<phm_shard> shards;
+  st = phm_plan_shards(o, R, shards);
+  if (st) return st;
+  struct Run { int32_t st = PHM_OK; std::string err; double ms = 0.0; };
+  std::vector<Run> runs(shards.size());
+  auto work = [&](size_t i) {
+    runs[i].st = sim_one_device(in, o, shards[i].device, shards[i].first, (int32_t)shards[i].count, tips, nodes, stats, R, &runs[i].ms);
+    if (runs[i].st) runs[i].err = g_phm_err;
+  };
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < shards.size(); ++i) th.emplace_back(work, i);
+  work(0);
+  for (std::thread& t : th) t.join();
+  double ms = 0.0;
+  for (size_t i = 0; i < shards.size(); ++i) {
+    if (runs[i].st) return shards.size() == 1 ? fail(runs[i].st, runs[i].err) : fail(runs[i].st, "device " + std::to_string(shards[i].device) + ": " + runs[i].err);
+    ms = std::max(ms, runs[i].ms);
+  }
+  g_phm_last_kernel_ms = ms;      // the devices simulate side by side: the longest
+  return PHM_OK;
+}
+
+}  // extern "C"

@@ -239,11 +239,39 @@ def make_tree(n_tips: int, Q, Omega: float, seed: int, pid=None, states=None, in
     for r in range(E):
         child = int(edge[r, 1])
         end = int(states[child - 1]) if child <= n_tips else 1
-        maps.append(np.full(init_segments, lens[r] / init_segments))
-        mapnames.append(np.array([1] * (init_segments - 1) + [end], dtype=np.int32))
+        m, mn = initial_path(lens[r], end, init_segments)
+        maps.append(m)
+        mapnames.append(mn)
         node_states[r, 1] = end
     return {"edge": edge, "Nnode": n_tips - 1, "edge.length": lens, "states": states,
             "maps": maps, "mapnames": mapnames, "node.states": node_states}
+
+
+def initial_path(length: float, end: int, init_segments: int = 2):
+    """(maps, mapnames) of one branch: ``init_segments`` equal pieces in state 1, the last one in state ``end``."""
+    return (np.full(init_segments, length / init_segments),
+            np.array([1] * (init_segments - 1) + [end], dtype=np.int32))
+
+
+def with_tip_states(z, states):
+    """The tree ``z`` with new tip states, shaped as R/simulate_2_state_tree.R:15-31 returns it: ``states`` replaced, every tip
+    branch re-initialised to two half-length pieces (1, tip state), internal branches keep their paths, ``node.states`` all 1
+    except the tip column of tip branches."""
+    states = np.asarray(states, dtype=np.int32)
+    edge = np.asarray(z["edge"])
+    n_tips = states.shape[-1]
+    out = dict(z)
+    out["states"] = states
+    out["maps"] = [np.asarray(m, dtype=np.float64) for m in z["maps"]]
+    out["mapnames"] = [np.asarray(m, dtype=np.int32) for m in z["mapnames"]]
+    node_states = np.ones((edge.shape[0], 2), dtype=np.int32)
+    for r in range(edge.shape[0]):
+        child = int(edge[r, 1])
+        if child <= n_tips:
+            out["maps"][r], out["mapnames"][r] = initial_path(float(z["edge.length"][r]), int(states[child - 1]), 2)
+            node_states[r, 1] = states[child - 1]
+    out["node.states"] = node_states
+    return out
 
 
 def make_treelist(n_trees: int, n_tips: int, Q, Omega: float, seed: int, pid=None, init_segments: int = 2):
