@@ -444,7 +444,7 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
     max_cap = std::max(max_cap, cap[b]);
     e->nw_off[b + 1] = e->nw_off[b] + cap[b];
-    if (std::max(1.0 + model->Omega * tb, (double)m0) >= phm::NARROW_WIDE_SEGMENTS) ++n_wide;      // a long path: the wave-wide walk (phm_narrow.hip)
+    if (expected_segments(x, b, model->Omega) >= phm::NARROW_WIDE_SEGMENTS) ++n_wide;      // a long path: the wave-wide walk (phm_narrow.hip)
   }
   e->nw_n_wide = std::max(n_wide, std::min(E / 16, phm::NARROW_LONG));
   // long chains: the pruning clusters without level barriers (phm_narrow.hip); debug pruning_form 1 / 2 = never / always
@@ -644,7 +644,7 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
     const int m0 = x->map_off[b + 1] - x->map_off[b];
     const int q = phm::poisson_capacity(model->Omega * tb, tail);
     cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
-    max_seg = std::max(max_seg, std::max(1.0 + model->Omega * tb, (double)m0));
+    max_seg = std::max(max_seg, expected_segments(x, b, model->Omega));
     if (cap[b] >= (1 << 23)) return fail(PHM_ERR_UNSUPPORTED, "branch too long: a slot of the (tile, branch) mapping exceeds 4 GB");   // 32-bit offsets, phm_tiles.hip
     max_cap = std::max(max_cap, cap[b]);
     rows += cap[b];
@@ -1036,8 +1036,8 @@ int32_t phm_engine_create_multi(const phm_tree* trees, int32_t n_trees, const ph
 
 }  // extern "C"
 
-// The one constructor behind phm_engine_create / _multi, the multi-device one-shot calls (worker threads pass the CALLER's
-// debug options) and the capacity recovery (boost_log2: log2 of the multiplier applied to the provisioned capacities).
+// The one constructor behind phm_engine_create / _multi, the one-shot calls (every shard's thread passes the CALLER's debug
+// options, run_shards) and the capacity recovery (boost_log2: log2 of the multiplier applied to the provisioned capacities).
 int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm_model* model, const phm_options* opt_in,
                                const phm_debug_options& dbg, int boost_log2, int32_t max_iters, phm_engine** out) {
   if (!out) return fail(PHM_ERR_BAD_INPUT, "out is NULL");
@@ -1045,10 +1045,7 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
   if (!trees || !model) return fail(PHM_ERR_BAD_INPUT, "tree/model is NULL");
   if (n_trees < 1) return fail(PHM_ERR_BAD_INPUT, "n_trees must be >= 1");
   const phm_tree* x = trees;
-  phm_options o;
-  std::memset(&o, 0, sizeof(o));
-  o.device = -1;
-  if (opt_in) o = *opt_in;
+  phm_options o = resolve_options(opt_in);
   if (o.n_replicas <= 0) o.n_replicas = 1;
   const int n = model->n_states;
   if (n < 2) return fail(PHM_ERR_BAD_INPUT, "n_states must be >= 2");
@@ -1139,9 +1136,7 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
       // 256; profiles/r04_probe_squamate_crossover.log).  S* = floor / slope.
       double max_seg = 0.0, tot_seg = 0.0;
       for (int b = 0; b < E; ++b) {
-        double tb = 0.0;
-        for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
-        const double seg = std::max(1.0 + model->Omega * tb, (double)(x->map_off[b + 1] - x->map_off[b]));
+        const double seg = expected_segments(x, b, model->Omega);
         max_seg = std::max(max_seg, seg); tot_seg += seg;
       }
       if (max_seg > 64.0) narrow_cap = std::max(narrow_cap, (int)std::min(65535.0, 1.35e-3 * max_seg / (4.4e-8 * tot_seg)));
@@ -1598,7 +1593,7 @@ int32_t phm_engine_read_stats(phm_engine* e, int32_t iter0, int32_t n, double* o
 
 }  // extern "C"
 
-// Multi-device one-shot calls, reduce = 1: the statistics of iterations [iter0, iter0 + n) summed over this engine's tiles in tile order,
+// One-shot calls, reduce = 1: the statistics of iterations [iter0, iter0 + n) summed over this engine's tiles in tile order,
 // CONTINUING from `acc` (n x dcols row-major: the totals of the devices before this one; empty = start from zero) -- the fold of
 // stats_reduce_kernel carried across devices, so whole-tile shards reproduce the one-device sum term by term.  `acc` is replaced.
 int32_t phm_engine_fold_reduced(phm_engine* e, int32_t iter0, int32_t n, std::vector<double>& acc) {

@@ -2,8 +2,6 @@
 // MFMA f64 variants) and the sumstatEXP driver (maketreelistEXP, src/phylomap.cpp:3001-3051).
 #include "phm_internal.h"
 
-#include <thread>
-
 namespace {
 
 struct Timer {
@@ -123,19 +121,15 @@ int32_t phm_expm_pade_mfma(int32_t n, const double* Q, const double* t, int32_t 
 
 // maketreelistEXP, src/phylomap.cpp:3001-3051.  P(t_b) and the pruning pass are computed ONCE (the reference
 // recomputes both every iteration although Q never changes, :2980-2981).
-// samples [it0, it0 + N) of the call on ONE device (o.device); out: N x cols column-major
+// samples [it0, it0 + N) of the call on one device; out: the caller's column-major matrix of ld_out rows, rows it0 .. it0 + N - 1
 static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* nen,
                            const int32_t* nodelist, int32_t root, int32_t N, int32_t it0, const double* lefts, const double* rights,
-                           const double* d, const phm_options* opt_in, double* out) {
+                           const double* d, const phm_options& o, int32_t device, double* out, int64_t ld_out) {
   if (!x || !Q || !pid || !lefts || !rights || !d || !out) return fail(PHM_ERR_BAD_INPUT, "phm_maketreelistEXP: NULL argument");
   if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
   if (n < 2) return fail(PHM_ERR_BAD_INPUT, "n_states must be >= 2");
   if (n > 64) return fail(PHM_ERR_UNSUPPORTED, "this build has EXP kernels for n_states <= 64 only");
   if (!x->edge_length) return fail(PHM_ERR_BAD_INPUT, "x$edge.length is required (src/phylomap.cpp:3034)");
-  phm_options o;
-  std::memset(&o, 0, sizeof(o));
-  o.device = -1;
-  if (opt_in) o = *opt_in;
   int32_t st = validate_tree_paths(x, n, 1);
   if (st) return st;
   phm::Schedule s;
@@ -161,7 +155,7 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
   std::vector<double> col, rowtab;
   build_chain_tables(B2.data(), n, phm::UNIF_CAP + 1, col, rowtab, false, false);      // newunifSample :127: unfused sums for every n; no row table
 
-  st = select_device(o.device);
+  st = select_device(device);
   if (st) return st;
   const size_t nn = (size_t)n * n;
   const int tiles = (N + 63) / 64;
@@ -211,6 +205,14 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
                                      o.rescale_pruning != 0, nullptr));
     HIPCHK(hipDeviceSynchronize());      // duord goes out of scope
   }
+  // the N x cols samples into rows it0 .. of the caller's matrix (one shard: the whole, contiguous matrix), then the error word
+  auto copy_out = [&]() -> int32_t {
+    if (ld_out == N) HIPCHK(hipMemcpy(out, dout.p, dout.bytes, hipMemcpyDeviceToHost));
+    else HIPCHK(hipMemcpy2D(out + it0, sizeof(double) * ld_out, dout.p, sizeof(double) * N, sizeof(double) * N, cols, hipMemcpyDeviceToHost));
+    uint32_t derrh = 0;
+    HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
+    return device_status(derrh);
+  };
   hipEvent_t ev0 = nullptr, ev1 = nullptr;      // time of the sampling kernel alone (phm_last_kernel_ms)
   HIPCHK(hipEventCreate(&ev0)); HIPCHK(hipEventCreate(&ev1));
   HIPCHK(hipEventRecord(ev0, nullptr));
@@ -263,10 +265,7 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
     HIPCHK(hipEventSynchronize(ev1));
     { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms; }
     (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-    HIPCHK(hipMemcpy(out, dout.p, dout.bytes, hipMemcpyDeviceToHost));
-    uint32_t derrh = 0;
-    HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
-    return device_status(derrh);
+    return copy_out();
   }
   auto fill = [&](auto& p) {
     p.n_tips = T; p.n_node = s.n_node; p.n_edge = E; p.root = s.root; p.N = N; p.n_tiles = tiles; p.it0 = it0;
@@ -302,55 +301,23 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
   HIPCHK(hipEventSynchronize(ev1));
   { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms; }
   (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-  HIPCHK(hipMemcpy(out, dout.p, dout.bytes, hipMemcpyDeviceToHost));
-  uint32_t derrh = 0;
-  HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
-  return device_status(derrh);
+  return copy_out();
 }
 
 // The samples are i.i.d. and addressed by their index (src/phylomap.cpp:3045-3048): with phm_options.n_devices > 1 device d draws
-// a contiguous range of the N samples (one host thread per device) -- the matrix is the one-device matrix row for row.
+// a contiguous range of the N samples (run_shards) into its rows of `out` -- the matrix is the one-device matrix row for row.
 int32_t phm_maketreelistEXP(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* nen,
                             const int32_t* nodelist, int32_t root, int32_t N, const double* lefts, const double* rights,
                             const double* d, const phm_options* opt_in, double* out) {
   if (!out) return fail(PHM_ERR_BAD_INPUT, "phm_maketreelistEXP: NULL argument");
   if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
-  phm_options o;
-  std::memset(&o, 0, sizeof(o));
-  o.device = -1;
-  if (opt_in) o = *opt_in;
+  const phm_options o = resolve_options(opt_in);
   std::vector<phm_shard> shards;
-  int32_t st = phm_plan_shards(o, N, shards);
+  const int32_t st = phm_plan_shards(o, N, shards);
   if (st) return st;
-  if (shards.size() == 1) {
-    o.device = shards[0].device; o.n_devices = 0;
-    return exp_oneshot(x, n, Q, pid, nen, nodelist, root, N, 0, lefts, rights, d, &o, out);
-  }
-  const int cols = n + n * (n - 1);
-  struct Run { int32_t st = PHM_OK; std::string err; double ms = 0.0; std::vector<double> buf; };
-  std::vector<Run> runs(shards.size());
-  auto work = [&](size_t i) {
-    phm_options oi = o;
-    oi.device = shards[i].device; oi.n_devices = 0;
-    const int32_t Ni = (int32_t)shards[i].count;
-    runs[i].buf.assign((size_t)Ni * cols, 0.0);
-    runs[i].st = exp_oneshot(x, n, Q, pid, nen, nodelist, root, Ni, (int32_t)shards[i].first, lefts, rights, d, &oi, runs[i].buf.data());
-    if (runs[i].st) runs[i].err = g_phm_err;
-    runs[i].ms = g_phm_last_kernel_ms;
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < shards.size(); ++i) th.emplace_back(work, i);
-  work(0);
-  for (std::thread& t : th) t.join();
-  double ms = 0.0;
-  for (size_t i = 0; i < shards.size(); ++i) {
-    if (runs[i].st) return fail(runs[i].st, "device " + std::to_string(shards[i].device) + ": " + runs[i].err);
-    ms = std::max(ms, runs[i].ms);
-    const size_t Ni = (size_t)shards[i].count, r0 = (size_t)shards[i].first;
-    for (int c = 0; c < cols; ++c) std::memcpy(out + (size_t)c * N + r0, runs[i].buf.data() + (size_t)c * Ni, sizeof(double) * Ni);
-  }
-  g_phm_last_kernel_ms = ms;      // the devices sample side by side: the longest
-  return PHM_OK;
+  return run_shards(shards, [&](const phm_shard& sh, size_t) {
+    return exp_oneshot(x, n, Q, pid, nen, nodelist, root, (int32_t)sh.count, (int32_t)sh.first, lefts, rights, d, o, sh.device, out, N);
+  });
 }
 
 double phm_last_kernel_ms(void) { return g_phm_last_kernel_ms; }

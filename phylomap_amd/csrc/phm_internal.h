@@ -1,5 +1,6 @@
-// phm_internal.h -- shared by the translation units behind the C-ABI (phm_engine.cpp, phm_drivers.cpp, phm_expm_api.cpp):
-// error reporting, device buffers, the engine object.  Not installed; include/phylomap_hip.h is the public interface.
+// phm_internal.h -- shared by the translation units behind the C-ABI (phm_engine.cpp, phm_drivers.cpp, phm_expm_api.cpp,
+// phm_sim_api.cpp): error reporting, options, device buffers, the engine object, the shard runner.  Not installed;
+// include/phylomap_hip.h is the public interface.
 #pragma once
 
 #include "../../include/phylomap_hip.h"
@@ -330,6 +331,57 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
 int32_t phm_engine_fold_reduced(phm_engine* e, int32_t iter0, int32_t n, std::vector<double>& acc);
 int32_t phm_engine_finish_reduced(phm_engine* e, int32_t iter0, int32_t n, const std::vector<double>& acc, double* out);
 
-// multi-device one-shot calls (phm_drivers.cpp): contiguous ranges of `units` (replicas / sites / EXP samples) per device
+// The caller's options with the defaults applied (NULL: every field 0, device -1); a device list of one entry names the device.
+inline phm_options resolve_options(const phm_options* opt) {
+  phm_options o;
+  std::memset(&o, 0, sizeof(o));
+  o.device = -1;
+  if (opt) o = *opt;
+  if (o.n_devices == 1) { o.device = o.devices[0]; o.n_devices = 0; }
+  return o;
+}
+
+// Segments branch b of x is expected to hold: 1 + Poisson(Omega t_b) in stationarity (t_b = sum(x$maps[[b]])), or the caller's
+// path when that is longer.
+inline double expected_segments(const phm_tree* x, int b, double Omega) {
+  double tb = 0.0;
+  for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
+  return std::max(1.0 + Omega * tb, (double)(x->map_off[b + 1] - x->map_off[b]));
+}
+
+// one-shot calls on the GPUs of a node (phm_drivers.cpp): contiguous ranges of `units` (replicas / sites / EXP samples) per device
 struct phm_shard { int32_t device; int64_t first, count; };
 int32_t phm_plan_shards(const phm_options& o, int64_t units, std::vector<phm_shard>& shards);
+
+// The one place a one-shot call fans out over its shards: shard 0 runs on the calling thread, every other shard on a thread of its
+// own that first installs the caller's phm_debug_options.  body(shard, i) returns a status.  The first failure is reported
+// (prefixed with its device when there are several shards), phm_last_kernel_ms is that of the longest shard (they run side by
+// side), and after a call with several shards the caller's current device is the one it was before.
+template <typename Body>
+int32_t run_shards(const std::vector<phm_shard>& shards, Body body) {
+  struct Result { int32_t st = PHM_OK; std::string err; double ms = 0.0; };
+  std::vector<Result> res(shards.size());
+  const phm_debug_options dbg = g_phm_debug;
+  auto work = [&](size_t i) {
+    g_phm_debug = dbg;
+    g_phm_last_kernel_ms = 0.0;
+    res[i].st = body(shards[i], i);
+    if (res[i].st) res[i].err = g_phm_err;
+    res[i].ms = g_phm_last_kernel_ms;
+  };
+  const bool many = shards.size() > 1;
+  int caller_device = -1;
+  if (many && hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < shards.size(); ++i) th.emplace_back(work, i);
+  if (!shards.empty()) work(0);
+  for (std::thread& t : th) t.join();
+  if (caller_device >= 0) (void)hipSetDevice(caller_device);
+  double ms = 0.0;
+  for (size_t i = 0; i < shards.size(); ++i) {
+    if (res[i].st) return fail(res[i].st, many ? "device " + std::to_string(shards[i].device) + ": " + res[i].err : res[i].err);
+    ms = std::max(ms, res[i].ms);
+  }
+  g_phm_last_kernel_ms = ms;
+  return PHM_OK;
+}

@@ -4,8 +4,6 @@
 #include "phm_internal.h"
 #include "phm_sim.h"
 
-#include <thread>
-
 namespace {
 
 // What every device of a call shares, checked and derived once on the host.
@@ -72,7 +70,7 @@ int32_t sim_validate(const phm_tree* x, int32_t n, const double* Q, const double
 // Replicas [first, first + R) of the call on one device.  tips / nodes / stats point at the caller's full matrices; stats has
 // ld_stats rows (the call's replica count).
 int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device, int64_t first, int32_t R, int32_t* tips, int32_t* nodes,
-                       double* stats, int64_t ld_stats, double* kernel_ms) {
+                       double* stats, int64_t ld_stats) {
   int32_t st = select_device(device);
   if (st) return st;
   const int n = in.n, T = in.T, E = in.E, rows = in.T + in.Nn, cols = n + n * n + 1;
@@ -108,7 +106,7 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
   if (le == hipSuccess) le = hipEventRecord(ev1, nullptr);
   if (le == hipSuccess) le = hipEventSynchronize(ev1);
   float ms = 0.f;
-  if (le == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess && kernel_ms) *kernel_ms = ms;
+  if (le == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms;
   (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
   HIPCHK(le);
   uint32_t errh[2];
@@ -135,13 +133,10 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
 extern "C" {
 
 // Replicas are independent given (seed, global replica id): with phm_options.n_devices > 1 device d simulates a contiguous range
-// of them (phm_plan_shards, one host thread per device); every output row is the one-device row bit for bit.
+// of them (phm_plan_shards, run_shards); every output row is the one-device row bit for bit.
 int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double* Q, const double* pid, const int32_t* observe,
                                const phm_options* opt, int32_t* tips, int32_t* nodes, double* stats) {
-  phm_options o;
-  std::memset(&o, 0, sizeof(o));
-  o.device = -1;
-  if (opt) o = *opt;
+  const phm_options o = resolve_options(opt);
   SimInput in;
   int32_t st = sim_validate(x, n_states, Q, pid, observe, o, tips, stats, in);
   if (st) return st;
@@ -149,23 +144,9 @@ int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double
   std::vector<phm_shard> shards;
   st = phm_plan_shards(o, R, shards);
   if (st) return st;
-  struct Run { int32_t st = PHM_OK; std::string err; double ms = 0.0; };
-  std::vector<Run> runs(shards.size());
-  auto work = [&](size_t i) {
-    runs[i].st = sim_one_device(in, o, shards[i].device, shards[i].first, (int32_t)shards[i].count, tips, nodes, stats, R, &runs[i].ms);
-    if (runs[i].st) runs[i].err = g_phm_err;
-  };
-  std::vector<std::thread> th;
-  for (size_t i = 1; i < shards.size(); ++i) th.emplace_back(work, i);
-  work(0);
-  for (std::thread& t : th) t.join();
-  double ms = 0.0;
-  for (size_t i = 0; i < shards.size(); ++i) {
-    if (runs[i].st) return shards.size() == 1 ? fail(runs[i].st, runs[i].err) : fail(runs[i].st, "device " + std::to_string(shards[i].device) + ": " + runs[i].err);
-    ms = std::max(ms, runs[i].ms);
-  }
-  g_phm_last_kernel_ms = ms;      // the devices simulate side by side: the longest
-  return PHM_OK;
+  return run_shards(shards, [&](const phm_shard& sh, size_t) {
+    return sim_one_device(in, o, sh.device, sh.first, (int32_t)sh.count, tips, nodes, stats, R);
+  });
 }
 
 }  // extern "C"

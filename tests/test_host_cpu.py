@@ -201,6 +201,41 @@ def test_input_validation_happens_before_the_device():
         api.sumstatMCMC(zb, Q, pid, Om, 3)
 
 
+def test_multi_tree_driver_refuses_a_tree_without_paths():
+    """the per-tree heuristic of the mt drivers reads tree 0's paths: they are validated first"""
+    import ctypes as C
+    L = _lib.load()
+    Q = synth.config_Q(1)
+    Omega = 1.2 * float(np.max(-np.diag(Q)))
+    trees = synth.make_treelist(3, 10, Q, Omega, seed=5)
+    ftl = _lib.FlatTreeList(trees)
+    ftl.c[0].map_off = None
+    Qf = np.asfortranarray(Q)
+    B = np.asfortranarray(np.eye(2) + Q / Omega)
+    pid = np.full(2, 0.5)
+    prior = np.ones(4)
+    out = np.zeros((2, 9), order="F")
+    st = L.phm_maketreelistMCMCmt(ftl.c, ftl.n, 2, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double),
+                                  Omega, None, None, None, 2, _lib._p(prior, C.c_double), 4, C.byref(_lib.make_options()),
+                                  _lib._p(out, C.c_double))
+    assert st == 1
+
+
+def test_rate_updating_driver_refuses_a_null_tree_before_the_device():
+    import ctypes as C
+    L = _lib.load()
+    Q = np.asfortranarray(synth.config_Q(2))
+    n = Q.shape[0]
+    B = np.asfortranarray(np.eye(n) + Q / 1.0)
+    pid = np.full(n, 1.0 / n)
+    prior = np.ones(6)
+    out = np.zeros((2, n + n * n + 2 + 3 * (n // 2 - 1) + 1), order="F")
+    o = _lib.make_options(n_replicas=2, devices=[0, 0])
+    st = L.phm_maketreelistMCMCks(None, n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double), 1.0,
+                                  None, None, 0, 2, _lib._p(prior, C.c_double), 6, C.byref(o), _lib._p(out, C.c_double))
+    assert st == 1
+
+
 def test_newick_parser_numbers_nodes_like_ape_and_prunes():
     """phylomap_amd/newick.py: tips 1..T in order of appearance, internal nodes in pre-order, cladewise edge rows; dropping
     tips suppresses single-child nodes and adds their branch lengths."""
