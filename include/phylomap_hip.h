@@ -179,7 +179,10 @@ typedef struct phm_debug_options {
   int32_t q_timing;            /* 1 = the rate-updating drivers print the mean host time of the phases of an iteration to stderr */
   double  pade_pivot_min;      /* > 0: smallest pivot phm_expm_pade_mfma's unpivoted block elimination accepts (default 1e-3;
                                   1e300 sends every matrix to the pivoted kernel) */
-  int32_t reserved[4];
+  int32_t expect_chunk;        /* > 0: phm_expected_stats runs at most this many sites (rounded up to 64) per pass and this many
+                                  branches per branch-stage launch (default 0: sites by free HBM, branches by a 256 MB scratch);
+                                  the results do not depend on it */
+  int32_t reserved[3];
 } phm_debug_options;
 
 typedef struct phm_info {
@@ -308,6 +311,27 @@ int32_t phm_maketreelistEXP(          /* src/phylomap.cpp:3001, src/RcppExports.
 int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
                                const int32_t* observe, const phm_options* opt,
                                int32_t* tips, int32_t* nodes, double* stats);
+
+/* ---- exact conditional expectations given the tips ----
+ * For a fixed Q, per site (one tip vector): E[dwell_i | tips], E[N_ij | tips] summed over the tree and per branch, log p(tips | Q)
+ * and P(state of node k | tips), by an up (pruning) pass, a down (outside) pass and one uniformization integral per branch
+ * (Minin & Suchard 2008).  No sampling: the numbers every sampler's posterior mean converges to.
+ * Reads x->edge, x->edge_length, n_tips, n_node and x->states: n_tips values shared by every site (tips_per_replica = 0) or
+ * n_replicas x n_tips replica-major (tips_per_replica = 1).  A tip state is 0 (missing: every state allowed) or a value y in 1..n;
+ * the tip vector is 1 for the states a with observe[a] == y (observe NULL = identity).  pid: root prior (normalised here).
+ * Outputs, column-major with the site index fastest (R's array(dim = c(S, ...))), S = n_replicas sites:
+ *   stats: S x (n + n(n-1)): n dwell columns, then the off-diagonal counts in man/sumstatMCMC.Rd:18 order (1->2, 1->3, .., n->n-1);
+ *   loglik: S values; branch_stats: NULL or S x n_edge x (n + n(n-1)) by edge row; node_post: NULL or S x (n_tips + n_node) x n
+ *   by ape node id.
+ * Options: n_replicas, tips_per_replica, device, n_devices / devices[] (sharded by global site id; every row is the one-device
+ * row bit for bit); reduce must be 0; seed and replica_offset are ignored.  2 <= n <= 64; Q finite, off-diagonal >= 0, rows
+ * summing to 0 (1e-12 max|q|), some q_ii < 0; pid >= 0 with a positive sum; a strictly bifurcating tree with finite
+ * non-negative edge lengths and max(-q_ii) * t_b <= 1e6.  Every check runs before any device call.  A site whose tips are
+ * impossible under Q returns PHM_ERR_ZERO_PROB naming the site.  phm_last_kernel_ms: device time of the passes and the
+ * branch stage. */
+int32_t phm_expected_stats(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
+                           const int32_t* observe, const phm_options* opt,
+                           double* stats, double* loglik, double* branch_stats, double* node_post);
 
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q

@@ -25,6 +25,7 @@ EXPORTS = [
     "phm_engine_time_pruning", "phm_tree_orders",
     "phm_engine_create_multi", "phm_maketreelistMCMCmt", "phm_maketreelistMCMCksmt", "phm_engine_phase_ms",
     "phm_last_kernel_ms", "phm_set_debug_options", "phm_sparse_kernel_source", "phm_simulate_histories",
+    "phm_expected_stats",
 ]
 
 
@@ -61,7 +62,7 @@ class DebugOptions(C.Structure):
     """phm_debug_options: measurement / test aids, per thread (phm_set_debug_options)."""
     _fields_ = [("pruning_form", C.c_int32), ("phase_timing", C.c_int32), ("fail_recovery", C.c_int32),
                 ("branch_group", C.c_int32), ("level_groups", C.c_int32), ("q_timing", C.c_int32),
-                ("pade_pivot_min", C.c_double), ("reserved", C.c_int32 * 4)]
+                ("pade_pivot_min", C.c_double), ("expect_chunk", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class Info(C.Structure):
@@ -147,6 +148,9 @@ def load():
         L.phm_simulate_histories.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                              C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+        L.phm_expected_stats.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.phm_sparse_kernel_source.argtypes = [C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]
         for which, mirror in enumerate((Options, Info, Tree, Model, DebugOptions)):      # the ctypes mirrors must match the C layout
             if L.phm_struct_size(which) != C.sizeof(mirror):
@@ -226,14 +230,15 @@ MAPPING = {"auto": 0, "replicas": 1, "branches": 2, "tiles": 3}
 
 def set_debug_options(**kw):
     """Install this thread's phm_debug_options (measurement / test aids; no arguments = defaults): pruning_form, phase_timing,
-    fail_recovery, branch_group, level_groups, q_timing, pade_pivot_min."""
+    fail_recovery, branch_group, level_groups, q_timing, pade_pivot_min, expect_chunk."""
     d = DebugOptions()
     for k, v in kw.items():
         setattr(d, k, float(v) if k == "pade_pivot_min" else int(v))
     check(load().phm_set_debug_options(C.byref(d)))
 
 
-_DEBUG_KEYS = ("pruning_form", "phase_timing", "fail_recovery", "branch_group", "level_groups", "q_timing", "pade_pivot_min")
+_DEBUG_KEYS = ("pruning_form", "phase_timing", "fail_recovery", "branch_group", "level_groups", "q_timing", "pade_pivot_min",
+               "expect_chunk")
 
 
 def make_options(seed=0, n_replicas=1, replica_offset=0, reduce=False, tips_per_replica=False, device=-1,

@@ -260,3 +260,51 @@ def simulate_state_tree(z, Q, pid, observe=None, **opt):
     from . import synth
     tips, _ = simulate_histories(z, Q, pid, 1, observe=observe, **opt)
     return synth.with_tip_states(z, tips[0])
+
+
+def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, nodes=False, **opt):
+    """Exact E[dwell_i | tips, Q] and E[N_ij | tips, Q] -> phm_expected_stats: what the samplers'
+    posterior means converge to, with no sampling.  Reads ``z['edge']``, ``z['edge.length']``, ``z['Nnode']`` and, without
+    ``sites``, ``z['states']``.  ``sites``: S x n_tips tip states (0 = missing, else 1..n; e.g. the tips of
+    ``simulate_histories``), one site per row.  ``observe``: n values in 1..n, the tip state each true state is seen as.
+    Returns ``(stats, loglik)``, plus ``branch`` with ``per_branch=True`` and ``nodes`` with ``nodes=True``: stats
+    [S, n + n(n-1)] in man/sumstatMCMC.Rd:18 column order, loglik [S] = log p(tips | Q), branch [S, n_edge, n + n(n-1)] by
+    edge row, nodes [S, n_tips + Nnode, n] = P(state of node | tips) by ape node id.  Options: device, devices."""
+    L = _lib.load()
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+    n = Q.shape[0]
+    pid = np.ascontiguousarray(pid, dtype=np.float64)
+    edge = np.asarray(z["edge"], dtype=np.int32)
+    E = edge.shape[0]
+    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
+    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
+    Nn = int(z["Nnode"])
+    T = E - Nn + 1
+    if sites is None:
+        tips = np.ascontiguousarray(np.asarray(z["states"]).round(), dtype=np.int32).reshape(1, -1)
+    else:
+        tips = np.ascontiguousarray(np.atleast_2d(np.asarray(sites)).round(), dtype=np.int32)
+        opt = dict(opt, n_replicas=tips.shape[0], tips_per_replica=True)
+    if tips.shape[1] != T:
+        raise ValueError(f"tip states must have {T} columns")
+    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), _lib._p(tips.reshape(-1), C.c_int32),
+                     None, None, None)
+    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
+    if obs is not None and obs.size != n:
+        raise ValueError("observe must have one entry per state")
+    o = _lib.make_options(**opt)
+    S = max(1, int(o.n_replicas))                  # without sites: n_replicas sites that share z['states']
+    cols = n + n * (n - 1)
+    stats = np.zeros((S, cols), order="F")
+    ll = np.zeros(S)
+    br = np.zeros((S, E, cols), order="F") if per_branch else None
+    post = np.zeros((S, T + Nn, n), order="F") if nodes else None
+    _lib.check(L.phm_expected_stats(C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
+                                    _lib._p(obs, C.c_int32), C.byref(o), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
+                                    _lib._p(br, C.c_double), _lib._p(post, C.c_double)))
+    out = [stats, ll]
+    if per_branch:
+        out.append(br)
+    if nodes:
+        out.append(post)
+    return tuple(out)

@@ -1,0 +1,330 @@
+// phm_expect_api.cpp -- C-ABI of the exact conditional expectations (phm_expected_stats): validation and
+// everything that depends on the branch alone (level schedules, Poisson weights, Pade squaring counts) on the host, then per
+// device P(t_b) once, and per chunk of sites the up pass, the down pass and the branch stage (phm_expect.hip).
+#include "phm_internal.h"
+#include "phm_expect.h"
+
+namespace {
+
+constexpr double EX_TAIL = 0x1p-60;                    // omitted Poisson mass of a branch's truncated sum
+constexpr double EX_MAX_JUMP_MEAN = 1e6;               // max(-q_ii) t_b: the branch stage runs M_b ~ this many steps
+constexpr size_t EX_SCRATCH = size_t(256) << 20;       // per-(branch, site) values of one branch-stage launch
+
+// What every device of a call shares, checked and derived once on the host.
+struct ExInput {
+  int n = 0, T = 0, Nn = 0, E = 0, NT = 0, S = 0, cols = 0;
+  bool per_site = false;
+  const int32_t* states = nullptr;
+  double mu = 0.0;
+  phm::Schedule sched;
+  std::vector<double> Qr, B, qoff, pid, edge_length;
+  std::vector<int32_t> obs, sq, child_row;
+  std::vector<phm::UpStep> up;                          // grouped by height
+  std::vector<int32_t> up_off;
+  std::vector<phm::ExDown> down;                        // grouped by the depth of the child
+  std::vector<int32_t> down_off;
+  std::vector<int64_t> w_off;
+  std::vector<double> w;
+};
+
+// pmf of Poisson(x) at 0 .. M + 1 and M: the first m with sum_{k >= m + 2} pmf(k) <= 2^-60.  Computed outward from the mode with
+// pmf(mode) = 1 and normalised by the sum, so x in the thousands keeps full relative precision (no lgamma cancellation).
+void poisson_weights(double x, std::vector<double>& p, int& M) {
+  if (!(x > 0.0)) { p.assign({1.0, 0.0}); M = 0; return; }
+  const int64_t mode = (int64_t)std::floor(x), half = (int64_t)std::ceil(12.0 * std::sqrt(x)) + 40;
+  const int64_t hi = mode + half, lo = std::max<int64_t>(0, mode - half);
+  std::vector<double> r((size_t)hi + 1, 0.0);
+  r[mode] = 1.0;
+  for (int64_t k = mode; k < hi; ++k) r[k + 1] = r[k] * x / (double)(k + 1);
+  for (int64_t k = mode; k > lo; --k) r[k - 1] = r[k] * (double)k / x;
+  double sum = 0.0;
+  for (int64_t k = hi; k >= lo; --k) sum += r[k];
+  std::vector<double> tail((size_t)hi + 2, 0.0);
+  for (int64_t k = hi; k >= 0; --k) tail[k] = tail[k + 1] + r[k] / sum;
+  int64_t m = 0;
+  while (m + 2 <= hi && tail[m + 2] > EX_TAIL) ++m;
+  M = (int)m;
+  p.resize((size_t)m + 2);
+  for (int64_t k = 0; k <= m + 1; ++k) p[k] = r[k] / sum;
+}
+
+int32_t ex_validate(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* observe, const phm_options& o,
+                    const double* stats, const double* loglik, ExInput& in) {
+  const std::string fn = "phm_expected_stats: ";
+  if (!x || !Q || !pid || !stats || !loglik) return fail(PHM_ERR_BAD_INPUT, fn + "NULL argument (only observe, branch_stats and node_post may be NULL)");
+  if (n < 2 || n > phm::EX_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, fn + "n_states must be in 2..64");
+  if (o.reduce != 0) return fail(PHM_ERR_BAD_INPUT, fn + "reduce must be 0 (expectations are per site)");
+  if (o.n_replicas < 0 || o.n_replicas > (1 << 22)) return fail(PHM_ERR_BAD_INPUT, fn + "n_replicas must be in 0..4194304");
+  if (!x->edge || !x->edge_length || !x->states) return fail(PHM_ERR_BAD_INPUT, fn + "x$edge, x$edge.length and x$states are required");
+  std::string serr;
+  if (!phm::build_schedule(x->n_tips, x->n_node, x->n_edge, x->edge, in.sched, serr)) return fail(PHM_ERR_BAD_INPUT, "tree: " + serr);
+  in.n = n; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge; in.NT = in.T + in.Nn;
+  in.S = std::max(1, (int)o.n_replicas);
+  in.cols = n + n * (n - 1);
+  in.per_site = o.tips_per_replica != 0;
+  in.states = x->states;
+  for (int b = 0; b < in.E; ++b)
+    if (!std::isfinite(x->edge_length[b]) || x->edge_length[b] < 0.0)
+      return fail(PHM_ERR_BAD_INPUT, "edge.length must be finite and non-negative (edge row " + std::to_string(b + 1) + ")");
+  in.edge_length.assign(x->edge_length, x->edge_length + in.E);
+  double qmax = 0.0;
+  for (int i = 0; i < n * n; ++i) {
+    if (!std::isfinite(Q[i])) return fail(PHM_ERR_BAD_INPUT, "Q must be finite");
+    qmax = std::max(qmax, std::fabs(Q[i]));
+  }
+  cm_to_rm(Q, n, in.Qr);
+  in.qoff.assign((size_t)n * n, 0.0);
+  in.mu = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double row = 0.0;
+    for (int j = 0; j < n; ++j) {
+      const double q = in.Qr[(size_t)i * n + j];
+      row += q;
+      if (j == i) continue;
+      if (q < 0.0) return fail(PHM_ERR_BAD_INPUT, "Q: off-diagonal entries must be >= 0 (row " + std::to_string(i + 1) + ")");
+      in.qoff[(size_t)i * n + j] = q;
+    }
+    if (std::fabs(row) > 1e-12 * qmax) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " does not sum to 0");
+    in.mu = std::max(in.mu, -in.Qr[(size_t)i * n + i]);
+  }
+  if (!(in.mu > 0.0)) return fail(PHM_ERR_BAD_INPUT, "Q: no state is left at a positive rate (max(-q_ii) must be > 0)");
+  in.B.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) in.B[(size_t)i * n + j] = (i == j ? 1.0 : 0.0) + in.Qr[(size_t)i * n + j] / in.mu;
+  double psum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    if (!(pid[i] >= 0.0) || !std::isfinite(pid[i])) return fail(PHM_ERR_ZERO_PROB, "pid must be finite and non-negative");
+    psum += pid[i];
+  }
+  if (!(psum > 0.0)) return fail(PHM_ERR_ZERO_PROB, "pid sums to zero");
+  in.pid.resize(n);
+  for (int i = 0; i < n; ++i) in.pid[i] = pid[i] / psum;
+  in.obs.resize(n);
+  for (int i = 0; i < n; ++i) {
+    in.obs[i] = observe ? observe[i] : i + 1;
+    if (in.obs[i] < 1 || in.obs[i] > n) return fail(PHM_ERR_BAD_INPUT, "observe: values must be in 1..n");
+  }
+  const int64_t n_states_in = (int64_t)(in.per_site ? in.S : 1) * in.T;
+  for (int64_t k = 0; k < n_states_in; ++k)
+    if (in.states[k] < 0 || in.states[k] > n) return fail(PHM_ERR_BAD_INPUT, "x$states must be in 0..n (0: missing)");
+  for (int b = 0; b < in.E; ++b)
+    if (in.mu * in.edge_length[b] > EX_MAX_JUMP_MEAN)
+      return fail(PHM_ERR_UNSUPPORTED, "edge row " + std::to_string(b + 1) + ": max(-q_ii) * t_b above 1e6");
+  return PHM_OK;
+}
+
+// Squarings of expm(Q t) so that the Pade(6) argument has norm <= 1/2 (phm_expm_pade's own count, pade_squarings, is
+// arma::expmat's, which leaves norms up to ~log2 of the norm and costs 1e-13 .. 1e-12 in P on fast branches).
+int ex_squarings(const double* Q_rm, int n, double t) {
+  double norm = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double r = 0.0;
+    for (int j = 0; j < n; ++j) r += std::fabs(Q_rm[(size_t)i * n + j] * t);
+    norm = std::max(norm, r);
+  }
+  int s = 0;
+  while (norm > 0.5 && s < 1000) { norm *= 0.5; ++s; }
+  return s;
+}
+
+// Level schedules, child rows, Poisson weights and Pade squaring counts (host, once per call)
+void ex_prepare(ExInput& in) {
+  const phm::Schedule& s = in.sched;
+  const int T = in.T;
+  std::vector<int32_t> height(s.n_node, 0), up_of(s.n_node, -1);
+  std::vector<std::vector<int32_t>> by_h;
+  for (int k = 0; k < s.n_node; ++k) {
+    const phm::UpStep& u = s.up[k];
+    int h = 0;
+    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) h = std::max(h, height[u.child[c]] + 1);
+    height[u.parent] = h;
+    up_of[u.parent] = k;
+    if ((int)by_h.size() <= h) by_h.resize(h + 1);
+    by_h[h].push_back(k);
+  }
+  in.up_off.assign(1, 0);
+  for (auto& v : by_h) {
+    for (int k : v) in.up.push_back(s.up[k]);
+    in.up_off.push_back((int32_t)in.up.size());
+  }
+  auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
+  std::vector<int32_t> depth(s.n_node, 0);
+  std::vector<std::vector<phm::ExDown>> by_d;
+  in.child_row.assign(in.E, 0);
+  for (const phm::DownStep& d : s.down) {
+    const phm::UpStep& u = s.up[up_of[d.parent]];
+    const int side = u.edge[0] == d.edge ? 1 : 0;                // the sibling branch
+    const int dd = depth[d.parent] + 1;
+    if (d.child >= 0) depth[d.child] = dd;
+    phm::ExDown x = {};
+    x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
+    x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
+    if ((int)by_d.size() <= dd) by_d.resize(dd + 1);
+    by_d[dd].push_back(x);
+    in.child_row[d.edge] = x.child;
+  }
+  in.down_off.assign(1, 0);
+  for (auto& v : by_d) {
+    in.down.insert(in.down.end(), v.begin(), v.end());
+    in.down_off.push_back((int32_t)in.down.size());
+  }
+  in.w_off.assign(1, 0);
+  in.sq.resize(in.E);
+  std::vector<double> p;
+  for (int b = 0; b < in.E; ++b) {
+    int M = 0;
+    poisson_weights(in.mu * in.edge_length[b], p, M);
+    for (int m = 0; m <= M; ++m) in.w.push_back(p[m + 1] / in.mu);     // w_m = pois(m + 1; mu t_b) / mu
+    in.w_off.push_back((int64_t)in.w.size());
+    in.sq[b] = ex_squarings(in.Qr.data(), in.n, in.edge_length[b]);
+  }
+}
+
+struct Events {
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+template <typename T>
+hipError_t upload(DevBuf& d, const std::vector<T>& h) {
+  hipError_t e = d.alloc(sizeof(T) * h.size());
+  if (e == hipSuccess && !h.empty()) e = hipMemcpy(d.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
+  return e;
+}
+
+// Sites [first, first + count) of the call on one device; outputs point at the caller's full arrays (S sites per column).
+int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t count, double* stats, double* loglik,
+                      double* branch_stats, double* node_post) {
+  int32_t st = select_device(device);
+  if (st) return st;
+  const int n = in.n, T = in.T, E = in.E, NT = in.NT, cols = in.cols;
+  const size_t nn = (size_t)n * n, S = (size_t)in.S;
+  DevBuf dQ, dt, dsq, dwork, dP, derr, dB, dq, dpid, dobs, dup, ddown, dchild, dwoff, dw;
+  HIPCHK(upload(dQ, in.Qr)); HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dsq, in.sq));
+  HIPCHK(dwork.alloc(sizeof(double) * nn * 5 * E)); HIPCHK(dP.alloc(sizeof(double) * nn * E));
+  HIPCHK(derr.alloc(sizeof(uint32_t))); HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
+  HIPCHK(upload(dB, in.B)); HIPCHK(upload(dq, in.qoff)); HIPCHK(upload(dpid, in.pid)); HIPCHK(upload(dobs, in.obs));
+  HIPCHK(upload(dup, in.up)); HIPCHK(upload(ddown, in.down)); HIPCHK(upload(dchild, in.child_row));
+  HIPCHK(upload(dwoff, in.w_off)); HIPCHK(upload(dw, in.w));
+  Events ev;
+  for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreate(&x));
+  double kernel_ms = 0.0;
+  HIPCHK(hipEventRecord(ev.e[0], nullptr));
+  HIPCHK(phm::launch_expm_pade(n, dQ.as<double>(), dt.as<double>(), dsq.as<int32_t>(), E, dwork.as<double>(), dP.as<double>(),
+                               derr.as<uint32_t>(), nullptr));
+  HIPCHK(hipEventRecord(ev.e[1], nullptr));
+  uint32_t derrh = 0;
+  HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
+  if (derrh) return fail(PHM_ERR_BAD_INPUT, "phm_expected_stats: singular Pade denominator in expm(Q t_b)");
+  { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1])); kernel_ms += ms; }
+  dwork.reset();
+
+  // sites per chunk: what fits in half the free HBM next to the branch-stage scratch
+  const int chunk = g_phm_debug.expect_chunk;
+  const size_t per_site = sizeof(double) * ((size_t)NT * (2 * n + 2) + (size_t)E * (n + 1) + 2 + cols + (node_post ? (size_t)NT * n : 0)) + T;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 2 > EX_SCRATCH ? free_b / 2 - EX_SCRATCH : 0;
+  int64_t Sc_max = std::max<int64_t>(64, (int64_t)(budget / per_site) / 64 * 64);
+  if (chunk > 0) Sc_max = std::min<int64_t>(Sc_max, ((int64_t)chunk + 63) / 64 * 64);
+  Sc_max = std::min<int64_t>(Sc_max, (count + 63) / 64 * 64);
+  const size_t Spm = (size_t)Sc_max;
+  DevBuf dL, dsL, dO, dsO, dF, dsF, dll, dlam, dtips, dtot, dpost, dout;
+  HIPCHK(dL.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsL.alloc(sizeof(double) * NT * Spm));
+  HIPCHK(dO.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsO.alloc(sizeof(double) * NT * Spm));
+  HIPCHK(dF.alloc(sizeof(double) * (size_t)E * n * Spm)); HIPCHK(dsF.alloc(sizeof(double) * E * Spm));
+  HIPCHK(dll.alloc(sizeof(double) * Spm)); HIPCHK(dlam.alloc(sizeof(double) * Spm)); HIPCHK(dtips.alloc((size_t)T * Spm)); HIPCHK(dtot.alloc(sizeof(double) * cols * Spm));
+  if (node_post) HIPCHK(dpost.alloc(sizeof(double) * NT * n * Spm));
+  int ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, EX_SCRATCH / (sizeof(double) * cols * Spm)}));
+  if (chunk > 0) ne_max = std::min(ne_max, chunk);
+  HIPCHK(dout.alloc(sizeof(double) * cols * (size_t)ne_max * Spm));
+  std::vector<uint8_t> tips_h((size_t)T * Spm);
+  std::vector<double> ll_h(Spm);
+
+  for (int64_t c0 = 0; c0 < count; c0 += Sc_max) {
+    const int64_t Sc = std::min<int64_t>(Sc_max, count - c0);
+    const int Sp = (int)((Sc + 63) / 64 * 64);
+    const int64_t site0 = first + c0;                              // global id of this chunk's first site
+    std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);           // padding sites: every tip missing
+    for (int64_t k = 0; k < Sc; ++k) {
+      const int32_t* y = in.states + (in.per_site ? (site0 + k) * T : 0);
+      for (int t = 0; t < T; ++t) tips_h[(size_t)t * Sp + k] = (uint8_t)y[t];
+    }
+    HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Sp, hipMemcpyHostToDevice));
+    phm::ExPassParams pp;
+    pp.n = n; pp.n_tips = T; pp.Sp = Sp;
+    pp.P = dP.as<double>(); pp.L = dL.as<double>(); pp.sL = dsL.as<double>(); pp.O = dO.as<double>(); pp.sO = dsO.as<double>();
+    pp.F = dF.as<double>(); pp.sF = dsF.as<double>(); pp.ll = dll.as<double>(); pp.lam = dlam.as<double>();
+    HIPCHK(hipEventRecord(ev.e[0], nullptr));
+    HIPCHK(phm::launch_ex_tips(pp, dtips.as<uint8_t>(), dobs.as<int32_t>(), nullptr));
+    for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
+      HIPCHK(phm::launch_ex_up(pp, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
+    HIPCHK(phm::launch_ex_root(pp, T + in.sched.root, dpid.as<double>(), nullptr));
+    for (size_t l = 0; l + 1 < in.down_off.size(); ++l)
+      HIPCHK(phm::launch_ex_down(pp, ddown.as<phm::ExDown>() + in.down_off[l], in.down_off[l + 1] - in.down_off[l], nullptr));
+    if (node_post) HIPCHK(phm::launch_ex_post(pp, NT, dpost.as<double>(), nullptr));
+    HIPCHK(hipEventRecord(ev.e[1], nullptr));
+    HIPCHK(hipMemcpy(ll_h.data(), dll.p, sizeof(double) * Sc, hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < Sc; ++k)
+      if (!std::isfinite(ll_h[k]))
+        return fail(PHM_ERR_ZERO_PROB, "phm_expected_stats: site " + std::to_string(site0 + k + 1) + " has probability 0 under Q (its tips are impossible)");
+    std::memcpy(loglik + site0, ll_h.data(), sizeof(double) * Sc);
+    { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1])); kernel_ms += ms; }
+    if (node_post)                                                 // [state][row][Sp] -> site + S (row + NT state)
+      HIPCHK(hipMemcpy2D(node_post + site0, sizeof(double) * S, dpost.p, sizeof(double) * Sp, sizeof(double) * Sc, (size_t)NT * n,
+                         hipMemcpyDeviceToHost));
+
+    phm::ExBranchParams bp;
+    bp.n = n; bp.Sp = Sp; bp.mu = in.mu; bp.B = dB.as<double>(); bp.qoff = dq.as<double>(); bp.w_off = dwoff.as<int64_t>();
+    bp.w = dw.as<double>(); bp.child = dchild.as<int32_t>(); bp.L = pp.L; bp.sL = pp.sL; bp.F = pp.F; bp.sF = pp.sF; bp.lam = pp.lam;
+    bp.root = T + in.sched.root;
+    bp.out = dout.as<double>();
+    HIPCHK(hipMemset(dtot.p, 0, sizeof(double) * cols * Sp));
+    float branch_ms = 0.f;
+    for (int e0 = 0; e0 < E; e0 += ne_max) {
+      const int ne = std::min(ne_max, E - e0);
+      bp.e0 = e0; bp.n_out_edges = ne;
+      HIPCHK(hipEventRecord(ev.e[2], nullptr));
+      HIPCHK(phm::launch_ex_branch(bp, ne, nullptr));
+      HIPCHK(phm::launch_ex_reduce(dout.as<double>(), cols, ne, Sp, dtot.as<double>(), nullptr));
+      HIPCHK(hipEventRecord(ev.e[3], nullptr));
+      if (branch_stats)                                            // [col][e][Sp] -> site + S (edge + E col)
+        for (int col = 0; col < cols; ++col)
+          HIPCHK(hipMemcpy2D(branch_stats + site0 + S * ((size_t)e0 + (size_t)E * col), sizeof(double) * S,
+                             dout.as<double>() + (size_t)col * ne * Sp, sizeof(double) * Sp, sizeof(double) * Sc, ne,
+                             hipMemcpyDeviceToHost));
+      HIPCHK(hipEventSynchronize(ev.e[3]));
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
+      branch_ms += ms;
+    }
+    kernel_ms += branch_ms;
+    HIPCHK(hipMemcpy2D(stats + site0, sizeof(double) * S, dtot.p, sizeof(double) * Sp, sizeof(double) * Sc, cols,
+                       hipMemcpyDeviceToHost));
+  }
+  g_phm_last_kernel_ms = kernel_ms;
+  return PHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Sites are independent: with phm_options.n_devices > 1 device d computes a contiguous range of them (phm_plan_shards,
+// run_shards); every output row is the one-device row bit for bit.
+int32_t phm_expected_stats(const phm_tree* x, int32_t n_states, const double* Q, const double* pid, const int32_t* observe,
+                           const phm_options* opt, double* stats, double* loglik, double* branch_stats, double* node_post) {
+  const phm_options o = resolve_options(opt);
+  ExInput in;
+  int32_t st = ex_validate(x, n_states, Q, pid, observe, o, stats, loglik, in);
+  if (st) return st;
+  ex_prepare(in);
+  std::vector<phm_shard> shards;
+  st = phm_plan_shards(o, in.S, shards);
+  if (st) return st;
+  return run_shards(shards, [&](const phm_shard& sh, size_t) {
+    return ex_one_device(in, sh.device, sh.first, sh.count, stats, loglik, branch_stats, node_post);
+  });
+}
+
+}  // extern "C"
