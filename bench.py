@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: stochastic-map realisations/s (branch x site paths sampled per second).
 
-Contract: `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]`; for N > 1 the driver launches one rank per GPU with
-torch.distributed.run.  A *step* is one full MCMC sweep (pruning + node sampling + branch path resampling +
+Contract: `python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]`; for N > 1 the driver launches one rank per
+GPU with torch.distributed.run.  A *step* is one full MCMC sweep (pruning + node sampling + branch path resampling +
 sufficient statistics) over every replica resident on the GPU.
 
 Workload at N = 1 (and, replica-sharded, at N > 1): BASELINE.json configs[2] = C3, the configuration the north-star target
@@ -13,11 +13,16 @@ RCCL all-reduce of the K x cols statistics at the end.  Inputs are resident in H
 `--scaling weak` (default): every rank runs the same number of replicas, rank 0's choice broadcast to all;
 `--scaling strong`: the replicas one GPU holds are split over the ranks.
 
-`roofline` is SURVEY.md 8(d)'s whole-sweep figure, E * S * B_alg / (time of all kernels of one sweep), with one block per
-kernel of the sweep nested under it (`kernels`; `dominant_kernel` names the largest).  The same JSON line carries, at N = 1,
-the rate of ONE chain on the headline configuration (what the R call gets), one block per other BASELINE configuration
-(C2 streaming layout, C4 dense 61 states in the n + n^2 counting layout, C5 sparse 20 states, sumstatEXP on C1 and on a
-1 000-tip tree), the batched expm rates, and the CPU oracle timed on this box's host cores.
+A plain run does only what the headline needs: it sizes and builds the headline engine, runs the burn-in and warm-up sweeps,
+times the K steps, writes --dump-outputs and prints the result line.  That line carries `roofline`, SURVEY.md 8(d)'s
+whole-sweep figure, E * S * B_alg / (time of all kernels of one sweep), with one block per kernel of the sweep nested under it
+(`kernels`; `dominant_kernel` names the largest), all read from the timed sweeps themselves.
+
+`--full` adds everything that takes runs of its own, at N = 1: the CPU oracle timed on this box's host cores (`--no-cpu` skips
+it), the rate of ONE chain on the headline configuration (what the R call gets), and -- unless `--no-extras` -- the headline
+provisioned for its stated length, one block per other BASELINE configuration (C2 streaming layout, C4 dense 61 states in the
+n + n^2 counting layout, C5 sparse 20 states, sumstatEXP on C1 and on a 1 000-tip tree) and the batched expm rates.  A full
+run also writes the whole result to a detail file beside the line.
 
 `--dump-outputs DIR` writes, after the timed sweeps, what the headline path handed its caller for the LAST timed sweep:
 DIR/stats_last_step.npy, the float64 row of sufficient statistics summed over all replicas (n dwell sums, then the n (n - 1)
@@ -206,8 +211,10 @@ def main():
     ap.add_argument("--storage", type=int, default=2, help="replica mapping, dwell streams: 2 = two buffers (fastest), 1 = one ring (half the HBM)")
     ap.add_argument("--mapping", default="", choices=["", "replicas", "tiles", "branches", "auto"],
                     help="how a sweep is laid over the lanes (DESIGN.md 4b); default: tiles for C3/C4/C5, replicas for C2")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline line only (skip the C2/C4/C5/EXP/expm blocks)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own (N = 1): CPU baseline, one chain, the "
+                    "stated-length engine, the other configurations, expm; write the detail file")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the stated-length, C2/C4/C5/EXP/expm and one-shot blocks")
     ap.add_argument("--force-collective", action="store_true", help="exercise the statistics hand-over to torch at N=1")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the headline path's output of its last timed sweep to DIR/*.npy")
     args = ap.parse_args()
@@ -220,7 +227,7 @@ def main():
                          f"--master-port P bench.py --gpus {args.gpus} ...` (one rank per GPU)")
 
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu:          # before any HIP call: the all-cores figure forks workers
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:   # before any HIP call: the all-cores figure forks workers
         cpu[args.config] = cpu_baseline(args.config, target_s=4.0, all_cores=True)
         if not args.no_extras:
             for c in (2, 4, 5):
@@ -365,7 +372,7 @@ def main():
                                    units_per_launch=per_l, measured_triad_peak=MEASURED_TRIAD_GBS)
             if valu:
                 blk["roofline"]["valu_issue_frac"] = valu * (per / tr["units_per_sweep_in_pmc_run"]) * VALU_CLOCKS / (N_SIMD * NOMINAL_GHZ * 1e9 * info.last_run_ms / K / 1e3)
-            if n <= 4 and mapping == "replicas":
+            if args.full and n <= 4 and mapping == "replicas":     # a run of its own, after the timed sweeps
                 prune_ms = eng.time_pruning(8, stream) / 8.0
                 blk["pruning_sweep"] = {"kernel": f"mcmc_sweep_kernel<{n}> (up sweep only)", "ms_per_sweep": prune_ms,
                                         "alg_bytes_per_unit": 12 * n + 12, "bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -427,7 +434,7 @@ def main():
         print(f"bench.py: free HBM sized the run to {S_req} < {cap} replicas; pass --replicas to compare dumps across runs", file=sys.stderr)
     dumped = {}
     head, dt = measure(cfg, mapping, S, K, W, 0x5EED0000 + cfg, ipl=args.ipl, storage=sto,
-                       collective=(world > 1 or args.force_collective), offset=offset, outputs=dumped)
+                       collective=(world > 1 or args.force_collective), offset=offset, problem=(zc, Qc, pidc, Omc), outputs=dumped)
     if args.dump_outputs and rank == 0:
         os.makedirs(args.dump_outputs, exist_ok=True)
         for name, a in dumped.items():
@@ -465,7 +472,7 @@ def main():
             out["speedup_vs_cpu_1core"] = out["value"] / cpu[cfg]["value"]
             out["speedup_vs_cpu_1core_faithful"] = out["value"] / cpu[cfg]["faithful_value"]
             out["speedup_vs_cpu_all_cores"] = out["value"] / cpu[cfg]["all_cores"]["value"]
-    if rank == 0 and world == 1 and not args.no_extras and cfg == 3:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and cfg == 3:
         # The headline at the configuration's STATED length (BASELINE configs[2]: 10 000 iterations): an engine provisioned for
         # max_iters = 10 000 -- slot tail 0.05 / (S E 10 000) per draw, 10 000 statistics rows per tile -- of which the same
         # burn-in + warm-up + K sweeps run.  Fewer replicas fit per GiB than in the 37-sweep engine above; both are reported.
@@ -476,7 +483,7 @@ def main():
                                 "hbm_gib_resident": blk10["hbm_gib_resident"], "ms_per_sweep": blk10["ms_per_sweep"],
                                 "realisations_per_s": blk10["realisations_per_s"], "roofline_frac": blk10["roofline"]["frac"],
                                 "recoveries": blk10["recoveries"]}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         sc = one_chain(cfg, 400)
         if cfg in cpu:
             sc["speedup_vs_cpu_1core"] = sc["realisations_per_s"] / cpu[cfg]["value"]
@@ -495,7 +502,7 @@ def main():
                                     "wall_s": wall, "realisations_per_s_incl_setup_and_copies": head["branches"] * Sc * Nc / wall}
 
     # ---- the other BASELINE configurations, one block each (N = 1 only) -----------------------------------------------
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         blocks = {}
         # (cfg, mapping, cap, K, W, storage, variant, key): C4 in the n + n^2 counting layout (shortenerbf: self pairs counted) SURVEY 8 scopes it in
         plan = [(2, "replicas", 393216, 16, 8, 2, _lib.PHM_MCMC_BIGTREE, "C2"), (4, "tiles", 65536, 6, 6, 0, _lib.PHM_MCMC_BF, "C4bf"),
@@ -622,7 +629,7 @@ def main():
                                   "n61_mfma_tflops": 2 * 61 ** 3 * t61.size / (ms_m / 1e3) / 1e12, "mfma_f64_peak_tflops": MFMA_F64_PEAK_TFLOPS,
                                   "roofline": {"bound": "mfma", "kernel": "expm_eigen_mfma_kernel", "achieved": 2 * 61 ** 3 * t61.size / (ms_m / 1e3) / 1e12,
                                                "peak": MFMA_F64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": 2 * 61 ** 3 * t61.size / (ms_m / 1e3) / 1e12 / MFMA_F64_PEAK_TFLOPS}})
-    if rank == 0:
+    if args.full and rank == 0:
         # the full detail goes to a FILE (never to stdout / stderr: the driver keeps a few KB of their tail); stdout carries ONE compact line
         ddir = os.path.join(ROOT, "gpurun_out")
         try:
@@ -631,7 +638,11 @@ def main():
                 json.dump(out, f, indent=1)
         except OSError:
             pass
-        print(json.dumps(compact_line(out)), flush=True)
+    if rank == 0:
+        line = compact_line(out)
+        if not args.full:
+            line.pop("detail")      # a plain run writes no detail file
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

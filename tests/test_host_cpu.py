@@ -352,6 +352,14 @@ def test_bench_line_is_compact():
         assert k in line["roofline"], k
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] == 1
     assert "what" not in text and "prose" not in text
+    # a plain run (no --full) hands over the headline alone: the line carries the contract keys and the roofline, no secondary block
+    plain = {k: v for k, v in out.items() if k not in ("cpu_baseline", "speedup_vs_cpu_1core", "single_chain", "stated_length", "one_shot_call",
+                                                         "configs", "expm_per_s")}
+    line = bench.compact_line(plain)
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert k in line, k
+    for k in ("cpu_baseline", "single_chain", "stated_length", "others", "expm_per_s"):
+        assert k not in line, k
 
 
 def test_generated_sparse_pruning_kernel_compiles_for_gfx950():
