@@ -1,5 +1,6 @@
-// phm_engine.cpp -- the resident engine behind the C-ABI (include/phylomap_hip.h): input validation, HBM layout of the
-// three mappings of the sweep (phm_mcmc.hip / phm_tiles.hip / phm_narrow.hip, phm_wide.hip for n > 4), launches, statistics.
+// phm_engine.cpp -- the resident engine behind the C-ABI (include/phylomap_hip.h): input validation, the choice of the sweep's
+// layout (replicas / branches / tiles, each with kernels for n <= 4 and for 5..64 states: phm_engine::mapping), its HBM layout,
+// launches, statistics.
 //
 // Host-side counterpart of what the exported drivers do before and after their N-loop (src/phylomap.cpp:891-986, 822-870):
 // unpack `x`, set up B, allocate the statistics matrix.  Built with -ffp-contract=off: the B^k chain tables computed here
@@ -20,11 +21,23 @@ namespace {
 // do not fill the device (C1 / C2 / C3: 0.16 / 0.33 / 0.84 ms up to ~512 chains) -> the branch mapping up to
 //   S* = (0.008 levels + 2.6e-5 E - 0.02) / (5.2e-7 E)      (C3: 72 chains, measured crossover 64..96; C2: 208, measured 256..384;
 //                                                             C1: 1 020, measured > 1 024)
-inline int narrow_auto_max_replicas(const phm::Schedule& s) {
+// Levels of internal nodes from the root down (= the height levels of build_level_orders)
+int tree_levels(const phm::Schedule& s) {
   std::vector<int32_t> depth(s.n_node, 0);
   int levels = 1;
   for (const phm::DownStep& d : s.down)              // parents before children
     if (d.child >= 0) { depth[d.child] = depth[d.parent] + 1; levels = std::max(levels, depth[d.child] + 1); }
+  return levels;
+}
+// A DEEP tree (a ladder-like phylogeny): far more levels than a balanced tree of its size would have
+bool deep_tree(const phm::Schedule& s) {
+  int lg2 = 0;
+  while ((1 << lg2) < s.n_node + 1) ++lg2;
+  return tree_levels(s) > 4 * lg2 + 32;
+}
+
+inline int narrow_auto_max_replicas(const phm::Schedule& s) {
+  const int levels = tree_levels(s);
   const double E = (double)s.n_edge;
   // Round 4 (profiles/r04_probe_crossover.log): with its tree passes over level clusters, counter copies and a workgroup per tile for the
   // statistics, the (tile, branch) mapping with ONE tile costs 0.03 + 0.0068 levels + 6e-6 E ms per sweep (C1 / C2 / C3: 0.11 / 0.21 / 0.33);
@@ -43,14 +56,7 @@ constexpr int TILES_AUTO_MAX_REPLICAS = 262144;
 // the tile mapping's floor there: 1 200-tip ladder, 64 chains at 8 states 3.1 against 7.2 ms, 200 chains at 33 states 6.4 against
 // 17.9) to the tile mapping too early: 50 000 / E chains, at most 256; 256 on a deep tree.
 inline int wbranch_auto_max_replicas(const phm::Schedule& s) {
-  std::vector<int32_t> depth(s.n_node, 0);
-  int levels = 1;
-  for (const phm::DownStep& d : s.down)              // parents before children
-    if (d.child >= 0) { depth[d.child] = depth[d.parent] + 1; levels = std::max(levels, depth[d.child] + 1); }
-  int lg2 = 0;
-  while ((1 << lg2) < s.n_node + 1) ++lg2;
-  const bool deep = levels > 4 * lg2 + 32;
-  return deep ? 256 : std::max(1, std::min(256, 50000 / std::max(1, s.n_edge)));
+  return deep_tree(s) ? 256 : std::max(1, std::min(256, 50000 / std::max(1, s.n_edge)));
 }
 
 // Tail at which the fixed slots of the branch-parallel mappings are provisioned, per (replica, branch, sweep).  A slot that
@@ -67,26 +73,166 @@ bool ks_layout(int v) { return v == PHM_MCMC_KS || v == PHM_MCMC_BF || v == PHM_
 bool hidden_rates(int v) { return v == PHM_MCMC_KS || v == PHM_MCMC_KSMT; }                                         // parity tip masks
 bool normalised_variant(int v) { return v == PHM_MCMC_BIGTREE || v == PHM_MCMC_KS || v == PHM_MCMC_BF; }           // makePLnormalized :1085
 
-template <int NS>
-void fill_params(phm_engine* e, phm::McmcParams<NS>& p, const double* B2, const double* Bc, const double* scale,
-                 const double* pid, const phm_options& o) {
-  p.n_tips = e->sched.n_tips; p.n_node = e->sched.n_node; p.n_edge = e->sched.n_edge; p.root = e->sched.root;
-  p.n_tiles = e->tiles; p.n_rep = e->n_trees > 1 ? e->S_tree : e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset;
-  p.tiles_per_tree = e->n_trees > 1 ? e->tpt : 0; p.roots = e->d_roots.as<int32_t>();
+// The one n = 2 / 3 / 4 dispatch: f(the engine's SmallParams<n>); nothing for n > 4.
+template <typename F>
+void small_n(phm_engine* e, F&& f) {
+  if (e->n == 2) f(e->s2);
+  else if (e->n == 3) f(e->s3);
+  else if (e->n == 4) f(e->s4);
+}
+
+// The kernel parameters every layout has under the same names (tree 0's schedule; a list of trees sets its own n_rep)
+template <typename P>
+void fill_common(const phm_engine* e, const phm_options& o, P& p) {
+  const phm::Schedule& s = e->sched;
+  p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
+  p.n_tiles = e->tiles; p.n_rep = e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset;
   p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-  p.reduce = e->reduce; p.n_cols = e->dcols; p.ktab = phm::MCMC_KTAB; p.klong = std::max(e->nw_klong, phm::MCMC_KTAB); p.prune_only = 0;
-  p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant);
-  p.maskpow = e->d_mask.as<double>();
+  p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant); p.reduce = e->reduce; p.n_cols = e->dcols;
   p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
+  p.stats = e->d_stats.as<double>(); p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
+}
+
+// `need` bytes of HBM beside 64 MiB of head-room, out of `free_b` (hipMemGetInfo, queried by the caller before its allocations)
+int32_t check_hbm(size_t need, size_t free_b) {
+  if (need + (64u << 20) <= free_b) return PHM_OK;
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "engine needs %.2f GiB of HBM, %.2f GiB free (reduce n_replicas or max_iters)", need / 1073741824.0, free_b / 1073741824.0);
+  return fail(PHM_ERR_OOM, buf);
+}
+
+// statistics of max_iters sweeps: reduce ? [iter][tile][cols] : [iter][cols][n_rep_pad]
+size_t stats_bytes(const phm_engine* e) {
+  return e->reduce ? sizeof(double) * (size_t)e->max_iters * e->tiles * e->dcols : sizeof(double) * (size_t)e->max_iters * e->dcols * e->S_pad;
+}
+
+// the statistics, the error word, the segment counter (zeroed) and, reduce = 1, the reduced rows
+int32_t alloc_stats(phm_engine* e) {
+  HIPCHK(e->d_stats.alloc(stats_bytes(e)));
+  HIPCHK(e->d_err.alloc(sizeof(uint32_t))); HIPCHK(e->d_seg.alloc(sizeof(unsigned long long)));
+  if (e->reduce) HIPCHK(e->d_red.alloc(sizeof(double) * (size_t)e->max_iters * e->dcols));
+  HIPCHK(hipMemset(e->d_err.p, 0, sizeof(uint32_t)));
+  HIPCHK(hipMemset(e->d_seg.p, 0, sizeof(unsigned long long)));
+  HIPCHK(hipMemset(e->d_stats.p, 0, e->d_stats.bytes));
+  return PHM_OK;
+}
+
+// host vector -> a device buffer of its size
+template <typename T>
+hipError_t to_device(DevBuf& d, const std::vector<T>& v) {
+  hipError_t err = d.alloc(sizeof(T) * v.size());
+  return err == hipSuccess ? hipMemcpy(d.p, v.data(), d.bytes, hipMemcpyHostToDevice) : err;
+}
+
+// Per-branch slots of the branch-parallel mappings: 1 + Poisson(Omega t_b) segments in stationarity, provisioned far into the tail
+// (cap_tail, else default_slot_tail) because a slot has no neighbour to borrow from (an overflow is recovered by rebuilding with
+// doubled slots); longer caller-supplied paths get m0 on top.  Sets nw_total_cap, nw_klong and rows.
+struct SlotPlan {
+  std::vector<int32_t> cap;          // [E] slot size of every branch
+  std::vector<int64_t> off;          // [E + 1] first slot entry of every branch
+  std::vector<int32_t> order;        // branches, largest slot first (stable)
+  double max_seg = 0.0;              // most segments a branch is expected to hold (or holds in the caller's path)
+  double tree_len = 0.0;             // sum of the branch lengths
+};
+SlotPlan plan_slots(phm_engine* e, const phm_tree* x, double Omega, const phm_options& o, int32_t max_iters) {
+  const int E = e->sched.n_edge;
+  const double tail = o.cap_tail > 0.0 ? o.cap_tail : default_slot_tail(e->S, E, max_iters);
+  SlotPlan sp;
+  sp.cap.resize(E); sp.off.assign(E + 1, 0);
+  int max_cap = 0;
+  for (int b = 0; b < E; ++b) {
+    double tb = 0.0;
+    for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
+    sp.tree_len += tb;
+    const int m0 = x->map_off[b + 1] - x->map_off[b];
+    const int q = phm::poisson_capacity(Omega * tb, tail);
+    sp.cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
+    sp.max_seg = std::max(sp.max_seg, expected_segments(x, b, Omega));
+    max_cap = std::max(max_cap, sp.cap[b]);
+    sp.off[b + 1] = sp.off[b] + sp.cap[b];
+  }
+  sp.order.resize(E);
+  for (int b = 0; b < E; ++b) sp.order[b] = b;
+  std::stable_sort(sp.order.begin(), sp.order.end(), [&](int a, int b) { return sp.cap[a] > sp.cap[b]; });
+  e->nw_total_cap = sp.off[E];
+  e->nw_klong = max_cap + 1;
+  e->rows = sp.off[E];
+  return sp;
+}
+
+// Tip states of a single tree, 0-based: [n_tips] for every chain, or (tips_per_replica) [tile][n_tips][64] with replica r in lane
+// pad_index(r).  The padding lanes of dense tiles are run like replicas and get the last replica's tips; the unused lanes of sparse
+// ones (rpt < 64) any valid state.
+void single_tree_tips(phm_engine* e, const phm_tree* x) {
+  const int T = x->n_tips;
+  if (!e->tips_per_replica) {
+    e->tips_host.resize(T);
+    for (int t = 0; t < T; ++t) e->tips_host[t] = (uint8_t)(x->states[t] - 1);
+    return;
+  }
+  e->tips_host.assign((size_t)e->tiles * T * 64, (uint8_t)(x->states[0] - 1));
+  auto put = [&](int lane, int r) {
+    for (int t = 0; t < T; ++t) e->tips_host[((size_t)(lane / 64) * T + t) * 64 + (lane % 64)] = (uint8_t)(x->states[(size_t)r * T + t] - 1);
+  };
+  for (int r = 0; r < e->S; ++r) put(e->pad_index(r), r);
+  if (e->rpt == 64)
+    for (int r = e->S; r < e->S_pad; ++r) put(r, e->S - 1);
+}
+
+// A cluster plan of the tree passes (phm_sched.h) to the device; its tiers stay on the host (nw_tier_off)
+int32_t upload_cluster_plan(phm_engine* e, const phm::ClusterPlan& plan, bool item_off) {
+  e->nw_tier_off = plan.tier_off;
+  HIPCHK(to_device(e->d_nw_cl_nodes, plan.nodes));
+  if (item_off) HIPCHK(to_device(e->d_nw_cl_item_off, plan.item_off));
+  HIPCHK(to_device(e->d_nw_cl_lvl_ptr, plan.lvl_ptr));
+  HIPCHK(to_device(e->d_nw_cl_lvl_off, plan.lvl_off));
+  return PHM_OK;
+}
+
+// initial paths -> every replica of the (tile, item) mappings (makeabranch, src/phylomap.cpp:24-34, :901)
+int32_t init_tile_paths(phm_engine* e, const phm_tree* x) {
+  const int E = e->sched.n_edge;
+  DevBuf d_off, d_maps;
+  HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
+  HIPCHK(d_maps.alloc(sizeof(double) * (size_t)x->map_off[E]));
+  HIPCHK(hipMemcpy(d_off.p, x->map_off, d_off.bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_maps.p, x->maps, d_maps.bytes, hipMemcpyHostToDevice));
+  HIPCHK(phm::launch_tiles_init(E, e->tiles, e->rows, e->d_tl_slot.as<int32_t>(), d_off.as<int32_t>(), d_maps.as<double>(),
+                                e->d_dw0.as<double>(), e->d_mcount.as<uint16_t>(), nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  return PHM_OK;
+}
+
+// One n x cols result matrix (column-major) of iterations [iter0, iter0 + n): dev(i, c) is device column c of iteration iter0 + i.
+// Device and result columns coincide except for ks, whose parameter columns (recordQks) sit between the counters and the root
+// state and hold the Q each iteration ran under.
+template <typename Dev>
+void result_matrix(const phm_engine* e, int iter0, int n, double* mat, Dev dev) {
+  const int cols = e->cols, dcols = e->dcols;
+  for (int c = 0; c < dcols; ++c) {
+    const int oc = (dcols != cols && c == dcols - 1) ? cols - 1 : c;
+    for (int i = 0; i < n; ++i) mat[(size_t)oc * n + i] = dev(i, c);
+  }
+  if (dcols != cols)
+    for (int i = 0; i < n; ++i) {
+      const std::vector<double>& qp = e->qhist[iter0 + i];
+      for (size_t q = 0; q < qp.size(); ++q) mat[(size_t)(dcols - 1 + q) * n + i] = qp[q];
+    }
+}
+
+template <int NS>
+void fill_params(phm_engine* e, phm::McmcParams<NS>& p, const phm_options& o) {
+  fill_common(e, o, p);
+  p.n_rep = e->n_trees > 1 ? e->S_tree : e->S;
+  p.tiles_per_tree = e->n_trees > 1 ? e->tpt : 0; p.roots = e->d_roots.as<int32_t>();
+  p.ktab = phm::MCMC_KTAB; p.klong = std::max(e->nw_klong, phm::MCMC_KTAB); p.prune_only = 0;
+  p.maskpow = e->d_mask.as<double>();
   p.rows = e->rows;
-  for (int i = 0; i < NS * NS; ++i) { p.B2[i] = B2[i]; p.Bc[i] = Bc[i]; }
-  for (int i = 0; i < NS; ++i) { p.scale[i] = scale[i]; p.pid[i] = pid[i]; }
   p.up = e->d_up.as<phm::UpStep>(); p.down = e->d_down.as<phm::DownStep>();
   p.colpow = e->d_col.as<double>(); p.rowpow = e->d_row.as<double>();
   p.tips = e->d_tips.as<uint8_t>(); p.mcount = e->d_mcount.as<uint16_t>();
   p.dwell0 = e->d_dw0.as<double>(); p.dwell1 = e->ring ? nullptr : e->d_dw1.as<double>(); p.cursor = e->d_cursor.as<int32_t>();
-  p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>(); p.stats = e->d_stats.as<double>();
-  p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
+  p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>();
 }
 
 // Model matrices from R's column-major Q / B: dense B2, chain matrix Bc (thresholded for SPARSE), rexp scales, and the
@@ -123,7 +269,8 @@ int32_t upload_model(phm_engine* e) {
   const int n = e->n;
   // rows of the chain tables: every mapping keeps full-length tables in global memory (nw_klong > every possible segment
   // count); the replica kernels additionally stage the first MCMC_KTAB rows in LDS
-  const int ktab = (e->narrow || e->tiled) ? e->nw_klong : std::max(e->nw_klong, e->wide ? phm::WIDE_KTAB : phm::MCMC_KTAB);      // narrow covers both branch mappings (n <= 4 and 5..64)
+  const bool replicas = e->mapping == PHM_MAP_REPLICAS;
+  const int ktab = replicas ? std::max(e->nw_klong, e->wide() ? phm::WIDE_KTAB : phm::MCMC_KTAB) : e->nw_klong;
   const double* Bc = e->hBc.data();
   std::vector<double> col, row;
   build_chain_tables(Bc, n, ktab, col, row, n > 4);
@@ -133,7 +280,7 @@ int32_t upload_model(phm_engine* e) {
     for (int k = 1; k < ktab; ++k)
       host_chain_matvec(Bc, n, &maskpow[((size_t)(k - 1) * 2 + par) * n], &maskpow[((size_t)k * 2 + par) * n], n > 4);
   }
-  if (e->tiled && e->wide) {        // phm_wtiles.hip: table rows padded to an even length (16-byte rows), model in global memory
+  if (e->mapping == PHM_MAP_TILES && e->wide()) {        // phm_wtiles.hip: table rows padded to an even length (16-byte rows), model in global memory
     const int ldt = e->pwt.ldt;
     auto padded = [&](const std::vector<double>& src, size_t rows) {
       std::vector<double> dst(rows * ldt, 0.0);
@@ -252,7 +399,11 @@ int32_t upload_model(phm_engine* e) {
     }
     return PHM_OK;
   }
-  if (e->narrow || e->tiled) {      // tables long enough for every possible segment count, read from global memory / L2
+  if (replicas) {
+    HIPCHK(hipMemcpy(e->d_col.p, col.data(), sizeof(double) * col.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_row.p, row.data(), sizeof(double) * row.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_mask.p, maskpow.data(), sizeof(double) * maskpow.size(), hipMemcpyHostToDevice));
+  } else {      // tables long enough for every possible segment count, read from global memory / L2
     // through page-locked staging (the rate-updating drivers come here after every sweep: three pageable hipMemcpy calls were
     // ~50 us of a 190 us iteration)
     const size_t nc = col.size(), nr = row.size(), nm = maskpow.size();
@@ -261,7 +412,7 @@ int32_t upload_model(phm_engine* e) {
     std::memcpy(stage, col.data(), sizeof(double) * nc);
     std::memcpy(stage + nc, row.data(), sizeof(double) * nr);
     std::memcpy(stage + nc + nr, maskpow.data(), sizeof(double) * nm);
-    if (e->narrow && !e->wide) {                       // phm_narrow.hip: one block, one copy
+    if (e->mapping == PHM_MAP_BRANCHES && !e->wide()) {                       // phm_narrow.hip: one block, one copy
       HIPCHK(hipMemcpyAsync(e->d_nw_colL.p, stage, sizeof(double) * (nc + nr + nm), hipMemcpyHostToDevice, e->last_stream));
     } else {
       HIPCHK(hipMemcpyAsync(e->d_nw_colL.p, stage, sizeof(double) * nc, hipMemcpyHostToDevice, e->last_stream));
@@ -269,81 +420,58 @@ int32_t upload_model(phm_engine* e) {
       HIPCHK(hipMemcpyAsync(e->d_nw_maskL.p, stage + nc + nr, sizeof(double) * nm, hipMemcpyHostToDevice, e->last_stream));
     }
     HIPCHK(wait_stream(e->last_stream));               // one wait for the three: the next sweep may be enqueued on another stream
-    if (e->wide) {      // 5..64 states: the model matrices live in global memory
-      HIPCHK(hipMemcpy(e->d_B2.p, e->hB2.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_Bc.p, e->hBc.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_scale.p, e->hscale.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-      // A chain matrix with few non-zeros per row (tridiagonal amino-acid-style Q, the SPARSE threshold) also goes up in
-      // ELLPACK form: skipping exact zeros leaves every left-to-right row sum bit-identical (all terms are >= +0).
-      auto ellpack = [&](const std::vector<double>& M, DevBuf& dcol, DevBuf& dval, int32_t& w_out) -> int32_t {
-        int w = 0;
-        for (int i = 0; i < n; ++i) {
-          int cnt = 0;
-          for (int j = 0; j < n; ++j) cnt += M[(size_t)i * n + j] != 0.0;
-          w = std::max(w, cnt);
-        }
-        w_out = (w >= 1 && w <= phm::WB_ELL_MAX && 3 * w <= n) ? w : 0;
-        if (!w_out) return PHM_OK;
-        std::vector<int32_t> ec((size_t)n * w);
-        std::vector<double> ev((size_t)n * w, 0.0);
-        for (int i = 0; i < n; ++i) {
-          int t = 0;
-          for (int j = 0; j < n; ++j) if (M[(size_t)i * n + j] != 0.0) { ec[(size_t)i * w + t] = j; ev[(size_t)i * w + t] = M[(size_t)i * n + j]; ++t; }
-          for (; t < w; ++t) ec[(size_t)i * w + t] = i;
-        }
-        HIPCHK(hipMemcpy(dcol.p, ec.data(), sizeof(int32_t) * ec.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dval.p, ev.data(), sizeof(double) * ev.size(), hipMemcpyHostToDevice));
-        return PHM_OK;
-      };
-      { int32_t st = ellpack(e->hBc, e->d_ell_col, e->d_ell_val, e->pwb.ell_w); if (st) return st; }
-      {   // a banded chain matrix (half-bandwidth 1 or 2): neighbours through wave shifts (coop_matvec_band)
-        int hb = 0;
-        for (int i = 0; i < n; ++i)
-          for (int j = 0; j < n; ++j) if (e->hBc[(size_t)i * n + j] != 0.0) hb = std::max(hb, std::abs(i - j));
-        e->pwb.band_hb = (e->pwb.ell_w > 0 && hb >= 1 && hb <= 2 && e->sparse_req != 2) ? hb : 0;
-      }
-      { int32_t st = ellpack(e->hB2, e->d_ell2_col, e->d_ell2_val, e->pwb.ell2_w); if (st) return st; }
-      return PHM_OK;
-    }
-    auto refresh_n = [&](auto& p) {
-      for (int i = 0; i < n * n; ++i) { p.B2[i] = e->hB2[i]; p.Bc[i] = e->hBc[i]; }
-      for (int i = 0; i < n; ++i) p.scale[i] = e->hscale[i];
-    };
-    if (e->narrow) { if (n == 2) refresh_n(e->n2); if (n == 3) refresh_n(e->n3); if (n == 4) refresh_n(e->n4); }
-    else { if (n == 2) refresh_n(e->t2); if (n == 3) refresh_n(e->t3); if (n == 4) refresh_n(e->t4); }
-    return PHM_OK;
   }
-  HIPCHK(hipMemcpy(e->d_col.p, col.data(), sizeof(double) * col.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_row.p, row.data(), sizeof(double) * row.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_mask.p, maskpow.data(), sizeof(double) * maskpow.size(), hipMemcpyHostToDevice));
-  if (e->wide) {
+  if (e->wide()) {      // 5..64 states: the model matrices live in global memory
     HIPCHK(hipMemcpy(e->d_B2.p, e->hB2.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_Bc.p, e->hBc.data(), sizeof(double) * n * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(e->d_scale.p, e->hscale.data(), sizeof(double) * n, hipMemcpyHostToDevice));
   }
-  auto refresh = [&](auto& p) {
+  if (e->wide() && !replicas) {
+    // A chain matrix with few non-zeros per row (tridiagonal amino-acid-style Q, the SPARSE threshold) also goes up in
+    // ELLPACK form: skipping exact zeros leaves every left-to-right row sum bit-identical (all terms are >= +0).
+    auto ellpack = [&](const std::vector<double>& M, DevBuf& dcol, DevBuf& dval, int32_t& w_out) -> int32_t {
+      int w = 0;
+      for (int i = 0; i < n; ++i) {
+        int cnt = 0;
+        for (int j = 0; j < n; ++j) cnt += M[(size_t)i * n + j] != 0.0;
+        w = std::max(w, cnt);
+      }
+      w_out = (w >= 1 && w <= phm::WB_ELL_MAX && 3 * w <= n) ? w : 0;
+      if (!w_out) return PHM_OK;
+      std::vector<int32_t> ec((size_t)n * w);
+      std::vector<double> ev((size_t)n * w, 0.0);
+      for (int i = 0; i < n; ++i) {
+        int t = 0;
+        for (int j = 0; j < n; ++j) if (M[(size_t)i * n + j] != 0.0) { ec[(size_t)i * w + t] = j; ev[(size_t)i * w + t] = M[(size_t)i * n + j]; ++t; }
+        for (; t < w; ++t) ec[(size_t)i * w + t] = i;
+      }
+      HIPCHK(hipMemcpy(dcol.p, ec.data(), sizeof(int32_t) * ec.size(), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dval.p, ev.data(), sizeof(double) * ev.size(), hipMemcpyHostToDevice));
+      return PHM_OK;
+    };
+    { int32_t st = ellpack(e->hBc, e->d_ell_col, e->d_ell_val, e->pwb.ell_w); if (st) return st; }
+    {   // a banded chain matrix (half-bandwidth 1 or 2): neighbours through wave shifts (coop_matvec_band)
+      int hb = 0;
+      for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) if (e->hBc[(size_t)i * n + j] != 0.0) hb = std::max(hb, std::abs(i - j));
+      e->pwb.band_hb = (e->pwb.ell_w > 0 && hb >= 1 && hb <= 2 && e->sparse_req != 2) ? hb : 0;
+    }
+    { int32_t st = ellpack(e->hB2, e->d_ell2_col, e->d_ell2_val, e->pwb.ell2_w); if (st) return st; }
+  }
+  auto refresh = [&](auto& p) {      // the model inside the by-value blocks of the n <= 4 kernels (their only source: every setup ends here)
     for (int i = 0; i < n * n; ++i) { p.B2[i] = e->hB2[i]; p.Bc[i] = e->hBc[i]; }
-    for (int i = 0; i < n; ++i) p.scale[i] = e->hscale[i];
+    for (int i = 0; i < n; ++i) { p.scale[i] = e->hscale[i]; p.pid[i] = e->hpid[i]; }
   };
-  if (n == 2) refresh(e->p2);
-  if (n == 3) refresh(e->p3);
-  if (n == 4) refresh(e->p4);
+  small_n(e, [&](auto& sp) { refresh(sp.rep); refresh(sp.br); refresh(sp.tl); });
   return PHM_OK;
 }
 
 // Branch-parallel engine state (phm_narrow.hip): level schedules, CSR branch slots, long chain tables, per-replica buffers.
 template <int NS>
 void fill_narrow_params(phm_engine* e, phm::NarrowParams<NS>& p, const phm_options& o) {
-  const phm::Schedule& s = e->sched;
-  p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
-  p.n_rep = e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset; p.n_tiles = e->tiles;
-  p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-  p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant); p.reduce = e->reduce; p.n_cols = e->dcols;
+  fill_common(e, o, p);
   p.klong = e->nw_klong; p.n_wide = e->nw_n_wide; p.cluster_async = e->nw_cluster_async;
-  p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
   p.total_cap = e->nw_total_cap;
-  for (int i = 0; i < NS * NS; ++i) { p.B2[i] = e->hB2[i]; p.Bc[i] = e->hBc[i]; }
-  for (int i = 0; i < NS; ++i) { p.scale[i] = e->hscale[i]; p.pid[i] = e->hpid[i]; }
   p.cl_nodes = e->d_nw_cl_nodes.as<phm::ClusterNode>(); p.cl_item_off = e->d_nw_cl_item_off.as<int32_t>();
   p.cl_lvl_ptr = e->d_nw_cl_lvl_ptr.as<int32_t>(); p.cl_lvl_off = e->d_nw_cl_lvl_off.as<int32_t>();
   p.down_lv = e->d_nw_down_lv.as<phm::DownStep>(); p.walk_off = e->d_nw_walk_off.as<int32_t>();
@@ -356,9 +484,8 @@ void fill_narrow_params(phm_engine* e, phm::NarrowParams<NS>& p, const phm_optio
   p.tips = e->d_tips.as<uint8_t>();
   p.mcount = e->d_nw_mcount.as<int32_t>(); p.dw[0] = e->d_nw_dwA.as<double>(); p.dw[1] = e->d_nw_dwB.as<double>();
   p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>(); p.part = e->d_nw_part.as<double>();
-  p.rowbuf = e->d_nw_rowbuf.as<double>(); p.stats = e->d_stats.as<double>();
+  p.rowbuf = e->d_nw_rowbuf.as<double>();
   p.dmap = e->d_nw_dmap.as<uint16_t>();
-  p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
   p.host_row = nullptr;
   if (e->S == 1 && !e->reduce && e->pin_row.reserve(sizeof(double) * (e->dcols + 2)) == hipSuccess) {
     void* dp = nullptr;
@@ -397,10 +524,8 @@ int32_t build_level_orders(phm_engine* e) {
     for (int k = 0; k < Nn; ++k) up_order[pu[height[s.up[k].parent]]++] = k;
     for (int k = 0; k < E; ++k) down_order[pd[edepth[k]]++] = k;
   }
-  HIPCHK(e->d_nw_up_order.alloc(sizeof(int32_t) * Nn)); HIPCHK(e->d_nw_down_order.alloc(sizeof(int32_t) * E));
-  HIPCHK(hipMemcpy(e->d_nw_up_order.p, up_order.data(), e->d_nw_up_order.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_down_order.p, down_order.data(), e->d_nw_down_order.bytes, hipMemcpyHostToDevice));
-  if (!e->wide) {
+  HIPCHK(to_device(e->d_nw_up_order, up_order)); HIPCHK(to_device(e->d_nw_down_order, down_order));
+  if (!e->wide()) {
     // phm_narrow.hip: the sampling steps themselves (no indirection).  Edges that lead to an INTERNAL node first, grouped by depth
     // level -- the walk propagates states only along those --, then the tip edges; boundaries of the first part in nw_walk_off
     std::vector<phm::DownStep> walk_lv;
@@ -414,88 +539,60 @@ int32_t build_level_orders(phm_engine* e) {
     for (int i = 0; i < E; ++i) if (s.down[down_order[i]].child < 0) walk_lv.push_back(s.down[down_order[i]]);
     std::vector<int32_t> edge_parent(E);
     for (int i = 0; i < E; ++i) edge_parent[s.down[i].edge] = s.down[i].parent;
-    HIPCHK(e->d_nw_down_lv.alloc(sizeof(phm::DownStep) * E));
-    HIPCHK(hipMemcpy(e->d_nw_down_lv.p, walk_lv.data(), e->d_nw_down_lv.bytes, hipMemcpyHostToDevice));
-    HIPCHK(e->d_nw_walk_off.alloc(sizeof(int32_t) * e->nw_walk_off.size()));
-    HIPCHK(hipMemcpy(e->d_nw_walk_off.p, e->nw_walk_off.data(), e->d_nw_walk_off.bytes, hipMemcpyHostToDevice));
-    HIPCHK(e->d_nw_edge_parent.alloc(sizeof(int32_t) * E));
-    HIPCHK(hipMemcpy(e->d_nw_edge_parent.p, edge_parent.data(), e->d_nw_edge_parent.bytes, hipMemcpyHostToDevice));
+    HIPCHK(to_device(e->d_nw_down_lv, walk_lv));
+    HIPCHK(to_device(e->d_nw_walk_off, e->nw_walk_off));
+    HIPCHK(to_device(e->d_nw_edge_parent, edge_parent));
   }
-  HIPCHK(e->d_nw_up_off.alloc(sizeof(int32_t) * e->nw_up_off.size())); HIPCHK(e->d_nw_down_off.alloc(sizeof(int32_t) * e->nw_down_off.size()));
-  HIPCHK(hipMemcpy(e->d_nw_up_off.p, e->nw_up_off.data(), e->d_nw_up_off.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_down_off.p, e->nw_down_off.data(), e->d_nw_down_off.bytes, hipMemcpyHostToDevice));
+  HIPCHK(to_device(e->d_nw_up_off, e->nw_up_off)); HIPCHK(to_device(e->d_nw_down_off, e->nw_down_off));
   return PHM_OK;
 }
 
 int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, const phm_options& o, int32_t max_iters) {
   const phm::Schedule& s = e->sched;
   const int E = s.n_edge, T = s.n_tips, Nn = s.n_node, n = e->n, S = e->S;
-  // One slot per branch: 1 + Poisson(Omega t_b) segments in stationarity, provisioned far into the tail because a slot
-  // has no neighbour to borrow from (default_slot_tail; an overflow is recovered by rebuilding with doubled slots); longer caller-supplied paths get m0 on top.
-  const double tail = o.cap_tail > 0.0 ? o.cap_tail : default_slot_tail(S, E, max_iters);
-  e->nw_off.assign(E + 1, 0);
-  std::vector<int32_t> cap(E);
-  int max_cap = 0, n_wide = 0;
-  for (int b = 0; b < E; ++b) {
-    double tb = 0.0;
-    for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
-    const int m0 = x->map_off[b + 1] - x->map_off[b];
-    const int q = phm::poisson_capacity(model->Omega * tb, tail);
-    cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
-    max_cap = std::max(max_cap, cap[b]);
-    e->nw_off[b + 1] = e->nw_off[b] + cap[b];
+  // One slot per branch (plan_slots)
+  const SlotPlan sp = plan_slots(e, x, model->Omega, o, max_iters);
+  e->nw_off = sp.off;
+  int n_wide = 0;
+  for (int b = 0; b < E; ++b)
     if (expected_segments(x, b, model->Omega) >= phm::NARROW_WIDE_SEGMENTS) ++n_wide;      // a long path: the wave-wide walk (phm_narrow.hip)
-  }
   e->nw_n_wide = std::max(n_wide, std::min(E / 16, phm::NARROW_LONG));
   // long chains: the pruning clusters without level barriers (phm_narrow.hip); debug pruning_form 1 / 2 = never / always
   e->nw_cluster_async = e->dbg.pruning_form == 2 || (e->dbg.pruning_form == 0 && n_wide > 0);
-  e->nw_total_cap = e->nw_off[E];
-  e->nw_klong = max_cap + 1;
-  e->rows = e->nw_total_cap;
-  std::vector<int32_t> border(E);
-  for (int b = 0; b < E; ++b) border[b] = b;
-  std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return cap[a] > cap[b]; });
 
   // tips: [T] shared, or [replica][T]
   if (e->tips_per_replica) {
     e->tips_host.resize((size_t)S * T);
     for (int r = 0; r < S; ++r) for (int t = 0; t < T; ++t) e->tips_host[(size_t)r * T + t] = (uint8_t)(x->states[(size_t)r * T + t] - 1);
   } else {
-    e->tips_host.resize(T);
-    for (int t = 0; t < T; ++t) e->tips_host[t] = (uint8_t)(x->states[t] - 1);
+    single_tree_tips(e, x);
   }
 
-  const size_t stats_bytes = e->reduce ? sizeof(double) * (size_t)max_iters * e->tiles * e->dcols
-                                       : sizeof(double) * (size_t)max_iters * e->dcols * e->S_pad;
   const size_t dw_bytes = sizeof(double) * (size_t)S * e->nw_total_cap;
   const size_t tab = (size_t)e->nw_klong * n * n;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const size_t part_cols = e->wide ? (size_t)n + 1 : (size_t)n + n * n + 1;      // n > 4: counters go through atomics, not per branch
-  const size_t n_dw = e->wide ? 3 : 2;             // n <= 4: the branch kernel needs no merged-segment scratch (phm_narrow.hip)
+  const size_t part_cols = e->wide() ? (size_t)n + 1 : (size_t)n + n * n + 1;      // n > 4: counters go through atomics, not per branch
+  const size_t n_dw = e->wide() ? 3 : 2;             // n <= 4: the branch kernel needs no merged-segment scratch (phm_narrow.hip)
   // transition maps of the sampling sweep: n <= 4 two 16-bit maps per (chain, edge); 5..64 states n bytes per (chain, edge) while that stays below 256 MiB
-  const size_t dmap_bytes = e->wide ? (((size_t)S * E * n <= (256u << 20)) ? (size_t)S * E * n : 0) : 2 * sizeof(uint16_t) * (size_t)S * E;
+  const size_t dmap_bytes = e->wide() ? (((size_t)S * E * n <= (256u << 20)) ? (size_t)S * E * n : 0) : 2 * sizeof(uint16_t) * (size_t)S * E;
   const size_t small_bytes = (size_t)S * (E * (sizeof(int32_t) + 2) + (size_t)Nn * (sizeof(double) * n + 1)) + sizeof(phm::ClusterNode) * (size_t)Nn + 16 * (size_t)E;   // segment counts, end states, PL, node states, schedules
-  const size_t need = n_dw * dw_bytes + (e->wide ? (size_t)S * e->nw_total_cap : 0) + stats_bytes + dmap_bytes + small_bytes +
-                      sizeof(double) * (3 * tab + (size_t)S * E * part_cols + (e->wide ? 2 * (size_t)S * e->dcols : 0));
-  if (need + (64u << 20) > free_b) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "engine needs %.2f GiB of HBM, %.2f GiB free (reduce n_replicas or max_iters)", need / 1073741824.0, free_b / 1073741824.0);
-    return fail(PHM_ERR_OOM, buf);
-  }
-  HIPCHK(e->d_up.alloc(sizeof(phm::UpStep) * Nn)); HIPCHK(e->d_down.alloc(sizeof(phm::DownStep) * E));
-  { int32_t lst = build_level_orders(e); if (lst) return lst; }
-  HIPCHK(e->d_nw_border.alloc(sizeof(int32_t) * E)); HIPCHK(e->d_nw_off.alloc(sizeof(int64_t) * (E + 1)));
-  if (e->wide) {
+  const size_t need = n_dw * dw_bytes + (e->wide() ? (size_t)S * e->nw_total_cap : 0) + stats_bytes(e) + dmap_bytes + small_bytes +
+                      sizeof(double) * (3 * tab + (size_t)S * E * part_cols + (e->wide() ? 2 * (size_t)S * e->dcols : 0));
+  if (int32_t st = check_hbm(need, free_b)) return st;
+  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  if (int32_t st = build_level_orders(e)) return st;
+  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_nw_off, e->nw_off));
+  if (e->wide()) {
     HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
     HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * n));
   } else {      // n <= 4: the three tables in one block (colL | rowL | maskL): a model update is ONE host-to-device copy
     HIPCHK(e->d_nw_colL.alloc(sizeof(double) * (2 * tab + (size_t)e->nw_klong * 2 * n)));
   }
-  HIPCHK(e->d_tips.alloc(e->tips_host.size()));
+  HIPCHK(to_device(e->d_tips, e->tips_host));
   HIPCHK(e->d_nw_mcount.alloc(sizeof(int32_t) * (size_t)S * E));
   HIPCHK(e->d_nw_dwA.alloc(dw_bytes)); HIPCHK(e->d_nw_dwB.alloc(dw_bytes));
-  if (e->wide) {
+  if (e->wide()) {
     HIPCHK(e->d_nw_mstate.alloc((size_t)S * e->nw_total_cap));
     HIPCHK(e->d_nw_mlen.alloc(dw_bytes));
     HIPCHK(e->d_nw_estate.alloc((size_t)S * E * 2));
@@ -504,35 +601,17 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
   HIPCHK(e->d_nstate.alloc((size_t)S * Nn));
   HIPCHK(e->d_nw_part.alloc(sizeof(double) * (size_t)S * E * part_cols));
   HIPCHK(e->d_nw_rowbuf.alloc(sizeof(double) * (size_t)S * e->dcols));
-  if (!e->wide) {
+  if (!e->wide()) {
     HIPCHK(e->d_nw_dmap.alloc(sizeof(uint16_t) * (size_t)S * E));
     HIPCHK(e->d_nw_dmap_edge.alloc(sizeof(uint16_t) * (size_t)S * E));
     phm::ClusterPlan plan;                           // pruning sweep of phm_narrow.hip: subtrees in tiers
     phm::build_cluster_plan(s, phm::NARROW_CLUSTER_NODES, plan);
-    e->nw_tier_off = plan.tier_off;
-    HIPCHK(e->d_nw_cl_nodes.alloc(sizeof(phm::ClusterNode) * plan.nodes.size()));
-    HIPCHK(e->d_nw_cl_item_off.alloc(sizeof(int32_t) * plan.item_off.size()));
-    HIPCHK(e->d_nw_cl_lvl_ptr.alloc(sizeof(int32_t) * plan.lvl_ptr.size()));
-    HIPCHK(e->d_nw_cl_lvl_off.alloc(sizeof(int32_t) * plan.lvl_off.size()));
-    HIPCHK(hipMemcpy(e->d_nw_cl_nodes.p, plan.nodes.data(), e->d_nw_cl_nodes.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_nw_cl_item_off.p, plan.item_off.data(), e->d_nw_cl_item_off.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_nw_cl_lvl_ptr.p, plan.lvl_ptr.data(), e->d_nw_cl_lvl_ptr.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_nw_cl_lvl_off.p, plan.lvl_off.data(), e->d_nw_cl_lvl_off.bytes, hipMemcpyHostToDevice));
+    if (int32_t st = upload_cluster_plan(e, plan, true)) return st;
   }
-  HIPCHK(e->d_stats.alloc(stats_bytes));
-  HIPCHK(e->d_err.alloc(sizeof(uint32_t))); HIPCHK(e->d_seg.alloc(sizeof(unsigned long long)));
-  if (e->reduce) HIPCHK(e->d_red.alloc(sizeof(double) * (size_t)max_iters * e->dcols));
+  if (int32_t st = alloc_stats(e)) return st;
   e->bytes = (int64_t)(n_dw * dw_bytes + e->d_nw_mstate.bytes + e->d_nw_part.bytes + e->d_PL.bytes + e->d_stats.bytes + e->d_red.bytes +
                        sizeof(double) * 3 * tab + e->d_nw_mcount.bytes + e->d_nw_dmap.bytes + e->d_nw_dmap_edge.bytes + e->d_nw_cl_nodes.bytes +
-                       (e->wide ? dmap_bytes : 0));
-  HIPCHK(hipMemcpy(e->d_up.p, s.up.data(), e->d_up.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_down.p, s.down.data(), e->d_down.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_border.p, border.data(), e->d_nw_border.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_off.p, e->nw_off.data(), e->d_nw_off.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_tips.p, e->tips_host.data(), e->tips_host.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(e->d_err.p, 0, sizeof(uint32_t)));
-  HIPCHK(hipMemset(e->d_seg.p, 0, sizeof(unsigned long long)));
-  HIPCHK(hipMemset(e->d_stats.p, 0, stats_bytes));
+                       (e->wide() ? dmap_bytes : 0));
   HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
   {   // initial paths (makeabranch, src/phylomap.cpp:24-34, :901) into every chain's first buffer
     std::vector<double> init((size_t)e->nw_total_cap, 0.0);
@@ -546,10 +625,8 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
       HIPCHK(hipMemcpy(e->d_nw_mcount.as<int32_t>() + (size_t)r * E, m0.data(), sizeof(int32_t) * E, hipMemcpyHostToDevice));
     }
   }
-  if (n == 2) fill_narrow_params<2>(e, e->n2, o);
-  if (n == 3) fill_narrow_params<3>(e, e->n3, o);
-  if (n == 4) fill_narrow_params<4>(e, e->n4, o);
-  if (e->wide) {      // 5..64 states: one wave per (replica, branch), lanes = states (phm_wbranch.hip)
+  small_n(e, [&](auto& p) { fill_narrow_params(e, p.br, o); });
+  if (e->wide()) {      // 5..64 states: one wave per (replica, branch), lanes = states (phm_wbranch.hip)
     HIPCHK(e->d_wb_cnt.alloc(sizeof(double) * (size_t)S * e->dcols));
     // transition maps of the sampling sweep (n bytes per edge and chain) while they stay small beside the paths; beyond: one launch
     // per depth level
@@ -558,15 +635,10 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     HIPCHK(e->d_B2.alloc(sizeof(double) * n * n)); HIPCHK(e->d_Bc.alloc(sizeof(double) * n * n));
     HIPCHK(e->d_ell_col.alloc(sizeof(int32_t) * n * phm::WB_ELL_MAX)); HIPCHK(e->d_ell_val.alloc(sizeof(double) * n * phm::WB_ELL_MAX));
     HIPCHK(e->d_ell2_col.alloc(sizeof(int32_t) * n * phm::WB_ELL_MAX)); HIPCHK(e->d_ell2_val.alloc(sizeof(double) * n * phm::WB_ELL_MAX));
-    HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(e->d_pid.alloc(sizeof(double) * n));
-    HIPCHK(hipMemcpy(e->d_pid.p, e->hpid.data(), e->d_pid.bytes, hipMemcpyHostToDevice));
+    HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(to_device(e->d_pid, e->hpid));
     phm::WideBranchParams& p = e->pwb;
-    p.n_states = n; p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
-    p.n_rep = e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset; p.n_tiles = e->tiles;
-    p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-    p.sparse = (e->variant == PHM_MCMC_SPARSE); p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant);
-    p.count_self = p.ks; p.reduce = e->reduce; p.n_cols = e->dcols; p.klong = e->nw_klong;
-    p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
+    fill_common(e, o, p);
+    p.n_states = n; p.sparse = (e->variant == PHM_MCMC_SPARSE); p.count_self = p.ks; p.klong = e->nw_klong;
     p.total_cap = e->nw_total_cap;
     p.B2 = e->d_B2.as<double>(); p.Bc = e->d_Bc.as<double>(); p.scale = e->d_scale.as<double>(); p.pid = e->d_pid.as<double>();
     p.ell_w = 0; p.band_hb = 0; p.ell_col = e->d_ell_col.as<int32_t>(); p.ell_val = e->d_ell_val.as<double>();
@@ -580,9 +652,8 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     p.dw[0] = e->d_nw_dwA.as<double>(); p.dw[1] = e->d_nw_dwB.as<double>(); p.mlen = e->d_nw_mlen.as<double>();
     p.mstate = e->d_nw_mstate.as<uint8_t>(); p.estate = e->d_nw_estate.as<uint8_t>();
     p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>(); p.part = e->d_nw_part.as<double>();
-    p.cnt = e->d_wb_cnt.as<double>(); p.rowbuf = e->d_nw_rowbuf.as<double>(); p.stats = e->d_stats.as<double>();
+    p.cnt = e->d_wb_cnt.as<double>(); p.rowbuf = e->d_nw_rowbuf.as<double>();
     p.dmap = e->d_nw_dmap.as<uint8_t>();
-    p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
   }
   return PHM_OK;
 }
@@ -597,20 +668,13 @@ inline int tiles_cnt_copies(int tiles) {
 // Engine state of the wave-per-(tile, branch) mapping (phm_tiles.hip).
 template <int NS>
 void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& o) {
-  const phm::Schedule& s = e->sched;
-  p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
-  p.n_tiles = e->tiles; p.n_rep = e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset;
-  p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-  p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant); p.reduce = e->reduce; p.n_cols = e->dcols;
+  fill_common(e, o, p);
   p.klong = e->nw_klong;
   // branches per wave of the branch kernel: one while waves are scarce, up to 16 once there are 65 536 of them anyway
-  p.group = (int32_t)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)e->tiles * s.n_edge / 65536));
-  p.n_groups = (s.n_edge + p.group - 1) / p.group;
+  p.group = (int32_t)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)e->tiles * p.n_edge / 65536));
+  p.n_groups = (p.n_edge + p.group - 1) / p.group;
   p.n_chunks = (p.n_groups + phm::TILES_CHUNK - 1) / phm::TILES_CHUNK;
-  p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
   p.rows = e->nw_total_cap;
-  for (int i = 0; i < NS * NS; ++i) { p.B2[i] = e->hB2[i]; p.Bc[i] = e->hBc[i]; }
-  for (int i = 0; i < NS; ++i) { p.scale[i] = e->hscale[i]; p.pid[i] = e->hpid[i]; }
   p.up = e->d_up.as<phm::UpStep>(); p.down = e->d_down.as<phm::DownStep>();
   p.up_order = e->d_nw_up_order.as<int32_t>(); p.down_order = e->d_nw_down_order.as<int32_t>();
   p.branch_order = e->d_nw_border.as<int32_t>(); p.slot = e->d_tl_slot.as<int32_t>();
@@ -624,54 +688,31 @@ void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& 
   p.pdw = e->d_tl_pdw.as<double>(); p.pchunk = e->d_tl_pchunk.as<double>(); p.cnt = e->d_tl_cnt.as<uint32_t>();
   p.cnt_copies = tiles_cnt_copies(e->tiles);
   p.pseg = e->d_tl_pseg.as<uint32_t>(); p.segprev = e->d_tl_segprev.as<uint32_t>();
-  p.stats = e->d_stats.as<double>(); p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
+}
+
+// The slots of the (tile, item) mappings: rows of 64 lanes, addressed with 32-bit offsets (phm_tiles.hip, phm_wtiles.hip)
+int32_t tile_slots(phm_engine* e, const SlotPlan& sp) {
+  const int E = e->sched.n_edge;
+  e->tl_slot.assign(E + 1, 0);
+  for (int b = 0; b < E; ++b) {
+    if (sp.cap[b] >= (1 << 23)) return fail(PHM_ERR_UNSUPPORTED, "branch too long: a slot of the (tile, branch) mapping exceeds 4 GB");
+    if (sp.off[b + 1] > 0x7fffff00ll / 64) return fail(PHM_ERR_UNSUPPORTED, "tree too large: dwell rows per replica tile exceed 32-bit indexing");
+    e->tl_slot[b + 1] = (int32_t)sp.off[b + 1];
+  }
+  return PHM_OK;
 }
 
 int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, const phm_options& o, int32_t max_iters) {
   const phm::Schedule& s = e->sched;
-  const int E = s.n_edge, T = s.n_tips, Nn = s.n_node, n = e->n, tiles = e->tiles;
+  const int E = s.n_edge, Nn = s.n_node, n = e->n, tiles = e->tiles;
   // One slot of rows per branch; a row holds the 64 replicas of the tile, so the slot must take the LARGEST of 64 segment
-  // counts: provisioned at default_slot_tail per replica, branch and sweep (1 + Poisson(Omega t_b), plus the caller's initial length).
-  const double tail = o.cap_tail > 0.0 ? o.cap_tail : default_slot_tail(e->S, E, max_iters);
-  e->tl_slot.assign(E + 1, 0);
-  std::vector<int32_t> cap(E);
-  int max_cap = 0;
-  double max_seg = 0.0;                             // most segments a branch is expected to hold (or holds in the caller's path)
-  int64_t rows = 0;
-  for (int b = 0; b < E; ++b) {
-    double tb = 0.0;
-    for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
-    const int m0 = x->map_off[b + 1] - x->map_off[b];
-    const int q = phm::poisson_capacity(model->Omega * tb, tail);
-    cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
-    max_seg = std::max(max_seg, expected_segments(x, b, model->Omega));
-    if (cap[b] >= (1 << 23)) return fail(PHM_ERR_UNSUPPORTED, "branch too long: a slot of the (tile, branch) mapping exceeds 4 GB");   // 32-bit offsets, phm_tiles.hip
-    max_cap = std::max(max_cap, cap[b]);
-    rows += cap[b];
-    if (rows > 0x7fffff00ll / 64) return fail(PHM_ERR_UNSUPPORTED, "tree too large: dwell rows per replica tile exceed 32-bit indexing");
-    e->tl_slot[b + 1] = (int32_t)rows;
-  }
-  e->nw_total_cap = rows;
-  e->nw_klong = max_cap + 1;
-  e->rows = rows;
-  std::vector<int32_t> border(E);
-  for (int b = 0; b < E; ++b) border[b] = b;
-  std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return cap[a] > cap[b]; });
-
-  if (e->tips_per_replica) {
-    e->tips_host.assign((size_t)tiles * T * 64, 0);
-    for (int r = 0; r < e->S_pad; ++r) {
-      const int src = r < e->S ? r : e->S - 1;
-      for (int t = 0; t < T; ++t) e->tips_host[((size_t)(r / 64) * T + t) * 64 + (r % 64)] = (uint8_t)(x->states[(size_t)src * T + t] - 1);
-    }
-  } else {
-    e->tips_host.resize(T);
-    for (int t = 0; t < T; ++t) e->tips_host[t] = (uint8_t)(x->states[t] - 1);
-  }
+  // counts: provisioned at default_slot_tail per replica, branch and sweep (plan_slots).
+  const SlotPlan sp = plan_slots(e, x, model->Omega, o, max_iters);
+  if (int32_t st = tile_slots(e, sp)) return st;
+  const int64_t rows = e->rows;
+  single_tree_tips(e, x);
 
   const int n_chunks = (E + phm::TILES_CHUNK - 1) / phm::TILES_CHUNK;
-  const size_t stats_bytes = e->reduce ? sizeof(double) * (size_t)max_iters * tiles * e->dcols
-                                       : sizeof(double) * (size_t)max_iters * e->dcols * e->S_pad;
   const size_t dw_bytes = sizeof(double) * (size_t)tiles * rows * 64;
   const size_t tab = (size_t)e->nw_klong * n * n;
   const size_t pdw_bytes = sizeof(double) * (size_t)tiles * E * n * 64;
@@ -681,22 +722,18 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
 #ifndef PHM_TILES_LONG_SEGMENTS
 #define PHM_TILES_LONG_SEGMENTS 48.0
 #endif
-  const bool long_paths = max_seg > PHM_TILES_LONG_SEGMENTS;
+  const bool long_paths = sp.max_seg > PHM_TILES_LONG_SEGMENTS;
   const size_t ms_bytes = long_paths ? (size_t)tiles * rows * 64 : 0;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + stats_bytes + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
-  if (need + (64u << 20) > free_b) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "engine needs %.2f GiB of HBM, %.2f GiB free (reduce n_replicas or max_iters)", need / 1073741824.0, free_b / 1073741824.0);
-    return fail(PHM_ERR_OOM, buf);
-  }
-  HIPCHK(e->d_up.alloc(sizeof(phm::UpStep) * Nn)); HIPCHK(e->d_down.alloc(sizeof(phm::DownStep) * E));
-  { int32_t lst = build_level_orders(e); if (lst) return lst; }
-  HIPCHK(e->d_nw_border.alloc(sizeof(int32_t) * E)); HIPCHK(e->d_tl_slot.alloc(sizeof(int32_t) * (E + 1)));
+  const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + stats_bytes(e) + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
+  if (int32_t st = check_hbm(need, free_b)) return st;
+  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  if (int32_t st = build_level_orders(e)) return st;
+  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_tl_slot, e->tl_slot));
   HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
   HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * n));
-  HIPCHK(e->d_tips.alloc(e->tips_host.size()));
+  HIPCHK(to_device(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes)); HIPCHK(e->d_dw1.alloc(dw_bytes));
   if (long_paths) HIPCHK(e->d_wt_mstate.alloc(ms_bytes));
@@ -707,58 +744,30 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   HIPCHK(e->d_tl_pchunk.alloc(sizeof(double) * (size_t)tiles * n_chunks * n * 64));
   HIPCHK(e->d_tl_cnt.alloc(sizeof(uint32_t) * (size_t)tiles * tiles_cnt_copies(tiles) * n * n * 64));
   HIPCHK(e->d_tl_pseg.alloc(sizeof(uint32_t) * (size_t)tiles * n_chunks * 64)); HIPCHK(e->d_tl_segprev.alloc(sizeof(uint32_t) * tiles));
-  HIPCHK(e->d_stats.alloc(stats_bytes));
-  HIPCHK(e->d_err.alloc(sizeof(uint32_t))); HIPCHK(e->d_seg.alloc(sizeof(unsigned long long)));
-  if (e->reduce) HIPCHK(e->d_red.alloc(sizeof(double) * (size_t)max_iters * e->dcols));
+  if (int32_t st = alloc_stats(e)) return st;
   e->bytes = (int64_t)(2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + e->d_stats.bytes + e->d_red.bytes + e->d_mcount.bytes + e->d_tl_pchunk.bytes +
                        sizeof(double) * 3 * tab);
-  HIPCHK(hipMemcpy(e->d_up.p, s.up.data(), e->d_up.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_down.p, s.down.data(), e->d_down.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_border.p, border.data(), e->d_nw_border.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_tl_slot.p, e->tl_slot.data(), e->d_tl_slot.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_tips.p, e->tips_host.data(), e->tips_host.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(e->d_err.p, 0, sizeof(uint32_t)));
-  HIPCHK(hipMemset(e->d_seg.p, 0, sizeof(unsigned long long)));
-  HIPCHK(hipMemset(e->d_stats.p, 0, stats_bytes));
   HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
   HIPCHK(hipMemset(e->d_tl_cnt.p, 0, e->d_tl_cnt.bytes));
-  {   // initial paths -> every replica (makeabranch, src/phylomap.cpp:24-34, :901)
-    DevBuf d_off, d_maps;
-    HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
-    HIPCHK(d_maps.alloc(sizeof(double) * (size_t)x->map_off[E]));
-    HIPCHK(hipMemcpy(d_off.p, x->map_off, d_off.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_maps.p, x->maps, d_maps.bytes, hipMemcpyHostToDevice));
-    HIPCHK(phm::launch_tiles_init(E, tiles, rows, e->d_tl_slot.as<int32_t>(), d_off.as<int32_t>(), d_maps.as<double>(),
-                                  e->d_dw0.as<double>(), e->d_mcount.as<uint16_t>(), nullptr));
-    HIPCHK(hipDeviceSynchronize());
+  if (int32_t st = init_tile_paths(e, x)) return st;
+  {
     std::vector<uint32_t> segprev(tiles);
     for (int t = 0; t < tiles; ++t) segprev[t] = (uint32_t)((int64_t)x->map_off[E] * std::min(64, e->S - t * 64));
     HIPCHK(hipMemcpy(e->d_tl_segprev.p, segprev.data(), e->d_tl_segprev.bytes, hipMemcpyHostToDevice));
   }
   // few tiles (the sites of an alignment): the two tree passes over clusters cut by height, one launch per tier, instead of one per
   // level (phm_tiles.h); phm_debug_options.level_groups: 1 = never, 2 = always, 3 = always, clusters cut by subtree size
-  // A DEEP tree (a ladder-like phylogeny: far more height levels than a balanced tree of its size would have) at any tile count:
-  // clusters cut by subtree size, a handful of tiers instead of a launch per level and pass (2 000-tip ladder at 8 192 replicas:
-  // 4 002 launches, 19.2 ms per sweep -> 19 launches, 9.0 ms; bands of eight levels 10.8).
+  // A DEEP tree at any tile count: clusters cut by subtree size, a handful of tiers instead of a launch per level and pass (2 000-tip
+  // ladder at 8 192 replicas: 4 002 launches, 19.2 ms per sweep -> 19 launches, 9.0 ms; bands of eight levels 10.8).
   e->nw_tier_off.clear();
-  int lg2 = 0;
-  while ((1 << lg2) < Nn + 1) ++lg2;
-  const bool deep = (int)e->nw_up_off.size() - 1 > 4 * lg2 + 32;
+  const bool deep = deep_tree(s);
   if (e->dbg.level_groups >= 2 || (e->dbg.level_groups == 0 && (deep || (int64_t)tiles * Nn <= phm::TILES_CL_MAX_WORK))) {
     phm::ClusterPlan plan;
     if (e->dbg.level_groups == 3 || (e->dbg.level_groups == 0 && deep)) phm::build_cluster_plan(s, phm::TILES_CL_NODES, plan);      // subtrees by size
     else phm::build_band_plan(s, TILES_CL_BAND, plan);
-    e->nw_tier_off = plan.tier_off;
-    HIPCHK(e->d_nw_cl_nodes.alloc(sizeof(phm::ClusterNode) * plan.nodes.size()));
-    HIPCHK(e->d_nw_cl_lvl_ptr.alloc(sizeof(int32_t) * plan.lvl_ptr.size()));
-    HIPCHK(e->d_nw_cl_lvl_off.alloc(sizeof(int32_t) * plan.lvl_off.size()));
-    HIPCHK(hipMemcpy(e->d_nw_cl_nodes.p, plan.nodes.data(), e->d_nw_cl_nodes.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_nw_cl_lvl_ptr.p, plan.lvl_ptr.data(), e->d_nw_cl_lvl_ptr.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_nw_cl_lvl_off.p, plan.lvl_off.data(), e->d_nw_cl_lvl_off.bytes, hipMemcpyHostToDevice));
+    if (int32_t st = upload_cluster_plan(e, plan, false)) return st;
   }
-  if (n == 2) fill_tile_params<2>(e, e->t2, o);
-  if (n == 3) fill_tile_params<3>(e, e->t3, o);
-  if (n == 4) fill_tile_params<4>(e, e->t4, o);
+  small_n(e, [&](auto& p) { fill_tile_params(e, p.tl, o); });
   return PHM_OK;
 }
 
@@ -766,98 +775,47 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
 // statistics in integer accumulators per tile.
 int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, const phm_options& o, int32_t max_iters) {
   const phm::Schedule& s = e->sched;
-  const int E = s.n_edge, T = s.n_tips, Nn = s.n_node, n = e->n, tiles = e->tiles;
-  const double tail = o.cap_tail > 0.0 ? o.cap_tail : default_slot_tail(e->S, E, max_iters);
-  e->tl_slot.assign(E + 1, 0);
-  std::vector<int32_t> cap(E);
-  int max_cap = 0;
-  int64_t rows = 0;
-  double tree_len = 0.0;
-  for (int b = 0; b < E; ++b) {
-    double tb = 0.0;
-    for (int i = x->map_off[b]; i < x->map_off[b + 1]; ++i) tb += x->maps[i];
-    tree_len += tb;
-    const int m0 = x->map_off[b + 1] - x->map_off[b];
-    const int q = phm::poisson_capacity(model->Omega * tb, tail);
-    cap[b] = (std::max(q, m0 + q - 1) + 2) * e->cap_boost;
-    if (cap[b] >= (1 << 23)) return fail(PHM_ERR_UNSUPPORTED, "branch too long: a slot of the (tile, branch) mapping exceeds 4 GB");
-    max_cap = std::max(max_cap, cap[b]);
-    rows += cap[b];
-    if (rows > 0x7fffff00ll / 64) return fail(PHM_ERR_UNSUPPORTED, "tree too large: dwell rows per replica tile exceed 32-bit indexing");
-    e->tl_slot[b + 1] = (int32_t)rows;
-  }
-  e->nw_total_cap = rows;
-  e->nw_klong = max_cap + 1;
-  e->rows = rows;
-  std::vector<int32_t> border(E);
-  for (int b = 0; b < E; ++b) border[b] = b;
-  std::stable_sort(border.begin(), border.end(), [&](int a, int b) { return cap[a] > cap[b]; });
-
-  if (e->tips_per_replica) {
-    e->tips_host.assign((size_t)tiles * T * 64, 0);
-    for (int r = 0; r < e->S_pad; ++r) {
-      const int src = r < e->S ? r : e->S - 1;
-      for (int t = 0; t < T; ++t) e->tips_host[((size_t)(r / 64) * T + t) * 64 + (r % 64)] = (uint8_t)(x->states[(size_t)src * T + t] - 1);
-    }
-  } else {
-    e->tips_host.resize(T);
-    for (int t = 0; t < T; ++t) e->tips_host[t] = (uint8_t)(x->states[t] - 1);
-  }
+  const int E = s.n_edge, Nn = s.n_node, n = e->n, tiles = e->tiles;
+  const SlotPlan sp = plan_slots(e, x, model->Omega, o, max_iters);
+  if (int32_t st = tile_slots(e, sp)) return st;
+  const int64_t rows = e->rows;
+  single_tree_tips(e, x);
 
   const int ldt = (n + 1) & ~1;
   if ((uint64_t)e->nw_klong * n * ldt * sizeof(double) >= (1ull << 32))      // the kernels address a chain table with 32-bit byte offsets
     return fail(PHM_ERR_UNSUPPORTED, "branch too long for the lane-per-replica mapping: a chain table would exceed 4 GB");
-  const size_t stats_bytes = e->reduce ? sizeof(double) * (size_t)max_iters * tiles * e->dcols
-                                       : sizeof(double) * (size_t)max_iters * e->dcols * e->S_pad;
   const size_t dw_bytes = sizeof(double) * (size_t)tiles * rows * 64;
   const size_t tab = (size_t)e->nw_klong * n * ldt;
   const size_t pl_bytes = sizeof(double) * (size_t)tiles * Nn * n * 64;
   const size_t cnt_bytes = sizeof(uint32_t) * (size_t)tiles * n * n * 64;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const int nblk_need = (n + 7) / 8, ldb_need = (nblk_need + 1) & ~1;
-  const size_t tot_bytes = sizeof(double) * (size_t)e->nw_klong * n * n * ldb_need;                     // blkL: running sums of the forward draws
+  const int nblk = (n + 7) / 8, ldb = (nblk + 1) & ~1;
+  const size_t tot_bytes = sizeof(double) * (size_t)e->nw_klong * n * n * ldb;                          // blkL: running sums of the forward draws
   const size_t acc_bytes = sizeof(unsigned long long) * (size_t)tiles * (n + 1) * 64;                   // dwfx + segacc
   const size_t red_bytes = e->reduce ? sizeof(double) * (size_t)max_iters * e->dcols : 0;
-  const size_t need = 2 * dw_bytes + dw_bytes / 8 + pl_bytes + cnt_bytes + stats_bytes + tot_bytes + acc_bytes + red_bytes + sizeof(double) * 3 * tab +
+  const size_t need = 2 * dw_bytes + dw_bytes / 8 + pl_bytes + cnt_bytes + stats_bytes(e) + tot_bytes + acc_bytes + red_bytes + sizeof(double) * 3 * tab +
                       (size_t)tiles * (5 * (size_t)E + Nn + 8 * (size_t)n) * 64;
-  if (need + (64u << 20) > free_b) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "engine needs %.2f GiB of HBM, %.2f GiB free (reduce n_replicas or max_iters)", need / 1073741824.0, free_b / 1073741824.0);
-    return fail(PHM_ERR_OOM, buf);
-  }
-  HIPCHK(e->d_up.alloc(sizeof(phm::UpStep) * Nn)); HIPCHK(e->d_down.alloc(sizeof(phm::DownStep) * E));
-  { int32_t lst = build_level_orders(e); if (lst) return lst; }
-  // A DEEP tree (tiles_setup has the rule): the band pruning kernel and the node draws for n <= 32 run over subtree clusters, a launch per
-  // tier instead of one per level and pass (phm_wtiles.hip); phm_debug_options.level_groups: 1 = never, 2 / 3 = always
+  if (int32_t st = check_hbm(need, free_b)) return st;
+  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  if (int32_t st = build_level_orders(e)) return st;
+  // A DEEP tree (deep_tree): the band pruning kernel and the node draws for n <= 32 run over subtree clusters, a launch per tier
+  // instead of one per level and pass (phm_wtiles.hip); phm_debug_options.level_groups: 1 = never, 2 / 3 = always
   e->nw_tier_off.clear();
-  {
-    int lg2 = 0;
-    while ((1 << lg2) < Nn + 1) ++lg2;
-    const bool deep = (int)e->nw_up_off.size() - 1 > 4 * lg2 + 32;
-    if (n <= 32 && (e->dbg.level_groups >= 2 || (e->dbg.level_groups == 0 && deep))) {
-      phm::ClusterPlan plan;
-      phm::build_cluster_plan(s, phm::TILES_CL_NODES, plan);
-      e->nw_tier_off = plan.tier_off;
-      HIPCHK(e->d_nw_cl_nodes.alloc(sizeof(phm::ClusterNode) * plan.nodes.size()));
-      HIPCHK(e->d_nw_cl_lvl_ptr.alloc(sizeof(int32_t) * plan.lvl_ptr.size()));
-      HIPCHK(e->d_nw_cl_lvl_off.alloc(sizeof(int32_t) * plan.lvl_off.size()));
-      HIPCHK(hipMemcpy(e->d_nw_cl_nodes.p, plan.nodes.data(), e->d_nw_cl_nodes.bytes, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_nw_cl_lvl_ptr.p, plan.lvl_ptr.data(), e->d_nw_cl_lvl_ptr.bytes, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(e->d_nw_cl_lvl_off.p, plan.lvl_off.data(), e->d_nw_cl_lvl_off.bytes, hipMemcpyHostToDevice));
-    }
+  if (n <= 32 && (e->dbg.level_groups >= 2 || (e->dbg.level_groups == 0 && deep_tree(s)))) {
+    phm::ClusterPlan plan;
+    phm::build_cluster_plan(s, phm::TILES_CL_NODES, plan);
+    if (int32_t st = upload_cluster_plan(e, plan, false)) return st;
   }
-  HIPCHK(e->d_nw_border.alloc(sizeof(int32_t) * E)); HIPCHK(e->d_tl_slot.alloc(sizeof(int32_t) * (E + 1)));
+  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_tl_slot, e->tl_slot));
   HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
   HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * ldt));
   HIPCHK(e->d_wt_B2.alloc(sizeof(double) * (size_t)n * ldt)); HIPCHK(e->d_Bc.alloc(sizeof(double) * n * n));
   HIPCHK(e->d_wt_B2band.alloc(sizeof(double) * (size_t)n * (2 * phm::WT_BAND_MAX + 1)));
-  const int nblk = (n + 7) / 8, ldb = (nblk + 1) & ~1;
-  HIPCHK(e->d_wt_totL.alloc(sizeof(double) * (size_t)e->nw_klong * n * n * ldb));
+  HIPCHK(e->d_wt_totL.alloc(tot_bytes));
   HIPCHK(e->d_wt_pair_slot.alloc(sizeof(int16_t) * (size_t)n * n)); HIPCHK(e->d_wt_slot_col.alloc(sizeof(int32_t) * phm::WT_MAX_SLOTS));
-  HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(e->d_pid.alloc(sizeof(double) * n));
-  HIPCHK(hipMemcpy(e->d_pid.p, e->hpid.data(), e->d_pid.bytes, hipMemcpyHostToDevice));
-  HIPCHK(e->d_tips.alloc(e->tips_host.size()));
+  HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(to_device(e->d_pid, e->hpid));
+  HIPCHK(to_device(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes)); HIPCHK(e->d_dw1.alloc(dw_bytes));
   HIPCHK(e->d_tl_estate.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
@@ -873,39 +831,17 @@ int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     HIPCHK(hipMemset(e->d_wt_dwfx_tile.p, 0, e->d_wt_dwfx_tile.bytes));
     HIPCHK(hipMemset(e->d_wt_cnt_tile.p, 0, e->d_wt_cnt_tile.bytes));
   }
-  HIPCHK(e->d_stats.alloc(stats_bytes));
-  HIPCHK(e->d_err.alloc(sizeof(uint32_t))); HIPCHK(e->d_seg.alloc(sizeof(unsigned long long)));
-  if (e->reduce) HIPCHK(e->d_red.alloc(sizeof(double) * (size_t)max_iters * e->dcols));
+  if (int32_t st = alloc_stats(e)) return st;
   e->bytes = (int64_t)(2 * dw_bytes + e->d_wt_mstate.bytes + pl_bytes + cnt_bytes + e->d_stats.bytes + e->d_red.bytes + e->d_mcount.bytes + e->d_tl_estate.bytes +
                        e->d_nstate.bytes + e->d_wt_dwfx.bytes + e->d_wt_segacc.bytes + e->d_wt_totL.bytes + sizeof(double) * 3 * tab);
-  HIPCHK(hipMemcpy(e->d_up.p, s.up.data(), e->d_up.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_down.p, s.down.data(), e->d_down.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_nw_border.p, border.data(), e->d_nw_border.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_tl_slot.p, e->tl_slot.data(), e->d_tl_slot.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->d_tips.p, e->tips_host.data(), e->tips_host.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(e->d_err.p, 0, sizeof(uint32_t)));
-  HIPCHK(hipMemset(e->d_seg.p, 0, sizeof(unsigned long long)));
-  HIPCHK(hipMemset(e->d_stats.p, 0, stats_bytes));
   HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
   HIPCHK(hipMemset(e->d_tl_cnt.p, 0, e->d_tl_cnt.bytes));
   HIPCHK(hipMemset(e->d_wt_dwfx.p, 0, e->d_wt_dwfx.bytes));
   HIPCHK(hipMemset(e->d_wt_segacc.p, 0, e->d_wt_segacc.bytes));
-  {   // initial paths -> every replica (makeabranch, src/phylomap.cpp:24-34, :901)
-    DevBuf d_off, d_maps;
-    HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
-    HIPCHK(d_maps.alloc(sizeof(double) * (size_t)x->map_off[E]));
-    HIPCHK(hipMemcpy(d_off.p, x->map_off, d_off.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_maps.p, x->maps, d_maps.bytes, hipMemcpyHostToDevice));
-    HIPCHK(phm::launch_tiles_init(E, tiles, rows, e->d_tl_slot.as<int32_t>(), d_off.as<int32_t>(), d_maps.as<double>(),
-                                  e->d_dw0.as<double>(), e->d_mcount.as<uint16_t>(), nullptr));
-    HIPCHK(hipDeviceSynchronize());
-  }
+  if (int32_t st = init_tile_paths(e, x)) return st;
   phm::WtParams& p = e->pwt;
+  fill_common(e, o, p);
   p.n_states = n; p.ldt = ldt;
-  p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
-  p.n_tiles = tiles; p.n_rep = e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset;
-  p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-  p.ks = ks_layout(e->variant); p.tip_masks = hidden_rates(e->variant); p.reduce = e->reduce; p.n_cols = e->dcols;
   p.klong = e->nw_klong;
   // branches per wave of the branch kernel: one while waves are scarce, up to 8 once there are 65 536 of them anyway
   p.group = (int32_t)std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)tiles * E / 65536));
@@ -915,11 +851,10 @@ int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
   p.cl_nodes = e->nw_tier_off.empty() ? nullptr : e->d_nw_cl_nodes.as<phm::ClusterNode>();
   p.cl_lvl_ptr = e->d_nw_cl_lvl_ptr.as<int32_t>(); p.cl_lvl_off = e->d_nw_cl_lvl_off.as<int32_t>();
   e->sparse_req = o.sparse_chains;
-  p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
   p.rows = rows;
   {   // dwell accumulators: 64-bit fixed point, a replica's column never exceeds the tree length
     int ex = 0;
-    (void)std::frexp(std::max(tree_len, 1.0), &ex);       // tree_len < 2^ex
+    (void)std::frexp(std::max(sp.tree_len, 1.0), &ex);       // tree_len < 2^ex
     p.fx_scale = std::ldexp(1.0, 60 - ex); p.fx_inv = std::ldexp(1.0, ex - 60);      // four lanes' sums share an accumulator in the reduced output: < 2^62
   }
   p.B2 = e->d_wt_B2.as<double>(); p.Bc = e->d_Bc.as<double>(); p.scale = e->d_scale.as<double>(); p.pid = e->d_pid.as<double>();
@@ -937,7 +872,162 @@ int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
   p.segacc = e->d_wt_segacc.as<unsigned long long>();
   p.dwfx_tile = e->reduce ? e->d_wt_dwfx_tile.as<unsigned long long>() : nullptr;
   p.cnt_tile = e->reduce ? e->d_wt_cnt_tile.as<uint32_t>() : nullptr;
-  p.stats = e->d_stats.as<double>(); p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
+  return PHM_OK;
+}
+
+// Engine state of the replica mapping (phm_mcmc.hip, phm_wide.hip for n > 4): a tile of 64 replicas walks the tree with one dwell
+// stream per tile; the one mapping that takes a list of trees (tpt tiles per tree).
+int32_t replicas_setup(phm_engine* e, const phm_tree* trees, const phm_model* model, const phm_options& o) {
+  const phm::Schedule& s = e->sched;
+  const phm_tree* x = trees;
+  const int E = s.n_edge, T = s.n_tips, n = e->n, n_trees = e->n_trees, max_iters = e->max_iters;
+  // Capacity of a tile's dwell stream.  Branch b holds 1 + Poisson(Omega t_b) segments in stationarity
+  // (t_b = sum(x$maps[[b]])) and occupies max-over-64-lanes rows; provision the per-branch quantile at
+  // `cap_tail` (default 1e-3, i.e. beyond the expected maximum of 64 draws) and check at run time.
+  int64_t rows = 0;
+  std::vector<std::vector<int32_t>> init_row(n_trees, std::vector<int32_t>(E));
+  std::vector<int64_t> init_rows(n_trees, 0);
+  for (int j = 0; j < n_trees; ++j) {
+    const phm_tree* xt = &trees[j];
+    int64_t rows_j = 0, max_q = 0;
+    double sum_lambda = 0.0;
+    for (int k = 0; k < E; ++k) {
+      const phm::DownStep& d = e->scheds[j].down[k];
+      double tb = 0.0;
+      for (int i = xt->map_off[d.edge]; i < xt->map_off[d.edge + 1]; ++i) tb += xt->maps[i];
+      int m0 = xt->map_off[d.edge + 1] - xt->map_off[d.edge];
+      if (e->wide() && m0 > phm::wide_maxseg(n))
+        return fail(PHM_ERR_UNSUPPORTED, "the replica mapping for 5..64 states holds at most " + std::to_string(phm::wide_maxseg(n)) +
+                                         " segments per branch (a path of " + std::to_string(m0) + " was given); use PHM_MAP_TILES or PHM_MAP_BRANCHES (the automatic choice for one tree)");
+      init_row[j][k] = (int32_t)init_rows[j];
+      init_rows[j] += m0;
+      // a sweep keeps at most the m merged segments it was given and adds Poisson(<= Omega t_b) virtual jumps, so a
+      // caller-supplied path longer than the stationary quantile (e.g. 100 equal pieces) needs m0 + that quantile
+      int q = phm::poisson_capacity(model->Omega * tb, o.cap_tail > 0.0 ? o.cap_tail : 1e-3);
+      rows_j += (int64_t)std::max(q, m0 + q - 1) * e->cap_boost;
+      max_q = std::max<int64_t>(max_q, (int64_t)std::max(q, m0 + q - 1) * e->cap_boost);
+      sum_lambda += model->Omega * tb;
+    }
+    // Ring capacity: the stream being read, plus head-room for the stream being written behind it.  While branch k is
+    // processed its input rows are still occupied and its output rows are already being written (one full branch of
+    // slack), and rows written so far minus rows freed so far performs a random walk whose standard deviation is about
+    // 0.7 sqrt(sum lambda) (wave-maximum of 64 Poisson counts per branch); 6 sigma of that on top.
+    rows_j = std::max(rows_j, init_rows[j]) + max_q + (int64_t)(6.0 * 0.7 * std::sqrt(sum_lambda)) + 64;
+    rows = std::max(rows, rows_j);
+  }
+  if (rows * 64 > 0x7fffff00ll) return fail(PHM_ERR_UNSUPPORTED, "tree too large: dwell rows per replica tile exceed 32-bit indexing");
+  e->rows = rows;
+
+  if (e->wide() && n_trees == 1) {
+    // n > 4: a wave takes the replicas of its tile in turn for the n-vector work (phm_wide.hip), so a tile that holds
+    // 64 replicas is 64 sequential passes in ONE wave.  With few replicas, place fewer of them on a tile (the unused lanes
+    // are skipped) until about 8 192 waves exist or the padded layout would take more than a quarter of the free HBM.
+    size_t free_now = 0, total_now = 0;
+    HIPCHK(hipMemGetInfo(&free_now, &total_now));
+    int rpt = 64;
+    while (rpt > 1 && (e->S + rpt / 2 - 1) / (rpt / 2) <= 8192) rpt /= 2;
+    auto tile_bytes = [&](int r) {
+      const size_t tl = (size_t)(e->S + r - 1) / r;
+      return tl * (sizeof(double) * ((size_t)rows * 64 + (size_t)s.n_node * n * 64) + 3 * (size_t)E * 64) +
+             sizeof(double) * (size_t)max_iters * e->dcols * (e->reduce ? tl : tl * 64);
+    };
+    while (rpt < 64 && tile_bytes(rpt) > free_now / 4) rpt *= 2;
+    e->rpt = rpt;
+    e->tiles = (e->S + rpt - 1) / rpt; e->S_pad = e->tiles * 64; e->tpt = e->tiles;
+  }
+
+  // tips (0-based u8)
+  if (n_trees > 1) {
+    e->tips_host.assign((size_t)e->tiles * T * 64, 0);
+    for (int tl = 0; tl < e->tiles; ++tl)
+      for (int t = 0; t < T; ++t)
+        std::memset(&e->tips_host[((size_t)tl * T + t) * 64], trees[tl / e->tpt].states[t] - 1, 64);
+  } else {
+    single_tree_tips(e, x);
+  }
+
+  // The n <= 4 replica kernel addresses a tile's arrays with 32-bit byte offsets from a scalar base (phm_mcmc.hip `at`).
+  if (!e->wide() && ((uint64_t)rows * 512u >= (1ull << 32) || (uint64_t)s.n_node * n * 512u >= (1ull << 32) ||
+                   (uint64_t)s.n_edge * 128u >= (1ull << 32)))
+    return fail(PHM_ERR_UNSUPPORTED, "tree too large for the replica layout (a tile's dwell stream or PL rows exceed 4 GB); use mapping=tiles");
+
+  // Full-length chain tables in global memory: the LDS copies of the replica kernels hold MCMC_KTAB rows, a longer chain
+  // reads row k of these instead of being continued step by step (which made a draw on an m-segment branch cost O(m)).
+  e->nw_klong = e->wide() ? phm::wide_maxseg(n) + 1 : (int)std::min<int64_t>(65536, rows + 1);
+  const size_t ktab = std::max(e->nw_klong, e->wide() ? phm::WIDE_KTAB : phm::MCMC_KTAB);      // rows of the tables upload_model fills
+
+  const size_t dw_bytes = sizeof(double) * (size_t)e->tiles * rows * 64;
+  // Two buffers save two VALU operations per dwell access (about 5 % of the n <= 4 sweep) and cost twice the HBM:
+  // used when they take less than a third of the free memory, unless the caller asks (phm_options.storage: 1 ring, 2 two buffers).
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  e->ring = e->wide() || n_trees > 1 || o.storage == 1 || (o.storage != 2 && 2 * dw_bytes > free_b / 3);
+  size_t need = (e->ring ? 1 : 2) * dw_bytes + stats_bytes(e) + sizeof(double) * (size_t)e->tiles * s.n_node * n * 64 +
+                (size_t)e->tiles * (s.n_node + 2 * (size_t)E) * 64 + e->tips_host.size();
+  if (int32_t st = check_hbm(need, free_b)) return st;
+  HIPCHK(e->d_up.alloc(sizeof(phm::UpStep) * s.up.size() * n_trees));
+  HIPCHK(e->d_down.alloc(sizeof(phm::DownStep) * s.down.size() * n_trees));
+  HIPCHK(e->d_roots.alloc(sizeof(int32_t) * n_trees));
+  HIPCHK(e->d_col.alloc(sizeof(double) * ktab * n * n));
+  HIPCHK(e->d_row.alloc(sizeof(double) * ktab * n * n));
+  HIPCHK(e->d_mask.alloc(sizeof(double) * ktab * 2 * n));
+
+  HIPCHK(to_device(e->d_tips, e->tips_host));
+  HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)e->tiles * E * 64));
+  HIPCHK(e->d_dw0.alloc(dw_bytes));
+  HIPCHK(e->d_cursor.alloc(sizeof(int32_t) * 2 * e->tiles));
+  if (!e->ring) HIPCHK(e->d_dw1.alloc(dw_bytes));
+  HIPCHK(e->d_PL.alloc(sizeof(double) * (size_t)e->tiles * s.n_node * n * 64));
+  HIPCHK(e->d_nstate.alloc((size_t)e->tiles * s.n_node * 64));
+  if (int32_t st = alloc_stats(e)) return st;
+  e->bytes = (int64_t)(e->d_up.bytes + e->d_down.bytes + e->d_col.bytes + e->d_row.bytes + e->d_tips.bytes + e->d_mcount.bytes +
+                       e->d_dw0.bytes + e->d_dw1.bytes + e->d_cursor.bytes + e->d_PL.bytes + e->d_nstate.bytes + e->d_stats.bytes + e->d_red.bytes);
+
+  for (int j = 0; j < n_trees; ++j) {
+    const phm::Schedule& sj = e->scheds[j];
+    HIPCHK(hipMemcpy(e->d_up.as<phm::UpStep>() + (size_t)j * sj.up.size(), sj.up.data(), sizeof(phm::UpStep) * sj.up.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_down.as<phm::DownStep>() + (size_t)j * sj.down.size(), sj.down.data(), sizeof(phm::DownStep) * sj.down.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_roots.as<int32_t>() + j, &sj.root, sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
+
+  {   // initial paths -> every replica (makeabranch, src/phylomap.cpp:24-34, :901), tree by tree
+    std::vector<int32_t> cur(2 * (size_t)e->tiles);
+    for (int j = 0; j < n_trees; ++j) {
+      const phm_tree* xt = &trees[j];
+      DevBuf d_off, d_maps, d_irow;
+      HIPCHK(to_device(d_irow, init_row[j]));
+      HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
+      HIPCHK(d_maps.alloc(sizeof(double) * (size_t)xt->map_off[E]));
+      HIPCHK(hipMemcpy(d_off.p, xt->map_off, d_off.bytes, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(d_maps.p, xt->maps, d_maps.bytes, hipMemcpyHostToDevice));
+      const size_t tile0 = (size_t)j * e->tpt;
+      HIPCHK(phm::launch_mcmc_init(E, e->tpt, rows, e->d_down.as<phm::DownStep>() + (size_t)j * E, d_irow.as<int32_t>(), d_off.as<int32_t>(),
+                                   d_maps.as<double>(), e->d_dw0.as<double>() + tile0 * rows * 64, e->d_mcount.as<uint16_t>() + tile0 * E * 64, nullptr));
+      HIPCHK(hipDeviceSynchronize());
+      for (int t = 0; t < e->tpt; ++t) { cur[2 * (tile0 + t)] = 0; cur[2 * (tile0 + t) + 1] = e->ring ? (int32_t)(init_rows[j] % rows) : 0; }
+    }
+    HIPCHK(hipMemcpy(e->d_cursor.p, cur.data(), e->d_cursor.bytes, hipMemcpyHostToDevice));
+  }
+
+  if (e->wide()) {      // the model tables go up in upload_model
+    HIPCHK(to_device(e->d_B2, e->hB2)); HIPCHK(to_device(e->d_Bc, e->hBc));
+    HIPCHK(to_device(e->d_scale, e->hscale)); HIPCHK(to_device(e->d_pid, e->hpid));
+    phm::WideParams& p = e->pw;
+    fill_common(e, o, p);
+    p.n_rep = n_trees > 1 ? e->S_tree : e->S;
+    p.tiles_per_tree = n_trees > 1 ? e->tpt : 0; p.roots = e->d_roots.as<int32_t>(); p.rep_stride = e->rpt;
+    p.n_states = n; p.ktab = std::max(e->nw_klong, phm::WIDE_KTAB); p.sparse = (e->variant == PHM_MCMC_SPARSE); p.count_self = p.ks;
+    p.maskpow = e->d_mask.as<double>();
+    p.rows = e->rows;
+    p.B2 = e->d_B2.as<double>(); p.Bc = e->d_Bc.as<double>(); p.scale = e->d_scale.as<double>(); p.pid = e->d_pid.as<double>();
+    p.up = e->d_up.as<phm::UpStep>(); p.down = e->d_down.as<phm::DownStep>();
+    p.colpow = e->d_col.as<double>(); p.rowpow = e->d_row.as<double>();
+    p.tips = e->d_tips.as<uint8_t>(); p.mcount = e->d_mcount.as<uint16_t>();
+    p.dwell0 = e->d_dw0.as<double>(); p.cursor = e->d_cursor.as<int32_t>();
+    p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>();
+  }
+  small_n(e, [&](auto& p) { fill_params(e, p.rep, o); });
   return PHM_OK;
 }
 
@@ -1078,13 +1168,11 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
     pidv[i] = model->pid[i];
     if (!(pidv[i] >= 0.0) || !std::isfinite(pidv[i])) return fail(PHM_ERR_BAD_INPUT, "pid must be non-negative");
   }
-  double *B2 = B2v.data(), *Bc = Bcv.data(), *scale = scalev.data(), *pid = pidv.data();
 
   phm_engine* e = new phm_engine();
   std::unique_ptr<phm_engine> guard(e);
   e->n = n; e->cols = n + n * (n - 1); e->variant = model->variant;
   e->dcols = e->cols;
-  e->wide = n > 4;
   if (ks_layout(e->variant)) {
     const int k = hidden_rates(e->variant) ? n / 2 - 1 : 0;
     e->cols = n + n * n + 2 + 3 * k + 1;        // man/sumstatMCMCks.Rd:19; bf: src/phylomap.cpp:1293
@@ -1115,21 +1203,22 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
   st = select_device(o.device);          // every input check above runs without a device
   if (st) return st;
   HIPCHK(hipGetDevice(&e->device));
-  const int E = s.n_edge, T = s.n_tips;
+  const int E = s.n_edge;
 
   // Mapping of the sweep onto lanes (phm_options.mapping): with few
   // chains the replica mapping would leave all but a handful of lanes idle and walk the tree sequentially.
-  const bool small_n = !e->wide && n_trees == 1;
+  const bool one_small = !e->wide() && n_trees == 1;
   const int map_req = o.mapping;
   const bool auto_map = map_req == PHM_MAP_AUTO && o.storage == 0;      // a ring / two-buffer request names the replica layout
   if ((map_req == 2 || map_req == 3) && n_trees != 1) return fail(PHM_ERR_UNSUPPORTED, "the branch-parallel mappings take a single tree");
-  if (e->wide) {      // 5..64 states: lane = replica, wave per (tile, item) (phm_wtiles.hip); a handful of chains: wave per (replica, branch)
-    e->tiled = n_trees == 1 && (map_req == 3 || (auto_map && e->S > wbranch_auto_max_replicas(s)));
-    e->narrow = n_trees == 1 && !e->tiled && (map_req == 2 || auto_map);
+  int mapping = PHM_MAP_REPLICAS;
+  if (e->wide()) {      // 5..64 states: lane = replica, wave per (tile, item) (phm_wtiles.hip); a handful of chains: wave per (replica, branch)
+    if (n_trees == 1 && (map_req == 3 || (auto_map && e->S > wbranch_auto_max_replicas(s)))) mapping = PHM_MAP_TILES;
+    else if (n_trees == 1 && (map_req == 2 || auto_map)) mapping = PHM_MAP_BRANCHES;
   } else {
     int narrow_cap = narrow_auto_max_replicas(s);
     bool long_paths = false;             // a branch expected to hold more than 64 segments: the replica mapping's lane-sequential loop is no place for it
-    if (small_n && auto_map) {
+    if (one_small && auto_map) {
       // Long paths: the (tile, branch) mapping cannot end a sweep before ONE wave has walked the longest branch twice (its two passes,
       // ~1.35 us per segment; the reference's squamate tree at Omega = 10, 2 280 segments on one branch: 3.1 ms per sweep up to 64
       // chains, 3.7 at 256), while the branch mapping costs 4.4e-8 ms per segment and chain (0.68 ms at 8 chains, 2.8 at 64, 10.2 at
@@ -1142,214 +1231,24 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
       if (max_seg > 64.0) narrow_cap = std::max(narrow_cap, (int)std::min(65535.0, 1.35e-3 * max_seg / (4.4e-8 * tot_seg)));
       long_paths = max_seg > 64.0;
     }
-    e->narrow = small_n && (map_req == 2 || (auto_map && e->S <= narrow_cap));
-    e->tiled = small_n && !e->narrow && (map_req == 3 || (auto_map && (long_paths || e->S <= TILES_AUTO_MAX_REPLICAS)));      // (no room: the replica layout, below)
+    if (one_small && (map_req == 2 || (auto_map && e->S <= narrow_cap))) mapping = PHM_MAP_BRANCHES;
+    else if (one_small && (map_req == 3 || (auto_map && (long_paths || e->S <= TILES_AUTO_MAX_REPLICAS)))) mapping = PHM_MAP_TILES;      // (no room: the replica layout, below)
   }
-  if (e->narrow && e->S > 65535) {      // the replica index is the grid's y dimension in these kernels
+  if (mapping == PHM_MAP_BRANCHES && e->S > 65535) {      // the replica index is the grid's y dimension in these kernels
     if (!auto_map) return fail(PHM_ERR_UNSUPPORTED, "the one-lane-per-branch / wave-per-(replica, branch) mappings take at most 65 535 replicas");
-    e->narrow = false; e->tiled = e->wide || e->S <= TILES_AUTO_MAX_REPLICAS;
+    mapping = (e->wide() || e->S <= TILES_AUTO_MAX_REPLICAS) ? PHM_MAP_TILES : PHM_MAP_REPLICAS;
   }
-  if (e->narrow) {
+  if (mapping == PHM_MAP_BRANCHES) {
     st = narrow_setup(e, x, model, o, max_iters);
-    if (st == PHM_ERR_OOM && auto_map) { e->narrow = false; e->tiled = true; st = PHM_OK; }
+    if (st == PHM_ERR_OOM && auto_map) { mapping = PHM_MAP_TILES; st = PHM_OK; }
   }
-  if (e->tiled) {
-    st = e->wide ? wtiles_setup(e, x, model, o, max_iters) : tiles_setup(e, x, model, o, max_iters);
-    if (st == PHM_ERR_OOM && auto_map) { e->tiled = false; st = PHM_OK; }     // automatic choice: fall back to the replica layout
+  if (mapping == PHM_MAP_TILES) {
+    st = e->wide() ? wtiles_setup(e, x, model, o, max_iters) : tiles_setup(e, x, model, o, max_iters);
+    if (st == PHM_ERR_OOM && auto_map) { mapping = PHM_MAP_REPLICAS; st = PHM_OK; }     // automatic choice: fall back to the replica layout
   }
-  if (e->narrow || e->tiled) {
-    if (st) return st;
-    st = upload_model(e);
-    if (st) return st;
-    HIPCHK(hipEventCreate(&e->ev0));
-    HIPCHK(hipEventCreate(&e->ev1));
-    *out = guard.release();
-    return PHM_OK;
-  }
-
-  // Capacity of a tile's dwell stream.  Branch b holds 1 + Poisson(Omega t_b) segments in stationarity
-  // (t_b = sum(x$maps[[b]])) and occupies max-over-64-lanes rows; provision the per-branch quantile at
-  // `cap_tail` (default 1e-3, i.e. beyond the expected maximum of 64 draws) and check at run time.
-  int64_t rows = 0;
-  std::vector<std::vector<int32_t>> init_row(n_trees, std::vector<int32_t>(E));
-  std::vector<int64_t> init_rows(n_trees, 0);
-  for (int j = 0; j < n_trees; ++j) {
-    const phm_tree* xt = &trees[j];
-    int64_t rows_j = 0, max_q = 0;
-    double sum_lambda = 0.0;
-    for (int k = 0; k < E; ++k) {
-      const phm::DownStep& d = e->scheds[j].down[k];
-      double tb = 0.0;
-      for (int i = xt->map_off[d.edge]; i < xt->map_off[d.edge + 1]; ++i) tb += xt->maps[i];
-      int m0 = xt->map_off[d.edge + 1] - xt->map_off[d.edge];
-      if (e->wide && m0 > phm::wide_maxseg(n))
-        return fail(PHM_ERR_UNSUPPORTED, "the replica mapping for 5..64 states holds at most " + std::to_string(phm::wide_maxseg(n)) +
-                                         " segments per branch (a path of " + std::to_string(m0) + " was given); use PHM_MAP_TILES or PHM_MAP_BRANCHES (the automatic choice for one tree)");
-      init_row[j][k] = (int32_t)init_rows[j];
-      init_rows[j] += m0;
-      // a sweep keeps at most the m merged segments it was given and adds Poisson(<= Omega t_b) virtual jumps, so a
-      // caller-supplied path longer than the stationary quantile (e.g. 100 equal pieces) needs m0 + that quantile
-      int q = phm::poisson_capacity(model->Omega * tb, o.cap_tail > 0.0 ? o.cap_tail : 1e-3);
-      rows_j += (int64_t)std::max(q, m0 + q - 1) * e->cap_boost;
-      max_q = std::max<int64_t>(max_q, (int64_t)std::max(q, m0 + q - 1) * e->cap_boost);
-      sum_lambda += model->Omega * tb;
-    }
-    // Ring capacity: the stream being read, plus head-room for the stream being written behind it.  While branch k is
-    // processed its input rows are still occupied and its output rows are already being written (one full branch of
-    // slack), and rows written so far minus rows freed so far performs a random walk whose standard deviation is about
-    // 0.7 sqrt(sum lambda) (wave-maximum of 64 Poisson counts per branch); 6 sigma of that on top.
-    rows_j = std::max(rows_j, init_rows[j]) + max_q + (int64_t)(6.0 * 0.7 * std::sqrt(sum_lambda)) + 64;
-    rows = std::max(rows, rows_j);
-  }
-  if (rows * 64 > 0x7fffff00ll) return fail(PHM_ERR_UNSUPPORTED, "tree too large: dwell rows per replica tile exceed 32-bit indexing");
-  e->rows = rows;
-
-  if (e->wide && n_trees == 1) {
-    // n > 4: a wave takes the replicas of its tile in turn for the n-vector work (phm_wide.hip), so a tile that holds
-    // 64 replicas is 64 sequential passes in ONE wave.  With few replicas, place fewer of them on a tile (the unused lanes
-    // are skipped) until about 8 192 waves exist or the padded layout would take more than a quarter of the free HBM.
-    size_t free_now = 0, total_now = 0;
-    HIPCHK(hipMemGetInfo(&free_now, &total_now));
-    int rpt = 64;
-    while (rpt > 1 && (e->S + rpt / 2 - 1) / (rpt / 2) <= 8192) rpt /= 2;
-    auto tile_bytes = [&](int r) {
-      const size_t tl = (size_t)(e->S + r - 1) / r;
-      return tl * (sizeof(double) * ((size_t)rows * 64 + (size_t)s.n_node * n * 64) + 3 * (size_t)E * 64) +
-             sizeof(double) * (size_t)max_iters * e->dcols * (e->reduce ? tl : tl * 64);
-    };
-    while (rpt < 64 && tile_bytes(rpt) > free_now / 4) rpt *= 2;
-    e->rpt = rpt;
-    e->tiles = (e->S + rpt - 1) / rpt; e->S_pad = e->tiles * 64; e->tpt = e->tiles;
-  }
-
-  // tips (0-based u8)
-  if (n_trees > 1) {
-    e->tips_host.assign((size_t)e->tiles * T * 64, 0);
-    for (int tl = 0; tl < e->tiles; ++tl)
-      for (int t = 0; t < T; ++t)
-        std::memset(&e->tips_host[((size_t)tl * T + t) * 64], trees[tl / e->tpt].states[t] - 1, 64);
-  } else if (e->tips_per_replica) {
-    e->tips_host.assign((size_t)e->tiles * T * 64, (uint8_t)(x->states[0] - 1));      // padding lanes: any valid state
-    for (int r = 0; r < e->S; ++r) {
-      const int pr = e->pad_index(r);
-      for (int t = 0; t < T; ++t) e->tips_host[((size_t)(pr / 64) * T + t) * 64 + (pr % 64)] = (uint8_t)(x->states[(size_t)r * T + t] - 1);
-    }
-    if (e->rpt == 64)      // dense tiles of the n <= 4 kernels: padding lanes are run like replicas, give them the last site
-      for (int r = e->S; r < e->S_pad; ++r)
-        for (int t = 0; t < T; ++t) e->tips_host[((size_t)(r / 64) * T + t) * 64 + (r % 64)] = (uint8_t)(x->states[(size_t)(e->S - 1) * T + t] - 1);
-  } else {
-    e->tips_host.resize(T);
-    for (int t = 0; t < T; ++t) e->tips_host[t] = (uint8_t)(x->states[t] - 1);
-  }
-
-  // The n <= 4 replica kernel addresses a tile's arrays with 32-bit byte offsets from a scalar base (phm_mcmc.hip `at`).
-  if (!e->wide && ((uint64_t)rows * 512u >= (1ull << 32) || (uint64_t)s.n_node * n * 512u >= (1ull << 32) ||
-                   (uint64_t)s.n_edge * 128u >= (1ull << 32)))
-    return fail(PHM_ERR_UNSUPPORTED, "tree too large for the replica layout (a tile's dwell stream or PL rows exceed 4 GB); use mapping=tiles");
-
-  std::vector<double> col, row;
-  // Full-length chain tables in global memory: the LDS copies of the replica kernels hold MCMC_KTAB rows, a longer chain
-  // reads row k of these instead of being continued step by step (which made a draw on an m-segment branch cost O(m)).
-  e->nw_klong = e->wide ? phm::wide_maxseg(n) + 1 : (int)std::min<int64_t>(65536, rows + 1);
-  const int ktab = std::max(e->nw_klong, e->wide ? phm::WIDE_KTAB : phm::MCMC_KTAB);
-  col.assign((size_t)ktab * n * n, 0.0); row.assign((size_t)ktab * n * n, 0.0);     // sizes only; filled by upload_model
-  std::vector<double> maskpow((size_t)ktab * 2 * n, 0.0);
-
-  const size_t stats_bytes = e->reduce ? sizeof(double) * (size_t)max_iters * e->tiles * e->dcols
-                                                     : sizeof(double) * (size_t)max_iters * e->dcols * e->S_pad;
-  const size_t dw_bytes = sizeof(double) * (size_t)e->tiles * rows * 64;
-  // Two buffers save two VALU operations per dwell access (about 5 % of the n <= 4 sweep) and cost twice the HBM:
-  // used when they take less than a third of the free memory, unless the caller asks (phm_options.storage: 1 ring, 2 two buffers).
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  e->ring = e->wide || n_trees > 1 || o.storage == 1 || (o.storage != 2 && 2 * dw_bytes > free_b / 3);
-  size_t need = (e->ring ? 1 : 2) * dw_bytes + stats_bytes + sizeof(double) * (size_t)e->tiles * s.n_node * n * 64 +
-                (size_t)e->tiles * (s.n_node + 2 * (size_t)E) * 64 + e->tips_host.size();
-  if (need + (64u << 20) > free_b) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "engine needs %.2f GiB of HBM, %.2f GiB free (reduce n_replicas or max_iters)", need / 1073741824.0, free_b / 1073741824.0);
-    return fail(PHM_ERR_OOM, buf);
-  }
-  HIPCHK(e->d_up.alloc(sizeof(phm::UpStep) * s.up.size() * n_trees));
-  HIPCHK(e->d_down.alloc(sizeof(phm::DownStep) * s.down.size() * n_trees));
-  HIPCHK(e->d_roots.alloc(sizeof(int32_t) * n_trees));
-  HIPCHK(e->d_col.alloc(sizeof(double) * col.size()));
-  HIPCHK(e->d_row.alloc(sizeof(double) * row.size()));
-  HIPCHK(e->d_mask.alloc(sizeof(double) * maskpow.size()));
-
-  HIPCHK(e->d_tips.alloc(e->tips_host.size()));
-  HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)e->tiles * E * 64));
-  HIPCHK(e->d_dw0.alloc(dw_bytes));
-  HIPCHK(e->d_cursor.alloc(sizeof(int32_t) * 2 * e->tiles));
-  if (!e->ring) HIPCHK(e->d_dw1.alloc(dw_bytes));
-  HIPCHK(e->d_PL.alloc(sizeof(double) * (size_t)e->tiles * s.n_node * n * 64));
-  HIPCHK(e->d_nstate.alloc((size_t)e->tiles * s.n_node * 64));
-  HIPCHK(e->d_stats.alloc(stats_bytes));
-  HIPCHK(e->d_err.alloc(sizeof(uint32_t)));
-  HIPCHK(e->d_seg.alloc(sizeof(unsigned long long)));
-  if (e->reduce) HIPCHK(e->d_red.alloc(sizeof(double) * (size_t)max_iters * e->dcols));
-  e->bytes = (int64_t)(e->d_up.bytes + e->d_down.bytes + e->d_col.bytes + e->d_row.bytes + e->d_tips.bytes + e->d_mcount.bytes +
-                       e->d_dw0.bytes + e->d_dw1.bytes + e->d_cursor.bytes + e->d_PL.bytes + e->d_nstate.bytes + e->d_stats.bytes + e->d_red.bytes);
-
-  for (int j = 0; j < n_trees; ++j) {
-    const phm::Schedule& sj = e->scheds[j];
-    HIPCHK(hipMemcpy(e->d_up.as<phm::UpStep>() + (size_t)j * sj.up.size(), sj.up.data(), sizeof(phm::UpStep) * sj.up.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_down.as<phm::DownStep>() + (size_t)j * sj.down.size(), sj.down.data(), sizeof(phm::DownStep) * sj.down.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_roots.as<int32_t>() + j, &sj.root, sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMemcpy(e->d_tips.p, e->tips_host.data(), e->tips_host.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(e->d_err.p, 0, sizeof(uint32_t)));
-  HIPCHK(hipMemset(e->d_seg.p, 0, sizeof(unsigned long long)));
-  HIPCHK(hipMemset(e->d_stats.p, 0, stats_bytes));
-  HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
-
-  {   // initial paths -> every replica (makeabranch, src/phylomap.cpp:24-34, :901), tree by tree
-    std::vector<int32_t> cur(2 * (size_t)e->tiles);
-    for (int j = 0; j < n_trees; ++j) {
-      const phm_tree* xt = &trees[j];
-      DevBuf d_off, d_maps, d_irow;
-      HIPCHK(d_irow.alloc(sizeof(int32_t) * E));
-      HIPCHK(hipMemcpy(d_irow.p, init_row[j].data(), d_irow.bytes, hipMemcpyHostToDevice));
-      HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
-      HIPCHK(d_maps.alloc(sizeof(double) * (size_t)xt->map_off[E]));
-      HIPCHK(hipMemcpy(d_off.p, xt->map_off, d_off.bytes, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_maps.p, xt->maps, d_maps.bytes, hipMemcpyHostToDevice));
-      const size_t tile0 = (size_t)j * e->tpt;
-      HIPCHK(phm::launch_mcmc_init(E, e->tpt, rows, e->d_down.as<phm::DownStep>() + (size_t)j * E, d_irow.as<int32_t>(), d_off.as<int32_t>(),
-                                   d_maps.as<double>(), e->d_dw0.as<double>() + tile0 * rows * 64, e->d_mcount.as<uint16_t>() + tile0 * E * 64, nullptr));
-      HIPCHK(hipDeviceSynchronize());
-      for (int t = 0; t < e->tpt; ++t) { cur[2 * (tile0 + t)] = 0; cur[2 * (tile0 + t) + 1] = e->ring ? (int32_t)(init_rows[j] % rows) : 0; }
-    }
-    HIPCHK(hipMemcpy(e->d_cursor.p, cur.data(), e->d_cursor.bytes, hipMemcpyHostToDevice));
-  }
-
-  if (e->wide) {
-    HIPCHK(e->d_B2.alloc(sizeof(double) * n * n)); HIPCHK(e->d_Bc.alloc(sizeof(double) * n * n));
-    HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(e->d_pid.alloc(sizeof(double) * n));
-    HIPCHK(hipMemcpy(e->d_B2.p, B2, e->d_B2.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_Bc.p, Bc, e->d_Bc.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_scale.p, scale, e->d_scale.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_pid.p, pid, e->d_pid.bytes, hipMemcpyHostToDevice));
-    phm::WideParams& p = e->pw;
-    p.n_states = n; p.n_tips = s.n_tips; p.n_node = s.n_node; p.n_edge = s.n_edge; p.root = s.root;
-    p.n_tiles = e->tiles; p.n_rep = n_trees > 1 ? e->S_tree : e->S; p.n_rep_pad = e->S_pad; p.replica_offset = o.replica_offset;
-    p.tiles_per_tree = n_trees > 1 ? e->tpt : 0; p.roots = e->d_roots.as<int32_t>(); p.rep_stride = e->rpt;
-    p.normalise = e->normalise; p.tips_per_replica = e->tips_per_replica ? 1 : 0;
-    p.reduce = e->reduce; p.n_cols = e->dcols; p.ktab = std::max(e->nw_klong, phm::WIDE_KTAB); p.sparse = (e->variant == PHM_MCMC_SPARSE); p.ks = ks_layout(e->variant); p.count_self = p.ks; p.tip_masks = hidden_rates(e->variant);
-    p.maskpow = e->d_mask.as<double>();
-    p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
-    p.rows = e->rows;
-    p.B2 = e->d_B2.as<double>(); p.Bc = e->d_Bc.as<double>(); p.scale = e->d_scale.as<double>(); p.pid = e->d_pid.as<double>();
-    p.up = e->d_up.as<phm::UpStep>(); p.down = e->d_down.as<phm::DownStep>();
-    p.colpow = e->d_col.as<double>(); p.rowpow = e->d_row.as<double>();
-    p.tips = e->d_tips.as<uint8_t>(); p.mcount = e->d_mcount.as<uint16_t>();
-    p.dwell0 = e->d_dw0.as<double>(); p.cursor = e->d_cursor.as<int32_t>();
-    p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>(); p.stats = e->d_stats.as<double>();
-    p.err = e->d_err.as<uint32_t>(); p.segcnt = e->d_seg.as<unsigned long long>();
-  }
-  if (n == 2) fill_params<2>(e, e->p2, B2, Bc, scale, pid, o);
-  if (n == 3) fill_params<3>(e, e->p3, B2, Bc, scale, pid, o);
-  if (n == 4) fill_params<4>(e, e->p4, B2, Bc, scale, pid, o);
+  e->mapping = mapping;
+  if (mapping == PHM_MAP_REPLICAS) st = replicas_setup(e, trees, model, o);
+  if (st) return st;
   st = upload_model(e);
   if (st) return st;
   HIPCHK(hipEventCreate(&e->ev0));
@@ -1369,26 +1268,18 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(hipEventRecord(e->ev0, stream));
   int launches = 0;
-  if (e->narrow) {
-    hipError_t le = hipSuccess;
+  hipError_t le = hipSuccess;
+  if (e->mapping == PHM_MAP_BRANCHES) {
     for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
       const int it = e->iters_done + i;
-      if (e->n == 2) le = phm::launch_narrow_sweep<2>(e->n2, e->nw_tier_off, e->nw_walk_off, it, stream, i > 0);
-      if (e->n == 3) le = phm::launch_narrow_sweep<3>(e->n3, e->nw_tier_off, e->nw_walk_off, it, stream, i > 0);
-      if (e->n == 4) le = phm::launch_narrow_sweep<4>(e->n4, e->nw_tier_off, e->nw_walk_off, it, stream, i > 0);
-      if (e->wide) le = phm::launch_wbranch_sweep(e->pwb, e->nw_up_off, e->nw_down_off, it, stream);
+      small_n(e, [&](auto& p) { le = phm::launch_narrow_sweep(p.br, e->nw_tier_off, e->nw_walk_off, it, stream, i > 0); });
+      if (e->wide()) le = phm::launch_wbranch_sweep(e->pwb, e->nw_up_off, e->nw_down_off, it, stream);
       launches += (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;
     }
-    if (n_iters > 0 && le == hipSuccess && !e->wide) {       // the last sweep's statistics (phm_narrow.hip defers them by one launch)
-      const int it = e->iters_done + n_iters - 1;
-      if (e->n == 2) le = phm::launch_narrow_stats<2>(e->n2, it, stream);
-      if (e->n == 3) le = phm::launch_narrow_stats<3>(e->n3, it, stream);
-      if (e->n == 4) le = phm::launch_narrow_stats<4>(e->n4, it, stream);
-    }
+    if (n_iters > 0 && le == hipSuccess)       // the last sweep's statistics (phm_narrow.hip defers them by one launch)
+      small_n(e, [&](auto& p) { le = phm::launch_narrow_stats(p.br, e->iters_done + n_iters - 1, stream); });
     HIPCHK(le);
-  }
-  if (e->tiled) {
-    hipError_t le = hipSuccess;
+  } else if (e->mapping == PHM_MAP_TILES) {
     e->phase_iters = 0;
     if (e->phase_timing) {
       while ((int)e->phase_ev.size() < 5 * n_iters) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); e->phase_ev.push_back(ev); }
@@ -1397,36 +1288,33 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
     for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
       const int it = e->iters_done + i;
       hipEvent_t* pev = e->phase_timing ? &e->phase_ev[5 * (size_t)i] : nullptr;
-      if (e->n == 2) le = phm::launch_tiles_sweep<2>(e->t2, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
-      if (e->n == 3) le = phm::launch_tiles_sweep<3>(e->t3, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
-      if (e->n == 4) le = phm::launch_tiles_sweep<4>(e->t4, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
-      if (e->wide) le = phm::launch_wtiles_sweep(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
+      small_n(e, [&](auto& p) { le = phm::launch_tiles_sweep(p.tl, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev); });
+      if (e->wide()) le = phm::launch_wtiles_sweep(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
       const bool clusters = !e->nw_tier_off.empty();
       const int tiers = (int)e->nw_tier_off.size() - 1;
-      if (clusters && e->wide)             // 5 .. 32 states on a deep tree: the node draws by tier, the pruning pass too when it runs on the band kernel
+      if (clusters && e->wide())             // 5 .. 32 states on a deep tree: the node draws by tier, the pruning pass too when it runs on the band kernel
         launches += (e->pwt.band_up > 0 && !e->wt_sparse.kernel ? tiers : (int)e->nw_up_off.size() - 1) + tiers + 4;
       else
         launches += clusters ? 2 * tiers + 3      // a launch per tier and pass, branch kernel, two reductions
                              : (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;
     }
     HIPCHK(le);
-  }
-  for (int done = 0; done < n_iters && !e->narrow && !e->tiled;) {
-    int chunk = std::min(e->ipl, n_iters - done);
-    hipError_t le = hipSuccess;
-    if (e->n == 2) le = phm::launch_mcmc<2>(e->p2, e->iters_done + done, chunk, stream);
-    if (e->n == 3) le = phm::launch_mcmc<3>(e->p3, e->iters_done + done, chunk, stream);
-    if (e->n == 4) le = phm::launch_mcmc<4>(e->p4, e->iters_done + done, chunk, stream);
-    if (e->wide && !e->narrow) le = phm::launch_mcmc_wide(e->pw, e->iters_done + done, chunk, stream);
-    HIPCHK(le);
-    done += chunk;
-    ++launches;
+  } else {
+    for (int done = 0; done < n_iters;) {
+      int chunk = std::min(e->ipl, n_iters - done);
+      small_n(e, [&](auto& p) { le = phm::launch_mcmc(p.rep, e->iters_done + done, chunk, stream); });
+      if (e->wide()) le = phm::launch_mcmc_wide(e->pw, e->iters_done + done, chunk, stream);
+      HIPCHK(le);
+      done += chunk;
+      ++launches;
+    }
   }
   HIPCHK(hipEventRecord(e->ev1, stream));
   for (int i = 0; i < n_iters; ++i) e->qhist.push_back(e->qparams);      // recordQ / recordQks at the start of each sweep
   e->iters_done += n_iters;
-  e->epi_iter = (e->narrow && !e->wide && n_iters > 0 && ((e->n == 2 && e->n2.host_row) || (e->n == 3 && e->n3.host_row) || (e->n == 4 && e->n4.host_row)))
-                    ? e->iters_done - 1 : -1;
+  bool host_row = false;
+  if (e->mapping == PHM_MAP_BRANCHES) small_n(e, [&](auto& p) { host_row = p.br.host_row != nullptr; });
+  e->epi_iter = (host_row && n_iters > 0) ? e->iters_done - 1 : -1;
   e->last_stream = stream;
   e->timing_pending = true;
   e->last_launches = launches;
@@ -1509,7 +1397,7 @@ int32_t phm_engine_sync(phm_engine* e) {
   uint32_t derr = 0;
   std::memcpy(&derr, e->pin_status.p, sizeof derr);
   std::memcpy(&e->seg_total, e->pin_status.as<unsigned char>() + 8, sizeof(unsigned long long));
-  const bool wide_replicas = e->wide && !e->narrow && !e->tiled;      // phm_wide.hip: a fixed 128-segment state scratch per replica in LDS, not recoverable
+  const bool wide_replicas = e->wide() && e->mapping == PHM_MAP_REPLICAS;      // phm_wide.hip: a fixed 128-segment state scratch per replica in LDS, not recoverable
   if ((derr & phm::DERR_CAPACITY) && !(derr & ~phm::DERR_CAPACITY) && e->recover && e->saved && !wide_replicas) return recover_capacity(e);
   if ((derr & phm::DERR_CAPACITY) && wide_replicas)
     return fail(PHM_ERR_CAPACITY, "a branch outgrew the replica mapping for 5..64 states (at most " + std::to_string(phm::wide_maxseg(e->n)) +
@@ -1526,25 +1414,13 @@ int32_t phm_engine_read_stats(phm_engine* e, int32_t iter0, int32_t n, double* o
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(wait_stream(e->last_stream));
   const int cols = e->cols, dcols = e->dcols;
-  // device column -> result column: identical except for ks, whose parameter columns (recordQks) sit between the
-  // counters and the root state and are constants of the fixed Q
-  auto out_col = [&](int dc) { return (dcols != cols && dc == dcols - 1) ? cols - 1 : dc; };
-  auto fill_params = [&](double* mat) {      // mat: n x cols column-major
-    if (dcols == cols) return;
-    for (int i = 0; i < n; ++i) {
-      const std::vector<double>& qp = e->qhist[iter0 + i];
-      for (size_t q = 0; q < qp.size(); ++q) mat[(size_t)(dcols - 1 + q) * n + i] = qp[q];
-    }
-  };
   if (e->reduce) {
     HIPCHK(phm::launch_stats_reduce(e->d_stats.as<double>() + (size_t)iter0 * e->tiles * dcols, n, e->tiles, dcols,
                                       e->d_red.as<double>(), e->last_stream));
     std::vector<double> h((size_t)n * dcols);
     HIPCHK(hipMemcpyAsync(h.data(), e->d_red.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, e->last_stream));
     HIPCHK(hipStreamSynchronize(e->last_stream));
-    for (int i = 0; i < n; ++i)
-      for (int c = 0; c < dcols; ++c) out[(size_t)out_col(c) * n + i] = h[(size_t)i * dcols + c];
-    fill_params(out);
+    result_matrix(e, iter0, n, out, [&](int i, int c) { return h[(size_t)i * dcols + c]; });
   } else {
     const size_t hn = (size_t)n * dcols * e->S_pad;
     std::vector<double> hv;
@@ -1571,11 +1447,8 @@ int32_t phm_engine_read_stats(phm_engine* e, int32_t iter0, int32_t n, double* o
       hv.resize(n_rows * e->S);
       HIPCHK(hipMemcpyAsync(hv.data(), d_pack.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, e->last_stream));
       HIPCHK(hipStreamSynchronize(e->last_stream));
-      for (int r = 0; r < e->S; ++r) {
-        for (int c = 0; c < dcols; ++c)
-          for (int i = 0; i < n; ++i) out[((size_t)r * cols + out_col(c)) * n + i] = hv[((size_t)i * dcols + c) * e->S + r];
-        fill_params(out + (size_t)r * cols * n);
-      }
+      for (int r = 0; r < e->S; ++r)
+        result_matrix(e, iter0, n, out + (size_t)r * cols * n, [&](int i, int c) { return hv[((size_t)i * dcols + c) * e->S + r]; });
       return PHM_OK;
     } else {
       hv.resize(hn);
@@ -1583,9 +1456,8 @@ int32_t phm_engine_read_stats(phm_engine* e, int32_t iter0, int32_t n, double* o
       h = hv.data();
     }
     for (int r = 0; r < e->S; ++r) {
-      for (int c = 0; c < dcols; ++c)
-        for (int i = 0; i < n; ++i) out[((size_t)r * cols + out_col(c)) * n + i] = h[((size_t)i * dcols + c) * e->S_pad + e->pad_index(r)];
-      fill_params(out + (size_t)r * cols * n);
+      const int pr = e->pad_index(r);
+      result_matrix(e, iter0, n, out + (size_t)r * cols * n, [&](int i, int c) { return h[((size_t)i * dcols + c) * e->S_pad + pr]; });
     }
   }
   return PHM_OK;
@@ -1626,15 +1498,9 @@ int32_t phm_engine_fold_reduced(phm_engine* e, int32_t iter0, int32_t n, std::ve
 int32_t phm_engine_finish_reduced(phm_engine* e, int32_t iter0, int32_t n, const std::vector<double>& acc, double* out) {
   e = live(e);
   if (!e || !out) return fail(PHM_ERR_STATE, "engine/out is NULL");
-  const int cols = e->cols, dcols = e->dcols;
+  const int dcols = e->dcols;
   if (acc.size() != (size_t)n * dcols) return fail(PHM_ERR_STATE, "fold: accumulator size mismatch");
-  for (int i = 0; i < n; ++i)
-    for (int c = 0; c < dcols; ++c) out[(size_t)((dcols != cols && c == dcols - 1) ? cols - 1 : c) * n + i] = acc[(size_t)i * dcols + c];
-  if (dcols != cols)
-    for (int i = 0; i < n; ++i) {
-      const std::vector<double>& qp = e->qhist[iter0 + i];
-      for (size_t q = 0; q < qp.size(); ++q) out[(size_t)(dcols - 1 + q) * n + i] = qp[q];
-    }
+  result_matrix(e, iter0, n, out, [&](int i, int c) { return acc[(size_t)i * dcols + c]; });
   return PHM_OK;
 }
 
@@ -1648,9 +1514,12 @@ int32_t phm_engine_dump(phm_engine* e, int32_t replica, int32_t* seg_count, doub
   if (replica < 0 || replica >= e->S) return fail(PHM_ERR_BAD_INPUT, "replica out of range");
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipStreamSynchronize(e->last_stream));
-  if (e->narrow) {      // branch-parallel layout: CSR slots of the buffer the next sweep will read
-    const phm::Schedule& s = e->sched;
-    const int E = s.n_edge, T = s.n_tips, n = e->n;
+  // the chain sits in lane `lane` of block `blk` of the per-chain arrays: [replica][...] (branch mapping) or [tile][...][64]
+  const bool branches = e->mapping == PHM_MAP_BRANCHES;
+  const int padded = branches ? replica : e->pad_index(replica), L = branches ? 1 : 64, blk = padded / L, lane = padded % L;
+  const phm::Schedule& s = e->scheds[e->n_trees > 1 ? blk / e->tpt : 0];
+  const int E = s.n_edge, T = s.n_tips, n = e->n;
+  if (branches) {      // CSR slots of the buffer the next sweep will read
     std::vector<int32_t> mc(E);
     HIPCHK(hipMemcpy(mc.data(), e->d_nw_mcount.as<int32_t>() + (size_t)replica * E, sizeof(int32_t) * E, hipMemcpyDeviceToHost));
     if (seg_count) for (int b = 0; b < E; ++b) seg_count[b] = mc[b];
@@ -1661,69 +1530,49 @@ int32_t phm_engine_dump(phm_engine* e, int32_t replica, int32_t* seg_count, doub
       for (int b = 0; b < E; ++b)
         for (int i = 0; i < std::min<int>(mc[b], seg_cap); ++i) seg_dwell[(size_t)b * seg_cap + i] = dw[(size_t)e->nw_off[b] + i];
     }
-    auto tip_state = [&](int t) -> int { return e->tips_per_replica ? e->tips_host[(size_t)replica * T + t] : e->tips_host[t]; };
-    if (node_states) {
-      std::vector<uint8_t> ns(s.n_node);
-      HIPCHK(hipMemcpy(ns.data(), e->d_nstate.as<uint8_t>() + (size_t)replica * s.n_node, ns.size(), hipMemcpyDeviceToHost));
-      for (int t = 0; t < T; ++t) node_states[t] = tip_state(t) + 1;
-      for (int v = 0; v < s.n_node; ++v) node_states[T + v] = ns[v] + 1;
-    }
-    if (PL) {
-      std::vector<double> pl((size_t)s.n_node * n);
-      HIPCHK(hipMemcpy(pl.data(), e->d_PL.as<double>() + (size_t)replica * s.n_node * n, sizeof(double) * pl.size(), hipMemcpyDeviceToHost));
-      for (int t = 0; t < T; ++t)
-        for (int c = 0; c < n; ++c) PL[(size_t)t * n + c] = (c == tip_state(t)) ? 1.0 : 0.0;
-      for (int v = 0; v < s.n_node; ++v)
-        for (int c = 0; c < n; ++c) PL[(size_t)(T + v) * n + c] = pl[(size_t)v * n + c];
-    }
-    return PHM_OK;
-  }
-  const int padded = e->pad_index(replica), tile = padded / 64, lane = padded % 64;
-  const phm::Schedule& s = e->scheds[e->n_trees > 1 ? tile / e->tpt : 0];
-  const int E = s.n_edge, T = s.n_tips, n = e->n;
-  std::vector<uint16_t> mc((size_t)E * 64);
-  HIPCHK(hipMemcpy(mc.data(), e->d_mcount.as<uint16_t>() + (size_t)tile * E * 64, sizeof(uint16_t) * mc.size(), hipMemcpyDeviceToHost));
-  if (seg_count) for (int b = 0; b < E; ++b) seg_count[b] = mc[(size_t)b * 64 + lane];
-  if (seg_dwell && e->tiled) {      // slots of the buffer the next sweep will read
-    std::vector<double> dw((size_t)e->rows * 64);
-    const double* src = ((e->iters_done & 1) ? e->d_dw1.as<double>() : e->d_dw0.as<double>()) + (size_t)tile * e->rows * 64;
-    HIPCHK(hipMemcpy(dw.data(), src, sizeof(double) * dw.size(), hipMemcpyDeviceToHost));
-    for (int b = 0; b < E; ++b)
-      for (int i = 0; i < std::min<int>(mc[(size_t)b * 64 + lane], seg_cap); ++i)
-        seg_dwell[(size_t)b * seg_cap + i] = dw[((size_t)e->tl_slot[b] + i) * 64 + lane];
-  } else if (seg_dwell) {
-    std::vector<double> dw((size_t)e->rows * 64);
-    int32_t cur[2];
-    HIPCHK(hipMemcpy(cur, e->d_cursor.as<int32_t>() + 2 * tile, sizeof cur, hipMemcpyDeviceToHost));
-    const double* src = ((!e->ring && cur[0]) ? e->d_dw1.as<double>() : e->d_dw0.as<double>()) + (size_t)tile * e->rows * 64;
-    HIPCHK(hipMemcpy(dw.data(), src, sizeof(double) * dw.size(), hipMemcpyDeviceToHost));
-    size_t row = e->ring ? (size_t)cur[0] : 0;     // replay the stream layout from the ring cursor: branch down[k] occupies max-over-lanes(m) rows
-    for (int k = 0; k < E; ++k) {
-      const phm::DownStep& d = s.down[k];
-      int m = std::min<int>(mc[(size_t)d.edge * 64 + lane], seg_cap);
-      for (int i = 0; i < m; ++i) seg_dwell[(size_t)d.edge * seg_cap + i] = dw[((row + i) % (size_t)e->rows) * 64 + lane];
-      int mx = 0;
-      for (int l = 0; l < 64; ++l) mx = std::max<int>(mx, mc[(size_t)d.edge * 64 + l]);
-      row += mx;
+  } else {
+    std::vector<uint16_t> mc((size_t)E * 64);
+    HIPCHK(hipMemcpy(mc.data(), e->d_mcount.as<uint16_t>() + (size_t)blk * E * 64, sizeof(uint16_t) * mc.size(), hipMemcpyDeviceToHost));
+    if (seg_count) for (int b = 0; b < E; ++b) seg_count[b] = mc[(size_t)b * 64 + lane];
+    if (seg_dwell && e->mapping == PHM_MAP_TILES) {      // slots of the buffer the next sweep will read
+      std::vector<double> dw((size_t)e->rows * 64);
+      const double* src = ((e->iters_done & 1) ? e->d_dw1.as<double>() : e->d_dw0.as<double>()) + (size_t)blk * e->rows * 64;
+      HIPCHK(hipMemcpy(dw.data(), src, sizeof(double) * dw.size(), hipMemcpyDeviceToHost));
+      for (int b = 0; b < E; ++b)
+        for (int i = 0; i < std::min<int>(mc[(size_t)b * 64 + lane], seg_cap); ++i)
+          seg_dwell[(size_t)b * seg_cap + i] = dw[((size_t)e->tl_slot[b] + i) * 64 + lane];
+    } else if (seg_dwell) {
+      std::vector<double> dw((size_t)e->rows * 64);
+      int32_t cur[2];
+      HIPCHK(hipMemcpy(cur, e->d_cursor.as<int32_t>() + 2 * blk, sizeof cur, hipMemcpyDeviceToHost));
+      const double* src = ((!e->ring && cur[0]) ? e->d_dw1.as<double>() : e->d_dw0.as<double>()) + (size_t)blk * e->rows * 64;
+      HIPCHK(hipMemcpy(dw.data(), src, sizeof(double) * dw.size(), hipMemcpyDeviceToHost));
+      size_t row = e->ring ? (size_t)cur[0] : 0;     // replay the stream layout from the ring cursor: branch down[k] occupies max-over-lanes(m) rows
+      for (int k = 0; k < E; ++k) {
+        const phm::DownStep& d = s.down[k];
+        int m = std::min<int>(mc[(size_t)d.edge * 64 + lane], seg_cap);
+        for (int i = 0; i < m; ++i) seg_dwell[(size_t)d.edge * seg_cap + i] = dw[((row + i) % (size_t)e->rows) * 64 + lane];
+        int mx = 0;
+        for (int l = 0; l < 64; ++l) mx = std::max<int>(mx, mc[(size_t)d.edge * 64 + l]);
+        row += mx;
+      }
     }
   }
-  auto tip_state = [&](int t) -> int {
-    return e->tips_per_replica ? e->tips_host[((size_t)tile * T + t) * 64 + lane] : e->tips_host[t];
-  };
+  auto tip_state = [&](int t) -> int { return e->tips_per_replica ? e->tips_host[((size_t)blk * T + t) * L + lane] : e->tips_host[t]; };
   if (node_states) {
-    std::vector<uint8_t> ns((size_t)s.n_node * 64);
-    HIPCHK(hipMemcpy(ns.data(), e->d_nstate.as<uint8_t>() + (size_t)tile * s.n_node * 64, ns.size(), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> ns((size_t)s.n_node * L);
+    HIPCHK(hipMemcpy(ns.data(), e->d_nstate.as<uint8_t>() + (size_t)blk * s.n_node * L, ns.size(), hipMemcpyDeviceToHost));
     for (int t = 0; t < T; ++t) node_states[t] = tip_state(t) + 1;
-    for (int v = 0; v < s.n_node; ++v) node_states[T + v] = ns[(size_t)v * 64 + lane] + 1;
+    for (int v = 0; v < s.n_node; ++v) node_states[T + v] = ns[(size_t)v * L + lane] + 1;
   }
   if (PL) {
-    std::vector<double> pl((size_t)s.n_node * n * 64);
-    HIPCHK(hipMemcpy(pl.data(), e->d_PL.as<double>() + (size_t)tile * s.n_node * n * 64, sizeof(double) * pl.size(), hipMemcpyDeviceToHost));
+    std::vector<double> pl((size_t)s.n_node * n * L);
+    HIPCHK(hipMemcpy(pl.data(), e->d_PL.as<double>() + (size_t)blk * s.n_node * n * L, sizeof(double) * pl.size(), hipMemcpyDeviceToHost));
     for (int t = 0; t < T; ++t)
       for (int c = 0; c < n; ++c) PL[(size_t)t * n + c] = (c == tip_state(t)) ? 1.0 : 0.0;
     for (int v = 0; v < s.n_node; ++v)
       for (int c = 0; c < n; ++c)
-        PL[(size_t)(T + v) * n + c] = (e->wide && !e->tiled) ? pl[((size_t)v * 64 + lane) * n + c] : pl[((size_t)v * n + c) * 64 + lane];
+        PL[(size_t)(T + v) * n + c] = (e->wide() && e->mapping == PHM_MAP_REPLICAS) ? pl[((size_t)v * L + lane) * n + c] : pl[((size_t)v * n + c) * L + lane];
   }
   return PHM_OK;
 }
@@ -1739,8 +1588,8 @@ int32_t phm_engine_info(phm_engine* e, phm_info* info) {
   info->seg_read = (int64_t)e->seg_total; info->seg_written = 0;
   info->last_run_ms = e->last_ms; info->last_run_launches = e->last_launches; info->iters_done = e->iters_done;
   info->recoveries = e->recoveries;
-  info->mapping = e->narrow ? PHM_MAP_BRANCHES : e->tiled ? PHM_MAP_TILES : PHM_MAP_REPLICAS;
-  info->sparse_chains = (e->tiled && e->wide) ? (e->pwt.band_up > 0 || e->wt_sparse.kernel != nullptr) + 2 * (e->pwt.band_draw > 0) + 4 * (e->wt_sparse.kernel != nullptr) : 0;
+  info->mapping = e->mapping;
+  info->sparse_chains = (e->mapping == PHM_MAP_TILES && e->wide()) ? (e->pwt.band_up > 0 || e->wt_sparse.kernel != nullptr) + 2 * (e->pwt.band_draw > 0) + 4 * (e->wt_sparse.kernel != nullptr) : 0;
   return PHM_OK;
 }
 
@@ -1750,7 +1599,7 @@ int32_t phm_engine_phase_ms(phm_engine* e, double* out4) {
   e = live(e);
   if (!e || !out4) return fail(PHM_ERR_STATE, "engine/out is NULL");
   if (e->dead) return dead_engine();
-  if (!e->phase_timing || !e->tiled) return fail(PHM_ERR_STATE, "phase timing needs phm_options.phase_timing = 1 and a (tile, item) mapping");
+  if (!e->phase_timing || e->mapping != PHM_MAP_TILES) return fail(PHM_ERR_STATE, "phase timing needs phm_options.phase_timing = 1 and a (tile, item) mapping");
   for (int i = 0; i < 4; ++i) out4[i] = e->phase_ms[i];
   return PHM_OK;
 }
@@ -1785,8 +1634,8 @@ extern "C" int32_t phm_engine_time_pruning(phm_engine* e, int32_t n_iters, void*
   e = live(e);
   if (!e || !ms_out) return fail(PHM_ERR_STATE, "engine/ms_out is NULL");
   if (e->dead) return dead_engine();
-  const bool wt = e->wide && e->tiled;
-  if (!wt && (e->wide || e->narrow || e->tiled || e->n_trees > 1)) return fail(PHM_ERR_UNSUPPORTED, "pruning-only timing is implemented for the replica mapping with n_states <= 4 and the lane-per-replica mapping of 5..64 states");
+  const bool wt = e->wide() && e->mapping == PHM_MAP_TILES;
+  if (!wt && (e->wide() || e->mapping != PHM_MAP_REPLICAS || e->n_trees > 1)) return fail(PHM_ERR_UNSUPPORTED, "pruning-only timing is implemented for the replica mapping with n_states <= 4 and the lane-per-replica mapping of 5..64 states");
   if (n_iters < 1) return fail(PHM_ERR_BAD_INPUT, "n_iters must be >= 1");
   HIPCHK(hipSetDevice(e->device));
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
@@ -1794,9 +1643,7 @@ extern "C" int32_t phm_engine_time_pruning(phm_engine* e, int32_t n_iters, void*
   hipError_t le = hipSuccess;
   if (wt) for (int i = 0; i < n_iters && le == hipSuccess; ++i) le = phm::launch_wtiles_up(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_tier_off, stream);
   // iteration index = iters_done keeps the dwell ping-pong parity; nothing but PL is written
-  if (!wt && e->n == 2) { auto p = e->p2; p.prune_only = 1; for (int i = 0; i < n_iters && le == hipSuccess; ++i) le = phm::launch_mcmc<2>(p, e->iters_done, 1, stream); }
-  if (e->n == 3) { auto p = e->p3; p.prune_only = 1; for (int i = 0; i < n_iters && le == hipSuccess; ++i) le = phm::launch_mcmc<3>(p, e->iters_done, 1, stream); }
-  if (e->n == 4) { auto p = e->p4; p.prune_only = 1; for (int i = 0; i < n_iters && le == hipSuccess; ++i) le = phm::launch_mcmc<4>(p, e->iters_done, 1, stream); }
+  small_n(e, [&](auto& sp) { auto p = sp.rep; p.prune_only = 1; for (int i = 0; i < n_iters && le == hipSuccess; ++i) le = phm::launch_mcmc(p, e->iters_done, 1, stream); });
   HIPCHK(le);
   HIPCHK(hipEventRecord(e->ev1, stream));
   HIPCHK(hipStreamSynchronize(stream));

@@ -254,15 +254,23 @@ struct phm_engine {
   int64_t rows = 0;
   DevBuf d_mask;
   DevBuf d_up, d_down, d_col, d_row, d_tips, d_mcount, d_dw0, d_dw1, d_cursor, d_PL, d_nstate, d_stats, d_err, d_seg, d_red, d_red_out;
-  phm::McmcParams<2> p2;
-  phm::McmcParams<3> p3;
-  phm::McmcParams<4> p4;
-  bool wide = false;                   // 5..64 states: phm_wide.hip
+  // The layout of the sweep (PHM_MAP_REPLICAS / BRANCHES / TILES), chosen once at creation; with n > 4 states each has kernels of
+  // its own:  replicas phm_mcmc.hip / phm_wide.hip, branches phm_narrow.hip / phm_wbranch.hip, tiles phm_tiles.hip / phm_wtiles.hip
+  int32_t mapping = PHM_MAP_REPLICAS;
+  bool wide() const { return n > 4; }
+  // by-value parameter blocks of the n <= 4 kernels, one set per state count (small_n in phm_engine.cpp picks the engine's)
+  template <int NS> struct SmallParams {
+    phm::McmcParams<NS> rep;
+    phm::NarrowParams<NS> br;
+    phm::TileParams<NS> tl;
+  };
+  SmallParams<2> s2;
+  SmallParams<3> s3;
+  SmallParams<4> s4;
   bool ring = true;                    // one ring per tile for both dwell streams (else two buffers)
   phm::WideParams pw;
   DevBuf d_B2, d_Bc, d_scale, d_pid;
   // branch-parallel mapping for few chains on a large tree (phm_narrow.hip)
-  bool narrow = false;
   std::vector<int32_t> nw_walk_off;                // depth-level boundaries of the internal-child edges (walk of phm_narrow.hip)
   std::vector<int32_t> nw_tier_off;                // cluster tiers of the one-chain pruning sweep (phm_sched.h ClusterPlan)
   std::vector<int32_t> nw_up_off, nw_down_off;     // level boundaries into up_order / down_order
@@ -274,18 +282,11 @@ struct phm_engine {
   DevBuf d_nw_up_off, d_nw_down_off, d_nw_up_order, d_nw_down_order, d_nw_border, d_nw_off, d_nw_colL, d_nw_rowL, d_nw_maskL, d_nw_mcount, d_nw_dwA, d_nw_dwB,
       d_nw_mstate, d_nw_mlen, d_nw_estate, d_nw_part, d_nw_rowbuf, d_nw_down_lv, d_nw_dmap, d_nw_dmap_edge, d_nw_walk_off, d_nw_edge_parent, d_nw_cl_nodes, d_nw_cl_item_off, d_nw_cl_lvl_ptr, d_nw_cl_lvl_off, d_ell_col, d_ell_val, d_ell2_col, d_ell2_val;
   DevBuf d_wb_cnt;
-  phm::WideBranchParams pwb;                  // n > 4 with `narrow` set: one wave per (replica, branch) (phm_wbranch.hip)
-  phm::NarrowParams<2> n2;
-  phm::NarrowParams<3> n3;
-  phm::NarrowParams<4> n4;
+  phm::WideBranchParams pwb;                  // n > 4, PHM_MAP_BRANCHES: one wave per (replica, branch) (phm_wbranch.hip)
   // wave per (tile, branch) mapping for 10^2 .. 10^5 replicas (phm_tiles.hip); shares the level schedules and long tables
-  bool tiled = false;
   std::vector<int32_t> tl_slot;                    // first row of every branch slot
   DevBuf d_tl_slot, d_tl_pdw, d_tl_pchunk, d_tl_cnt, d_tl_estate, d_tl_pseg, d_tl_segprev;
-  phm::TileParams<2> t2;
-  phm::TileParams<3> t3;
-  phm::TileParams<4> t4;
-  // 5..64 states with `tiled` set: one lane per replica, wave per (tile, item), pruning on the matrix cores (phm_wtiles.hip)
+  // 5..64 states, PHM_MAP_TILES: one lane per replica, wave per (tile, item), pruning on the matrix cores (phm_wtiles.hip)
   phm::WtParams pwt;
   DevBuf d_wt_dwfx, d_wt_segacc, d_wt_B2, d_wt_totL, d_wt_pair_slot, d_wt_slot_col, d_wt_B2band, d_wt_mstate, d_wt_dwfx_tile, d_wt_cnt_tile;
   phm::WtBand wt_band;                            // band of the chain matrix (kernel-argument constants of wt_up_band_kernel)
