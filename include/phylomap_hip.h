@@ -312,6 +312,34 @@ int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double
                                const int32_t* observe, const phm_options* opt,
                                int32_t* tips, int32_t* nodes, double* stats);
 
+/* ---- stochastic maps of sampled and simulated histories ----
+ * phm_simulate_histories / phm_maketreelistEXP that also return each history: R histories (n_replicas simulations, N EXP samples)
+ * over the E = n_edge edge rows.  Row k = r * E + b (0-based, edge-row order) is history r's map on edge row b: segments
+ * [map_off[k], map_off[k+1]) of map_dwell (time) and map_state (1-based, the mapnames convention), from the parent end to the
+ * child end; the first segment has the parent's state, the last the child's (TRUE states for the simulator, whatever `observe`
+ * reports), consecutive segments differ, and each dwell is the double the sampler adds to its statistics.  One history's rows
+ * are a phm_tree map_off / maps / mapnames triple once its offsets are rebased to 0 and narrowed to int32.
+ * Two phases, no state kept between calls:
+ *   sizing  (map_dwell == map_state == NULL): the usual call, and map_off (R*E + 1 int64, map_off[0] = 0) is written;
+ *   filling (both non-NULL): map_off is READ (from a sizing call with the same inputs and seed: draws are addressed by (seed,
+ *           entity, replica), so the same inputs give the same histories); map_cap >= map_off[R*E] is required; the segments are
+ *           written and every other output is bit-identical to the sizing call.  A row whose segment count differs from map_off
+ *           gives PHM_ERR_BAD_INPUT naming the first such row; nothing outside a row's [map_off[k], map_off[k+1]) is written.
+ * Every other argument means what it means for the plain entry point and gives the same bits; n_devices / devices[] shard the
+ * histories and every output is the one-device output bit for bit.  Checks, all before any device call: map_off non-NULL,
+ * R*E + 1 offsets addressable, and when filling: map_off[0] = 0, never decreasing, map_off[R*E] <= map_cap.  Segments that do not
+ * fit in free HBM: PHM_ERR_OOM with the size.  Segment counts: at most 10 000 per row (simulator), 301 (EXP).
+ * phm_maketreelistEXP_maps runs the (tile, branch) kernels: mapping PHM_MAP_AUTO or PHM_MAP_TILES, anything else is
+ * PHM_ERR_UNSUPPORTED; rescale_pruning is honoured.  phm_last_kernel_ms: the sampling kernel plus, when sizing, the offsets scan. */
+int32_t phm_simulate_histories_maps(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
+                                    const int32_t* observe, const phm_options* opt,
+                                    int32_t* tips, int32_t* nodes, double* stats,
+                                    int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
+int32_t phm_maketreelistEXP_maps(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* nen,
+                                 const int32_t* nodelist, int32_t root, int32_t N, const double* lefts, const double* rights,
+                                 const double* d, const phm_options* opt, double* out,
+                                 int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
+
 /* ---- exact conditional expectations given the tips ----
  * For a fixed Q, per site (one tip vector): E[dwell_i | tips], E[N_ij | tips] summed over the tree and per branch, log p(tips | Q)
  * and P(state of node k | tips), by an up (pruning) pass, a down (outside) pass and one uniformization integral per branch

@@ -170,9 +170,11 @@ def eigen_decompose(Q):
     return lefts, rights, np.diag(np.real(vals))
 
 
-def sumstatEXP(z, Q, pid, N, eig=None, **opt):
+def sumstatEXP(z, Q, pid, N, eig=None, maps=False, **opt):
     """R/sumstatEXP.R:21-33 -> phm_maketreelistEXP.  ``eig`` = (lefts, rights, d) overrides the eigendecomposition
-    R/sumstatEXP.R:26-29 computes (LAPACK results differ between machines in the last bits)."""
+    R/sumstatEXP.R:26-29 computes (LAPACK results differ between machines in the last bits).  ``maps=True``: returns
+    ``(out, maps)`` with the N sampled histories as a ``maps.Maps`` (phm_maketreelistEXP_maps: a sizing call, then a filling
+    call; the (tile, branch) mapping)."""
     L = _lib.load()
     Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
     n = Q.shape[0]
@@ -182,12 +184,25 @@ def sumstatEXP(z, Q, pid, N, eig=None, **opt):
     ft = _lib.FlatTree(z)
     o = _lib.make_options(**opt)
     out = np.zeros((N, n + n * (n - 1)), order="F")
-    st = L.phm_maketreelistEXP(C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
-                               _lib._p(nen, C.c_int32), _lib._p(nodelist, C.c_int32), root, int(N),
-                               _lib._p(lefts, C.c_double), _lib._p(rights, C.c_double), _lib._p(d, C.c_double),
-                               C.byref(o), _lib._p(out, C.c_double))
-    _lib.check(st)
-    return out
+    args = (C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(nen, C.c_int32),
+            _lib._p(nodelist, C.c_int32), root, int(N), _lib._p(lefts, C.c_double), _lib._p(rights, C.c_double),
+            _lib._p(d, C.c_double), C.byref(o), _lib._p(out, C.c_double))
+    if not maps:
+        _lib.check(L.phm_maketreelistEXP(*args))
+        return out
+    return out, _two_phase_maps(L.phm_maketreelistEXP_maps, args, int(N), ft.E)
+
+
+def _two_phase_maps(fn, args, R, E):
+    """the sizing call (writes the offsets), then the filling call into arrays of that size"""
+    from .maps import Maps
+    off = np.zeros(R * E + 1, dtype=np.int64)
+    _lib.check(fn(*args, _lib._p(off, C.c_int64), 0, None, None))
+    total = int(off[-1])
+    dwell = np.empty(max(total, 1))
+    state = np.empty(max(total, 1), dtype=np.int32)
+    _lib.check(fn(*args, _lib._p(off, C.c_int64), total, _lib._p(dwell, C.c_double), _lib._p(state, C.c_int32)))
+    return Maps(off, dwell[:total], state[:total], E)
 
 
 def expm_eigen(lefts, rights, d, t, device=-1, mfma=False):
@@ -220,13 +235,15 @@ def expm_pade(Q, t, device=-1, mfma=False):
     return out, ms.value
 
 
-def simulate_histories(z, Q, pid, R, observe=None, nodes=False, **opt):
+def simulate_histories(z, Q, pid, R, observe=None, nodes=False, maps=False, **opt):
     """``R`` independent forward simulations of the chain along the tree of ``z`` (sample2statehistory, R/sourceme.R:346-414)
     -> phm_simulate_histories.  Reads ``z['edge']``, ``z['edge.length']`` and ``z['Nnode']`` only.  ``observe``: n values in
     1..n, the tip state reported for each true state (simulate_4_state_tree's parity map is (1, 2, 1, 2)).
     Returns ``(tips, stats)`` or, with ``nodes=True``, ``(tips, stats, nodes)``: tips [R, n_tips] 1-based (ready for the
     samplers' ``sites=``), stats [R, n + n*n + 1] (dwell per state, jump counts n x n row-major (from, to), root state 0-based),
-    nodes [R, n_tips + Nnode] 1-based true states by ape node id.  Options: seed, replica_offset, device, devices."""
+    nodes [R, n_tips + Nnode] 1-based true states by ape node id.  Options: seed, replica_offset, device, devices.
+    ``maps=True`` appends the R histories as a ``maps.Maps`` (true states; phm_simulate_histories_maps: a sizing call, then a
+    filling call): ``(tips, stats[, nodes], maps)``."""
     L = _lib.load()
     Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
     n = Q.shape[0]
@@ -246,10 +263,13 @@ def simulate_histories(z, Q, pid, R, observe=None, nodes=False, **opt):
     tips = np.zeros((max(R, 1), T), dtype=np.int32)
     nst = np.zeros((max(R, 1), T + Nn), dtype=np.int32) if nodes else None
     stats = np.zeros((max(R, 1), n + n * n + 1), order="F")
-    _lib.check(L.phm_simulate_histories(C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
-                                        _lib._p(obs, C.c_int32), C.byref(o), _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32),
-                                        _lib._p(stats, C.c_double)))
-    return (tips, stats, nst) if nodes else (tips, stats)
+    args = (C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(obs, C.c_int32), C.byref(o),
+            _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32), _lib._p(stats, C.c_double))
+    res = (tips, stats, nst) if nodes else (tips, stats)
+    if not maps:
+        _lib.check(L.phm_simulate_histories(*args))
+        return res
+    return res + (_two_phase_maps(L.phm_simulate_histories_maps, args, max(R, 1), E),)
 
 
 def simulate_state_tree(z, Q, pid, observe=None, **opt):

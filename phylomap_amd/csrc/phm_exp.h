@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "phm_device.h"
+#include "phm_maps.h"
 #include "phm_sched.h"
 
 namespace phm {
@@ -123,8 +124,10 @@ struct ExpTilesParams {
   uint32_t* cnt;                               // [n(n-1)][n_tiles*64]
   double* out;                                 // N x cols column-major
   uint32_t* err;
+  MapsDev maps;                                // stochastic maps (maps_mode != MAPS_OFF), rows it * n_edge + edge row
 };
-// level_off: boundaries of the depth levels in node_order (host)
-hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>& level_off, int branch_blocks, hipStream_t stream);
+// level_off: boundaries of the depth levels in node_order (host); maps_mode: MapMode (phm_maps.h), MAPS_OFF = the plain sampler
+hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>& level_off, int branch_blocks, hipStream_t stream,
+                            int maps_mode = MAPS_OFF);
 
 }  // namespace phm

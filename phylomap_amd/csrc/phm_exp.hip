@@ -695,7 +695,10 @@ __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_node_kernel(ExpTilesParam
 //    point, n(n-1) counters) and reach the per-sample accumulators once per group; NS = 0 (runtime n up to 64): one atomic per segment.
 constexpr int EXP_KL = 12;
 
-template <int NS>
+//  * MODE (phm_maps.h): MAPS_OFF = the plain sampler; MAPS_COUNT also stores every (branch, sample)'s segment count into
+//    p.maps.seg_cnt [edge][tile*64]; MAPS_WRITE also stores every segment (dwell, 1-based state) at the lane's cursor in row
+//    it * n_edge + b of p.maps.  Same draws and statistics in all three.
+template <int NS, int MODE>
 __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_branch_kernel(ExpTilesParams p, int group) {
   __shared__ double s_tm[EXP_BLOCK / 64][EXP_KL][64];
   const int lane = threadIdx.x & 63;
@@ -749,6 +752,19 @@ __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_branch_kernel(ExpTilesPar
       const double* Pb = p.P + (size_t)b * n * n;
       const double tb = p.edge_length[b];
       const double transProb = Pb[(size_t)a_cur * n + e_cur];
+      // maps: segments of this branch so far (count) / the write cursor and the end of row it * E + b (write)
+      const size_t mrow = (size_t)it * p.n_edge + b;
+      int64_t cur = 0, end = 0;
+      if constexpr (MODE == MAPS_WRITE) {
+        if (valid) { cur = p.maps.off[mrow] - p.maps.base; end = p.maps.off[mrow + 1] - p.maps.base; }
+      }
+      auto segment = [&](int col, double v) {
+        stat_add(col, v);
+        if constexpr (MODE == MAPS_WRITE) {
+          if (cur < end) { p.maps.dwell[cur] = v; p.maps.state[cur] = col + 1; }
+        }
+        if constexpr (MODE != MAPS_OFF) ++cur;
+      };
       Stream sr;
       sr.open(ENT_BUNIF | (uint32_t)b, (uint32_t)(it + p.it0), p.replica, p.seed_lo, p.seed_hi);
       uint32_t dr = 0;
@@ -774,11 +790,11 @@ __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_branch_kernel(ExpTilesPar
       }
       if (capped) { if (valid) err |= DERR_UNIF_CAP; continue; }
       if (nj == 0 || (nj == 1 && a_cur == e_cur)) {                               // :138
-        stat_add(a_cur, tb - 0.0);
+        segment(a_cur, tb - 0.0);
       } else if (nj == 1) {                                                       // :144
         const double tj = tb * sr.draw(dr++);
-        stat_add(a_cur, tj - 0.0);
-        stat_add(e_cur, tb - tj);
+        segment(a_cur, tj - 0.0);
+        segment(e_cur, tb - tj);
         count(a_cur, e_cur);
       } else {
         const bool in_lds = nj <= EXP_KL;
@@ -817,13 +833,17 @@ __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_branch_kernel(ExpTilesPar
           }
           if (prev != di) {                                                       // :168-173 drop virtual jumps
             const double ti = tm_get(i - 1);
-            stat_add(sprev, ti - tprev);
+            segment(sprev, ti - tprev);
             count(sprev, di);
             tprev = ti; sprev = di;
           }
           prev = di;
         }
-        stat_add(sprev, tb - tprev);
+        segment(sprev, tb - tprev);
+      }
+      if constexpr (MODE == MAPS_COUNT) p.maps.seg_cnt[(size_t)b * npad + it] = (uint16_t)cur;   // one 128-byte row per wave
+      if constexpr (MODE == MAPS_WRITE) {
+        if (valid && cur != end) atomicMin(p.maps.bad_row, (unsigned long long)mrow);
       }
     }
     if (NS > 0 && valid) {
@@ -848,7 +868,16 @@ __global__ void exp_tiles_finish_kernel(ExpTilesParams p) {
 
 }  // namespace
 
-hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>& level_off, int branch_blocks, hipStream_t stream) {
+template <int MODE>
+void launch_exp_tiles_branch(const ExpTilesParams& p, int branch_blocks, int group, hipStream_t stream) {
+  if (p.n_states == 2) hipLaunchKernelGGL((exp_tiles_branch_kernel<2, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
+  else if (p.n_states == 3) hipLaunchKernelGGL((exp_tiles_branch_kernel<3, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
+  else if (p.n_states == 4) hipLaunchKernelGGL((exp_tiles_branch_kernel<4, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
+  else hipLaunchKernelGGL((exp_tiles_branch_kernel<0, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
+}
+
+hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>& level_off, int branch_blocks, hipStream_t stream,
+                            int maps_mode) {
   constexpr int W = EXP_BLOCK / 64;
   hipLaunchKernelGGL(exp_tiles_root_kernel, dim3((p.n_tiles + W - 1) / W), dim3(EXP_BLOCK), 0, stream, p);
   for (size_t l = 0; l + 1 < level_off.size(); ++l) {
@@ -857,10 +886,9 @@ hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>&
   }
   // branches per wave-item: as many as still leave every SIMD a few waves (an R call with N = 1 000 samples has 16 tiles)
   const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.n_edge * p.n_tiles / 8192));
-  if (p.n_states == 2) hipLaunchKernelGGL(exp_tiles_branch_kernel<2>, dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else if (p.n_states == 3) hipLaunchKernelGGL(exp_tiles_branch_kernel<3>, dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else if (p.n_states == 4) hipLaunchKernelGGL(exp_tiles_branch_kernel<4>, dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else hipLaunchKernelGGL(exp_tiles_branch_kernel<0>, dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
+  if (maps_mode == MAPS_COUNT) launch_exp_tiles_branch<MAPS_COUNT>(p, branch_blocks, group, stream);
+  else if (maps_mode == MAPS_WRITE) launch_exp_tiles_branch<MAPS_WRITE>(p, branch_blocks, group, stream);
+  else launch_exp_tiles_branch<MAPS_OFF>(p, branch_blocks, group, stream);
   const int64_t cells = (int64_t)(p.n_states + p.n_states * (p.n_states - 1)) * p.N;
   hipLaunchKernelGGL(exp_tiles_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
   return hipGetLastError();

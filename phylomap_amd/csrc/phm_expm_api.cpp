@@ -1,6 +1,7 @@
 // phm_expm_api.cpp -- C-ABI of the matrix-exponentiation path: batched transition matrices (eigen route, Pade route, their
 // MFMA f64 variants) and the sumstatEXP driver (maketreelistEXP, src/phylomap.cpp:3001-3051).
 #include "phm_internal.h"
+#include "phm_maps_host.h"
 
 namespace {
 
@@ -124,7 +125,8 @@ int32_t phm_expm_pade_mfma(int32_t n, const double* Q, const double* t, int32_t 
 // samples [it0, it0 + N) of the call on one device; out: the caller's column-major matrix of ld_out rows, rows it0 .. it0 + N - 1
 static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* nen,
                            const int32_t* nodelist, int32_t root, int32_t N, int32_t it0, const double* lefts, const double* rights,
-                           const double* d, const phm_options& o, int32_t device, double* out, int64_t ld_out) {
+                           const double* d, const phm_options& o, int32_t device, double* out, int64_t ld_out,
+                           phm_maps::Host* mh = nullptr, size_t si = 0) {
   if (!x || !Q || !pid || !lefts || !rights || !d || !out) return fail(PHM_ERR_BAD_INPUT, "phm_maketreelistEXP: NULL argument");
   if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
   if (n < 2) return fail(PHM_ERR_BAD_INPUT, "n_states must be >= 2");
@@ -220,7 +222,8 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
   // Mapping (phm_options.mapping): 1 = one wave per tile of 64 samples walks the tree (exp_sample_kernel / exp_wide_kernel);
   // 3 = one wave per (tile, branch) (exp_tiles_*); 0 = automatic: the (tile, branch) mapping unless there are so many samples
   // that the tiles alone fill the chip.
-  const bool use_tiles = o.mapping == PHM_MAP_TILES || (o.mapping == PHM_MAP_AUTO && tiles < EXP_TILES_AUTO_MAX_TILES);
+  // maps (phm_maketreelistEXP_maps) come from the (tile, branch) kernels only
+  const bool use_tiles = mh || o.mapping == PHM_MAP_TILES || (o.mapping == PHM_MAP_AUTO && tiles < EXP_TILES_AUTO_MAX_TILES);
   if (use_tiles) {
     // edges with an internal child, grouped by depth (parents' states are drawn a level earlier)
     std::vector<int32_t> depth(s.n_node, 0), order, level_off;
@@ -259,13 +262,21 @@ static int32_t exp_oneshot(const phm_tree* x, int32_t n, const double* Q, const 
     p.P = dP.as<double>(); p.PL = dPL.as<double>(); p.edge_length = dt.as<double>(); p.colpow = dcol.as<double>(); p.B2 = dB2.as<double>();
     p.tips = dtips.as<uint8_t>(); p.nstate = dnst.as<uint8_t>(); p.times = dtm.as<double>();
     p.dwfx = ddw.as<unsigned long long>(); p.cnt = dcnt.as<uint32_t>(); p.out = dout.as<double>(); p.err = derr.as<uint32_t>();
+    phm_maps::Shard ms;
+    if (mh) {
+      st = ms.setup(*mh, it0, N, (int64_t)npad, p.maps);
+      if (st) return st;
+    }
     HIPCHK(hipEventRecord(ev0, nullptr));      // (re-recorded: the set-up above is not part of the sampler's time)
-    HIPCHK(phm::launch_exp_tiles(p, level_off, branch_blocks, nullptr));
+    HIPCHK(phm::launch_exp_tiles(p, level_off, branch_blocks, nullptr, mh ? mh->mode : phm::MAPS_OFF));
+    if (mh) HIPCHK(ms.after_kernel(*mh, (int64_t)npad, nullptr));      // sizing: counts -> offsets
     HIPCHK(hipEventRecord(ev1, nullptr));
     HIPCHK(hipEventSynchronize(ev1));
-    { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms; }
+    { float ms_ = 0.f; if (hipEventElapsedTime(&ms_, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms_; }
     (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-    return copy_out();
+    st = copy_out();
+    if (st || !mh) return st;
+    return ms.copy_home(*mh, si, "phm_maketreelistEXP_maps");
   }
   auto fill = [&](auto& p) {
     p.n_tips = T; p.n_node = s.n_node; p.n_edge = E; p.root = s.root; p.N = N; p.n_tiles = tiles; p.it0 = it0;
@@ -318,6 +329,33 @@ int32_t phm_maketreelistEXP(const phm_tree* x, int32_t n, const double* Q, const
   return run_shards(shards, [&](const phm_shard& sh, size_t) {
     return exp_oneshot(x, n, Q, pid, nen, nodelist, root, (int32_t)sh.count, (int32_t)sh.first, lefts, rights, d, o, sh.device, out, N);
   });
+}
+
+// The same call, plus the stochastic maps of the N samples, from the (tile, branch) kernels: a sizing call
+// (map_dwell and map_state NULL) writes map_off, a filling call reads it and writes the segments.
+int32_t phm_maketreelistEXP_maps(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* nen,
+                                 const int32_t* nodelist, int32_t root, int32_t N, const double* lefts, const double* rights,
+                                 const double* d, const phm_options* opt_in, double* out,
+                                 int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state) {
+  if (!x || !out) return fail(PHM_ERR_BAD_INPUT, "phm_maketreelistEXP_maps: NULL argument");
+  if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
+  const phm_options o = resolve_options(opt_in);
+  if (o.mapping != PHM_MAP_AUTO && o.mapping != PHM_MAP_TILES)
+    return fail(PHM_ERR_UNSUPPORTED, "phm_maketreelistEXP_maps: maps come from the (tile, branch) kernels (mapping PHM_MAP_AUTO or PHM_MAP_TILES)");
+  phm_maps::Host mh;
+  int32_t st = phm_maps::validate("phm_maketreelistEXP_maps", N, x->n_edge, map_off, map_cap, map_dwell, map_state, mh);
+  if (st) return st;
+  std::vector<phm_shard> shards;
+  st = phm_plan_shards(o, N, shards);
+  if (st) return st;
+  mh.shard_total.assign(shards.size(), 0);
+  st = run_shards(shards, [&](const phm_shard& sh, size_t i) {
+    return exp_oneshot(x, n, Q, pid, nen, nodelist, root, (int32_t)sh.count, (int32_t)sh.first, lefts, rights, d, o, sh.device, out, N,
+                       &mh, i);
+  });
+  if (st) return st;
+  phm_maps::finish_sizing(mh, shards);
+  return PHM_OK;
 }
 
 double phm_last_kernel_ms(void) { return g_phm_last_kernel_ms; }

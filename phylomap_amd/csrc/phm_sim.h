@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "phm_device.h"
+#include "phm_maps.h"
 #include "phm_sched.h"
 
 namespace phm {
@@ -30,9 +31,11 @@ struct SimParams {
   uint8_t* nstate;                             // [node id - 1][n_rep_pad] 0-based true states
   double* stats;                               // [col][n_rep_pad]: dwell (n), counts (n x n, row-major from,to), root state
   uint32_t* err;                               // [0] device error bits; [1] lowest edge row (0-based) past SIM_MAX_JUMPS
+  MapsDev maps;                                // stochastic maps (maps_mode != MAPS_OFF), rows r * n_edge + edge row
 };
 
-hipError_t launch_simulate(const SimParams& p, hipStream_t stream);
+// maps_mode: MapMode (phm_maps.h); MAPS_OFF is the plain simulation
+hipError_t launch_simulate(const SimParams& p, hipStream_t stream, int maps_mode = MAPS_OFF);
 // out[r * rows + i] = map[nstate[i][r]] for i < rows, r < n_rep (replica-major int32; map: n 1-based states)
 hipError_t launch_sim_transpose(const uint8_t* nstate, int rows, int n_rep, int n_rep_pad, const int32_t* map, int32_t* out,
                                 hipStream_t stream);

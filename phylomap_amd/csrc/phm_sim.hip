@@ -27,7 +27,9 @@ __device__ __forceinline__ int sim_categorical(const double* __restrict__ w, dou
   return idx;
 }
 
-template <int NS>
+// MODE (phm_maps.h): MAPS_OFF = the plain simulation; MAPS_COUNT also stores every branch's segment count; MAPS_WRITE also
+// stores every segment (dwell, 1-based true state) at the lane's cursor in its row of p.maps.  The draws are the same in all three.
+template <int NS, int MODE>
 __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
   constexpr int QN = NS > 0 ? NS : SIM_MAX_STATES;
   constexpr int AN = NS > 0 ? NS : 1;
@@ -85,16 +87,27 @@ __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
     const size_t parent_row = (size_t)(T + d.parent), child_row = (size_t)(d.child >= 0 ? T + d.child : ~d.child);
     const double t = p.edge_length[d.edge];
     int s = p.nstate[parent_row * pad + r];
+    // maps: segments of this branch so far (count) / the write cursor and the end of row r * E + edge (write)
+    const size_t mrow = (size_t)r * p.n_edge + d.edge;
+    int64_t cur = 0, end = 0;
+    if constexpr (MODE == MAPS_WRITE) { cur = p.maps.off[mrow] - p.maps.base; end = p.maps.off[mrow + 1] - p.maps.base; }
+    auto segment = [&](int st, double x) {
+      add_dwell(st, x);
+      if constexpr (MODE == MAPS_WRITE) {
+        if (cur < end) { p.maps.dwell[cur] = x; p.maps.state[cur] = st + 1; }
+      }
+      if constexpr (MODE != MAPS_OFF) ++cur;
+    };
     Stream rs;
     rs.open(ENT_BSTATE | (uint32_t)d.edge, SIM_ITER, rep, p.seed_lo, p.seed_hi);
     double pos = 0.0;
     for (uint32_t j = 0;; ++j) {
       const double ir = s_inv[s];
-      if (ir == 0.0) { add_dwell(s, t - pos); break; }           // absorbing: the rest of the branch, no draw
+      if (ir == 0.0) { segment(s, t - pos); break; }             // absorbing: the rest of the branch, no draw
       const double gap = ir * neglog_u32(rs.draw_word(2u * j), s_ltab);
       const double dab = pos + gap;
-      if (!(dab < t)) { add_dwell(s, gap - (dab - t)); break; }  // seg_len - (dab - branchlength)
-      add_dwell(s, gap);
+      if (!(dab < t)) { segment(s, gap - (dab - t)); break; }    // seg_len - (dab - branchlength)
+      segment(s, gap);
       if (j == (uint32_t)SIM_MAX_JUMPS) { err |= DERR_CAPACITY; atomicMin(&p.err[1], (uint32_t)d.edge); break; }
       const int nx = sim_categorical<NS>(&s_q[s * n], s_tot[s], n, rs.draw(2u * j + 1u), err);
       if constexpr (NS > 0) {
@@ -109,6 +122,10 @@ __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
       pos = dab;
     }
     p.nstate[child_row * pad + r] = (uint8_t)s;
+    if constexpr (MODE == MAPS_COUNT) p.maps.seg_cnt[(size_t)d.edge * pad + r] = (uint16_t)cur;   // one 128-byte row per wave
+    if constexpr (MODE == MAPS_WRITE) {
+      if (cur != end) atomicMin(p.maps.bad_row, (unsigned long long)mrow);
+    }
   }
 
   if constexpr (NS > 0) {
@@ -144,14 +161,21 @@ __global__ __launch_bounds__(256) void sim_transpose_kernel(const uint8_t* __res
 
 }  // namespace
 
-hipError_t launch_simulate(const SimParams& p, hipStream_t stream) {
+template <int MODE>
+void launch_simulate_mode(const SimParams& p, hipStream_t stream) {
   const dim3 grid((p.n_rep + SIM_BLOCK - 1) / SIM_BLOCK);
   switch (p.n_states) {
-    case 2: hipLaunchKernelGGL((sim_kernel<2>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    case 3: hipLaunchKernelGGL((sim_kernel<3>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    case 4: hipLaunchKernelGGL((sim_kernel<4>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    default: hipLaunchKernelGGL((sim_kernel<0>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
+    case 2: hipLaunchKernelGGL((sim_kernel<2, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
+    case 3: hipLaunchKernelGGL((sim_kernel<3, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
+    case 4: hipLaunchKernelGGL((sim_kernel<4, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
+    default: hipLaunchKernelGGL((sim_kernel<0, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
   }
+}
+
+hipError_t launch_simulate(const SimParams& p, hipStream_t stream, int maps_mode) {
+  if (maps_mode == MAPS_COUNT) launch_simulate_mode<MAPS_COUNT>(p, stream);
+  else if (maps_mode == MAPS_WRITE) launch_simulate_mode<MAPS_WRITE>(p, stream);
+  else launch_simulate_mode<MAPS_OFF>(p, stream);
   return hipGetLastError();
 }
 

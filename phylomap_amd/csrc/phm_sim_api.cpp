@@ -2,6 +2,7 @@
 // samplethebranch (R/sourceme.R:346-414), simulate_2_state_tree / simulate_4_state_tree (R/simulate_*_state_tree.R) for many
 // replicas in one call.  Validation on the host, one kernel launch per device, a transposing epilogue for the state matrices.
 #include "phm_internal.h"
+#include "phm_maps_host.h"
 #include "phm_sim.h"
 
 namespace {
@@ -68,9 +69,9 @@ int32_t sim_validate(const phm_tree* x, int32_t n, const double* Q, const double
 }
 
 // Replicas [first, first + R) of the call on one device.  tips / nodes / stats point at the caller's full matrices; stats has
-// ld_stats rows (the call's replica count).
+// ld_stats rows (the call's replica count).  mh: the maps of phm_simulate_histories_maps (NULL: none), shard index `si`.
 int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device, int64_t first, int32_t R, int32_t* tips, int32_t* nodes,
-                       double* stats, int64_t ld_stats) {
+                       double* stats, int64_t ld_stats, phm_maps::Host* mh = nullptr, size_t si = 0) {
   int32_t st = select_device(device);
   if (st) return st;
   const int n = in.n, T = in.T, E = in.E, rows = in.T + in.Nn, cols = n + n * n + 1;
@@ -98,11 +99,18 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
   p.seed_lo = (uint32_t)(o.seed & 0xFFFFFFFFull); p.seed_hi = (uint32_t)(o.seed >> 32);
   p.down = ddown.as<phm::DownStep>(); p.qoff = dq.as<double>(); p.inv_rate = dinv.as<double>(); p.pid = dpid.as<double>();
   p.edge_length = dlen.as<double>(); p.nstate = dns.as<uint8_t>(); p.stats = dstats.as<double>(); p.err = derr.as<uint32_t>();
+  const int maps_mode = mh ? mh->mode : phm::MAPS_OFF;
+  phm_maps::Shard msh;
+  if (mh) {
+    st = msh.setup(*mh, first, R, pad, p.maps);
+    if (st) return st;
+  }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   HIPCHK(hipEventCreate(&ev0));
   if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(PHM_ERR_NO_DEVICE, "hipEventCreate failed"); }
   hipError_t le = hipEventRecord(ev0, nullptr);
-  if (le == hipSuccess) le = phm::launch_simulate(p, nullptr);
+  if (le == hipSuccess) le = phm::launch_simulate(p, nullptr, maps_mode);
+  if (le == hipSuccess && mh) le = msh.after_kernel(*mh, pad, nullptr);      // sizing: counts -> offsets
   if (le == hipSuccess) le = hipEventRecord(ev1, nullptr);
   if (le == hipSuccess) le = hipEventSynchronize(ev1);
   float ms = 0.f;
@@ -116,6 +124,10 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
                                       " (samplethebranch stops there, R/sourceme.R:356)");
   st = device_status(errh[0]);
   if (st) return st;
+  if (mh) {
+    st = msh.copy_home(*mh, si, "phm_simulate_histories_maps");
+    if (st) return st;
+  }
   // statistics: [col][pad] -> the caller's column-major ld_stats x cols matrix, rows first .. first + R - 1
   HIPCHK(hipMemcpy2D(stats + first, sizeof(double) * ld_stats, dstats.p, sizeof(double) * pad, sizeof(double) * R, cols,
                      hipMemcpyDeviceToHost));
@@ -147,6 +159,31 @@ int32_t phm_simulate_histories(const phm_tree* x, int32_t n_states, const double
   return run_shards(shards, [&](const phm_shard& sh, size_t) {
     return sim_one_device(in, o, sh.device, sh.first, (int32_t)sh.count, tips, nodes, stats, R);
   });
+}
+
+// The same call, plus the stochastic maps of the histories: a sizing call (map_dwell and map_state NULL)
+// writes map_off, a filling call reads it and writes the segments.  Every check runs before any device call.
+int32_t phm_simulate_histories_maps(const phm_tree* x, int32_t n_states, const double* Q, const double* pid, const int32_t* observe,
+                                    const phm_options* opt, int32_t* tips, int32_t* nodes, double* stats,
+                                    int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state) {
+  const phm_options o = resolve_options(opt);
+  SimInput in;
+  int32_t st = sim_validate(x, n_states, Q, pid, observe, o, tips, stats, in);
+  if (st) return st;
+  const int32_t R = std::max(1, (int)o.n_replicas);
+  phm_maps::Host mh;
+  st = phm_maps::validate("phm_simulate_histories_maps", R, in.E, map_off, map_cap, map_dwell, map_state, mh);
+  if (st) return st;
+  std::vector<phm_shard> shards;
+  st = phm_plan_shards(o, R, shards);
+  if (st) return st;
+  mh.shard_total.assign(shards.size(), 0);
+  st = run_shards(shards, [&](const phm_shard& sh, size_t i) {
+    return sim_one_device(in, o, sh.device, sh.first, (int32_t)sh.count, tips, nodes, stats, R, &mh, i);
+  });
+  if (st) return st;
+  phm_maps::finish_sizing(mh, shards);
+  return PHM_OK;
 }
 
 }  // extern "C"
