@@ -185,40 +185,27 @@ struct DicLoglik {
   int32_t setup(int variant, const phm_tree* x, int n_, const double* pid, const int32_t* nen, int32_t N) {
     n = n_; E = x->n_edge; Nn = x->n_node; T = x->n_tips;
     const size_t nn = (size_t)n * n;
-    std::vector<phm::UpStep> upn(Nn);
+    std::vector<phm::UpStep> upn(Nn);                   // nen lists children before parents (checked by the caller)
     const int32_t* e1 = x->edge; const int32_t* e2 = x->edge + E;
     auto code = [&](int32_t node) { return node > T ? node - T - 1 : ~(node - 1); };
-    std::vector<int32_t> height(Nn, 0);
-    int max_h = 0;
     for (int i = 0; i < Nn; ++i) {
       const int ea = nen[2 * i] - 1, eb = nen[2 * i + 1] - 1;
       upn[i].parent = e1[ea] - T - 1;
       upn[i].child[0] = code(e2[ea]); upn[i].child[1] = code(e2[eb]);
       upn[i].edge[0] = ea; upn[i].edge[1] = eb;
-      int h = 0;                                        // nen lists children before parents (checked by the caller)
-      for (int c = 0; c < 2; ++c) if (upn[i].child[c] >= 0) h = std::max(h, height[upn[i].child[c]] + 1);
-      height[upn[i].parent] = h; max_h = std::max(max_h, h);
     }
-    level_off.assign(max_h + 2, 0);
-    for (int i = 0; i < Nn; ++i) level_off[height[upn[i].parent] + 1]++;
-    for (size_t l = 1; l < level_off.size(); ++l) level_off[l] += level_off[l - 1];
-    std::vector<int32_t> order(Nn), pos(level_off.begin(), level_off.end() - 1);
-    for (int i = 0; i < Nn; ++i) order[pos[height[upn[i].parent]]++] = i;
+    std::vector<int32_t> order;
+    phm::height_levels(upn, order, level_off);
     std::vector<double> PLh((size_t)(2 * T - 1) * n, 0.0);
     for (int t = 0; t < T; ++t) {
       if (variant == PHM_MCMC_BF) PLh[(size_t)t * n + (x->states[t] - 1)] = 1.0;                         // :3165
       else for (int j = (x->states[t] % 2 == 0) ? 1 : 0; j < n; j += 2) PLh[(size_t)t * n + j] = 1.0;   // :3275-3282
     }
-    HIPCHK(dorder.alloc(sizeof(int32_t) * Nn)); HIPCHK(dlogs.alloc(sizeof(double) * Nn));
-    HIPCHK(dQ.alloc(sizeof(double) * nn)); HIPCHK(dt.alloc(sizeof(double) * E)); HIPCHK(ds.alloc(sizeof(int32_t) * E));
+    HIPCHK(upload(dorder, order)); HIPCHK(dlogs.alloc(sizeof(double) * Nn));
+    HIPCHK(dQ.alloc(sizeof(double) * nn)); HIPCHK(upload(dt, x->edge_length, E)); HIPCHK(ds.alloc(sizeof(int32_t) * E));
     HIPCHK(dwork.alloc(sizeof(double) * nn * 5 * E)); HIPCHK(dP.alloc(sizeof(double) * nn * E));
-    HIPCHK(dPL0.alloc(sizeof(double) * PLh.size())); HIPCHK(dPL.alloc(sizeof(double) * PLh.size()));
-    HIPCHK(dpid.alloc(sizeof(double) * n)); HIPCHK(dup.alloc(sizeof(phm::UpStep) * Nn)); HIPCHK(derr.alloc(sizeof(uint32_t)));
-    HIPCHK(hipMemcpy(dorder.p, order.data(), dorder.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dt.p, x->edge_length, dt.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dPL0.p, PLh.data(), dPL0.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpid.p, pid, dpid.bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dup.p, upn.data(), dup.bytes, hipMemcpyHostToDevice));
+    HIPCHK(upload(dPL0, PLh)); HIPCHK(dPL.alloc(sizeof(double) * PLh.size()));
+    HIPCHK(upload(dpid, pid, n)); HIPCHK(upload(dup, upn)); HIPCHK(derr.alloc(sizeof(uint32_t)));
     HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
     HIPCHK(pin_dic.reserve(sizeof(double) * nn + sizeof(int32_t) * E));
     HIPCHK(pin_ll.reserve(sizeof(double) * N));

@@ -117,13 +117,6 @@ int32_t alloc_stats(phm_engine* e) {
   return PHM_OK;
 }
 
-// host vector -> a device buffer of its size
-template <typename T>
-hipError_t to_device(DevBuf& d, const std::vector<T>& v) {
-  hipError_t err = d.alloc(sizeof(T) * v.size());
-  return err == hipSuccess ? hipMemcpy(d.p, v.data(), d.bytes, hipMemcpyHostToDevice) : err;
-}
-
 // Per-branch slots of the branch-parallel mappings: 1 + Poisson(Omega t_b) segments in stationarity, provisioned far into the tail
 // (cap_tail, else default_slot_tail) because a slot has no neighbour to borrow from (an overflow is recovered by rebuilding with
 // doubled slots); longer caller-supplied paths get m0 on top.  Sets nw_total_cap, nw_klong and rows.
@@ -182,10 +175,10 @@ void single_tree_tips(phm_engine* e, const phm_tree* x) {
 // A cluster plan of the tree passes (phm_sched.h) to the device; its tiers stay on the host (nw_tier_off)
 int32_t upload_cluster_plan(phm_engine* e, const phm::ClusterPlan& plan, bool item_off) {
   e->nw_tier_off = plan.tier_off;
-  HIPCHK(to_device(e->d_nw_cl_nodes, plan.nodes));
-  if (item_off) HIPCHK(to_device(e->d_nw_cl_item_off, plan.item_off));
-  HIPCHK(to_device(e->d_nw_cl_lvl_ptr, plan.lvl_ptr));
-  HIPCHK(to_device(e->d_nw_cl_lvl_off, plan.lvl_off));
+  HIPCHK(upload(e->d_nw_cl_nodes, plan.nodes));
+  if (item_off) HIPCHK(upload(e->d_nw_cl_item_off, plan.item_off));
+  HIPCHK(upload(e->d_nw_cl_lvl_ptr, plan.lvl_ptr));
+  HIPCHK(upload(e->d_nw_cl_lvl_off, plan.lvl_off));
   return PHM_OK;
 }
 
@@ -193,10 +186,7 @@ int32_t upload_cluster_plan(phm_engine* e, const phm::ClusterPlan& plan, bool it
 int32_t init_tile_paths(phm_engine* e, const phm_tree* x) {
   const int E = e->sched.n_edge;
   DevBuf d_off, d_maps;
-  HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
-  HIPCHK(d_maps.alloc(sizeof(double) * (size_t)x->map_off[E]));
-  HIPCHK(hipMemcpy(d_off.p, x->map_off, d_off.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_maps.p, x->maps, d_maps.bytes, hipMemcpyHostToDevice));
+  HIPCHK(upload(d_off, x->map_off, E + 1)); HIPCHK(upload(d_maps, x->maps, x->map_off[E]));
   HIPCHK(phm::launch_tiles_init(E, e->tiles, e->rows, e->d_tl_slot.as<int32_t>(), d_off.as<int32_t>(), d_maps.as<double>(),
                                 e->d_dw0.as<double>(), e->d_mcount.as<uint16_t>(), nullptr));
   HIPCHK(hipDeviceSynchronize());
@@ -493,57 +483,31 @@ void fill_narrow_params(phm_engine* e, phm::NarrowParams<NS>& p, const phm_optio
   }
 }
 
-// Level schedules shared by the branch-parallel mappings: positions of up[] grouped by HEIGHT (children strictly below their
-// parent) and of down[] grouped by DEPTH; uploads the two order arrays, leaves the level boundaries in the engine.
+// Level schedules shared by the branch-parallel mappings: positions of up[] grouped by HEIGHT and of down[] grouped by DEPTH
+// (phm_sched.h); uploads the two order arrays, leaves the level boundaries in the engine.
 int32_t build_level_orders(phm_engine* e) {
   const phm::Schedule& s = e->sched;
-  const int E = s.n_edge, Nn = s.n_node;
-  std::vector<int32_t> height(Nn, 0), depth(Nn, 0);
-  int max_h = 0, max_d = 0;
-  for (int k = 0; k < Nn; ++k) {
-    const phm::UpStep& u = s.up[k];
-    int h = 0;
-    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) h = std::max(h, height[u.child[c]] + 1);
-    height[u.parent] = h; max_h = std::max(max_h, h);
-  }
-  std::vector<int32_t> edepth(E, 0);
-  for (int k = 0; k < E; ++k) {
-    const phm::DownStep& d = s.down[k];
-    edepth[k] = depth[d.parent];
-    if (d.child >= 0) depth[d.child] = depth[d.parent] + 1;
-    max_d = std::max(max_d, edepth[k]);
-  }
-  std::vector<int32_t> up_order(Nn), down_order(E);
-  e->nw_up_off.assign(max_h + 2, 0); e->nw_down_off.assign(max_d + 2, 0);
-  for (int k = 0; k < Nn; ++k) e->nw_up_off[height[s.up[k].parent] + 1]++;
-  for (int k = 0; k < E; ++k) e->nw_down_off[edepth[k] + 1]++;
-  for (size_t l = 1; l < e->nw_up_off.size(); ++l) e->nw_up_off[l] += e->nw_up_off[l - 1];
-  for (size_t l = 1; l < e->nw_down_off.size(); ++l) e->nw_down_off[l] += e->nw_down_off[l - 1];
-  {
-    std::vector<int32_t> pu(e->nw_up_off.begin(), e->nw_up_off.end() - 1), pd(e->nw_down_off.begin(), e->nw_down_off.end() - 1);
-    for (int k = 0; k < Nn; ++k) up_order[pu[height[s.up[k].parent]]++] = k;
-    for (int k = 0; k < E; ++k) down_order[pd[edepth[k]]++] = k;
-  }
-  HIPCHK(to_device(e->d_nw_up_order, up_order)); HIPCHK(to_device(e->d_nw_down_order, down_order));
+  const int E = s.n_edge;
+  std::vector<int32_t> up_order, down_order;
+  phm::height_levels(s.up, up_order, e->nw_up_off);
+  phm::depth_levels(s, down_order, e->nw_down_off);
+  HIPCHK(upload(e->d_nw_up_order, up_order)); HIPCHK(upload(e->d_nw_down_order, down_order));
   if (!e->wide()) {
     // phm_narrow.hip: the sampling steps themselves (no indirection).  Edges that lead to an INTERNAL node first, grouped by depth
     // level -- the walk propagates states only along those --, then the tip edges; boundaries of the first part in nw_walk_off
+    std::vector<int32_t> walk;
+    phm::depth_levels(s, walk, e->nw_walk_off, true);
     std::vector<phm::DownStep> walk_lv;
     walk_lv.reserve(E);
-    e->nw_walk_off.assign(1, 0);
-    for (int l = 0; l + 1 < (int)e->nw_down_off.size(); ++l) {
-      for (int i = e->nw_down_off[l]; i < e->nw_down_off[l + 1]; ++i)
-        if (s.down[down_order[i]].child >= 0) walk_lv.push_back(s.down[down_order[i]]);
-      if ((int)walk_lv.size() > e->nw_walk_off.back()) e->nw_walk_off.push_back((int)walk_lv.size());
-    }
-    for (int i = 0; i < E; ++i) if (s.down[down_order[i]].child < 0) walk_lv.push_back(s.down[down_order[i]]);
+    for (int k : walk) walk_lv.push_back(s.down[k]);
+    for (int k : down_order) if (s.down[k].child < 0) walk_lv.push_back(s.down[k]);
     std::vector<int32_t> edge_parent(E);
     for (int i = 0; i < E; ++i) edge_parent[s.down[i].edge] = s.down[i].parent;
-    HIPCHK(to_device(e->d_nw_down_lv, walk_lv));
-    HIPCHK(to_device(e->d_nw_walk_off, e->nw_walk_off));
-    HIPCHK(to_device(e->d_nw_edge_parent, edge_parent));
+    HIPCHK(upload(e->d_nw_down_lv, walk_lv));
+    HIPCHK(upload(e->d_nw_walk_off, e->nw_walk_off));
+    HIPCHK(upload(e->d_nw_edge_parent, edge_parent));
   }
-  HIPCHK(to_device(e->d_nw_up_off, e->nw_up_off)); HIPCHK(to_device(e->d_nw_down_off, e->nw_down_off));
+  HIPCHK(upload(e->d_nw_up_off, e->nw_up_off)); HIPCHK(upload(e->d_nw_down_off, e->nw_down_off));
   return PHM_OK;
 }
 
@@ -580,16 +544,16 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
   const size_t need = n_dw * dw_bytes + (e->wide() ? (size_t)S * e->nw_total_cap : 0) + stats_bytes(e) + dmap_bytes + small_bytes +
                       sizeof(double) * (3 * tab + (size_t)S * E * part_cols + (e->wide() ? 2 * (size_t)S * e->dcols : 0));
   if (int32_t st = check_hbm(need, free_b)) return st;
-  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  HIPCHK(upload(e->d_up, s.up)); HIPCHK(upload(e->d_down, s.down));
   if (int32_t st = build_level_orders(e)) return st;
-  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_nw_off, e->nw_off));
+  HIPCHK(upload(e->d_nw_border, sp.order)); HIPCHK(upload(e->d_nw_off, e->nw_off));
   if (e->wide()) {
     HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
     HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * n));
   } else {      // n <= 4: the three tables in one block (colL | rowL | maskL): a model update is ONE host-to-device copy
     HIPCHK(e->d_nw_colL.alloc(sizeof(double) * (2 * tab + (size_t)e->nw_klong * 2 * n)));
   }
-  HIPCHK(to_device(e->d_tips, e->tips_host));
+  HIPCHK(upload(e->d_tips, e->tips_host));
   HIPCHK(e->d_nw_mcount.alloc(sizeof(int32_t) * (size_t)S * E));
   HIPCHK(e->d_nw_dwA.alloc(dw_bytes)); HIPCHK(e->d_nw_dwB.alloc(dw_bytes));
   if (e->wide()) {
@@ -635,7 +599,7 @@ int32_t narrow_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     HIPCHK(e->d_B2.alloc(sizeof(double) * n * n)); HIPCHK(e->d_Bc.alloc(sizeof(double) * n * n));
     HIPCHK(e->d_ell_col.alloc(sizeof(int32_t) * n * phm::WB_ELL_MAX)); HIPCHK(e->d_ell_val.alloc(sizeof(double) * n * phm::WB_ELL_MAX));
     HIPCHK(e->d_ell2_col.alloc(sizeof(int32_t) * n * phm::WB_ELL_MAX)); HIPCHK(e->d_ell2_val.alloc(sizeof(double) * n * phm::WB_ELL_MAX));
-    HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(to_device(e->d_pid, e->hpid));
+    HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(upload(e->d_pid, e->hpid));
     phm::WideBranchParams& p = e->pwb;
     fill_common(e, o, p);
     p.n_states = n; p.sparse = (e->variant == PHM_MCMC_SPARSE); p.count_self = p.ks; p.klong = e->nw_klong;
@@ -728,12 +692,12 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + stats_bytes(e) + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
   if (int32_t st = check_hbm(need, free_b)) return st;
-  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  HIPCHK(upload(e->d_up, s.up)); HIPCHK(upload(e->d_down, s.down));
   if (int32_t st = build_level_orders(e)) return st;
-  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_tl_slot, e->tl_slot));
+  HIPCHK(upload(e->d_nw_border, sp.order)); HIPCHK(upload(e->d_tl_slot, e->tl_slot));
   HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
   HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * n));
-  HIPCHK(to_device(e->d_tips, e->tips_host));
+  HIPCHK(upload(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes)); HIPCHK(e->d_dw1.alloc(dw_bytes));
   if (long_paths) HIPCHK(e->d_wt_mstate.alloc(ms_bytes));
@@ -797,7 +761,7 @@ int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
   const size_t need = 2 * dw_bytes + dw_bytes / 8 + pl_bytes + cnt_bytes + stats_bytes(e) + tot_bytes + acc_bytes + red_bytes + sizeof(double) * 3 * tab +
                       (size_t)tiles * (5 * (size_t)E + Nn + 8 * (size_t)n) * 64;
   if (int32_t st = check_hbm(need, free_b)) return st;
-  HIPCHK(to_device(e->d_up, s.up)); HIPCHK(to_device(e->d_down, s.down));
+  HIPCHK(upload(e->d_up, s.up)); HIPCHK(upload(e->d_down, s.down));
   if (int32_t st = build_level_orders(e)) return st;
   // A DEEP tree (deep_tree): the band pruning kernel and the node draws for n <= 32 run over subtree clusters, a launch per tier
   // instead of one per level and pass (phm_wtiles.hip); phm_debug_options.level_groups: 1 = never, 2 / 3 = always
@@ -807,15 +771,15 @@ int32_t wtiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, c
     phm::build_cluster_plan(s, phm::TILES_CL_NODES, plan);
     if (int32_t st = upload_cluster_plan(e, plan, false)) return st;
   }
-  HIPCHK(to_device(e->d_nw_border, sp.order)); HIPCHK(to_device(e->d_tl_slot, e->tl_slot));
+  HIPCHK(upload(e->d_nw_border, sp.order)); HIPCHK(upload(e->d_tl_slot, e->tl_slot));
   HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
   HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * ldt));
   HIPCHK(e->d_wt_B2.alloc(sizeof(double) * (size_t)n * ldt)); HIPCHK(e->d_Bc.alloc(sizeof(double) * n * n));
   HIPCHK(e->d_wt_B2band.alloc(sizeof(double) * (size_t)n * (2 * phm::WT_BAND_MAX + 1)));
   HIPCHK(e->d_wt_totL.alloc(tot_bytes));
   HIPCHK(e->d_wt_pair_slot.alloc(sizeof(int16_t) * (size_t)n * n)); HIPCHK(e->d_wt_slot_col.alloc(sizeof(int32_t) * phm::WT_MAX_SLOTS));
-  HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(to_device(e->d_pid, e->hpid));
-  HIPCHK(to_device(e->d_tips, e->tips_host));
+  HIPCHK(e->d_scale.alloc(sizeof(double) * n)); HIPCHK(upload(e->d_pid, e->hpid));
+  HIPCHK(upload(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes)); HIPCHK(e->d_dw1.alloc(dw_bytes));
   HIPCHK(e->d_tl_estate.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
@@ -972,7 +936,7 @@ int32_t replicas_setup(phm_engine* e, const phm_tree* trees, const phm_model* mo
   HIPCHK(e->d_row.alloc(sizeof(double) * ktab * n * n));
   HIPCHK(e->d_mask.alloc(sizeof(double) * ktab * 2 * n));
 
-  HIPCHK(to_device(e->d_tips, e->tips_host));
+  HIPCHK(upload(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)e->tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes));
   HIPCHK(e->d_cursor.alloc(sizeof(int32_t) * 2 * e->tiles));
@@ -996,11 +960,8 @@ int32_t replicas_setup(phm_engine* e, const phm_tree* trees, const phm_model* mo
     for (int j = 0; j < n_trees; ++j) {
       const phm_tree* xt = &trees[j];
       DevBuf d_off, d_maps, d_irow;
-      HIPCHK(to_device(d_irow, init_row[j]));
-      HIPCHK(d_off.alloc(sizeof(int32_t) * (E + 1)));
-      HIPCHK(d_maps.alloc(sizeof(double) * (size_t)xt->map_off[E]));
-      HIPCHK(hipMemcpy(d_off.p, xt->map_off, d_off.bytes, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(d_maps.p, xt->maps, d_maps.bytes, hipMemcpyHostToDevice));
+      HIPCHK(upload(d_irow, init_row[j]));
+      HIPCHK(upload(d_off, xt->map_off, E + 1)); HIPCHK(upload(d_maps, xt->maps, xt->map_off[E]));
       const size_t tile0 = (size_t)j * e->tpt;
       HIPCHK(phm::launch_mcmc_init(E, e->tpt, rows, e->d_down.as<phm::DownStep>() + (size_t)j * E, d_irow.as<int32_t>(), d_off.as<int32_t>(),
                                    d_maps.as<double>(), e->d_dw0.as<double>() + tile0 * rows * 64, e->d_mcount.as<uint16_t>() + tile0 * E * 64, nullptr));
@@ -1011,8 +972,8 @@ int32_t replicas_setup(phm_engine* e, const phm_tree* trees, const phm_model* mo
   }
 
   if (e->wide()) {      // the model tables go up in upload_model
-    HIPCHK(to_device(e->d_B2, e->hB2)); HIPCHK(to_device(e->d_Bc, e->hBc));
-    HIPCHK(to_device(e->d_scale, e->hscale)); HIPCHK(to_device(e->d_pid, e->hpid));
+    HIPCHK(upload(e->d_B2, e->hB2)); HIPCHK(upload(e->d_Bc, e->hBc));
+    HIPCHK(upload(e->d_scale, e->hscale)); HIPCHK(upload(e->d_pid, e->hpid));
     phm::WideParams& p = e->pw;
     fill_common(e, o, p);
     p.n_rep = n_trees > 1 ? e->S_tree : e->S;

@@ -36,10 +36,8 @@ hipError_t launch_expm_pade_mfma(int n, const double* Q, const double* t, const 
                                  int32_t* bad, double piv_min, hipStream_t stream);
 
 // PL[parent] = (P_a PL[child_a]) (.) (P_b PL[child_b]); PL is (2T-1) x n row-major, tips pre-filled one-hot;
-// rescale: every internal row divided by its sum (not in the reference; the node draws do not depend on a row's scale)
-hipError_t launch_exp_pl(int n, int n_node, int n_tips, const UpStep* up, const double* P, double* PL, int rescale,
-                         hipStream_t stream);
-// the same values, one launch per height level of the tree, a thread per node (`order`: positions of `up` grouped by height)
+// rescale: every internal row divided by its sum (not in the reference; the node draws do not depend on a row's scale).
+// One launch per height level of the tree, a wave per node (`order`: positions of `up` grouped by height)
 hipError_t launch_exp_pl_levels(int n, int n_tips, const UpStep* up, const int32_t* order, const std::vector<int32_t>& level_off,
                                 const double* P, double* PL, int rescale, hipStream_t stream);
 

@@ -2,7 +2,7 @@
 //
 //   K1  expm_eigen_kernel : P_b = |L diag(exp(d_k t_b)) R|          matexp :2964-2968, abs :2980/:3042
 //   K1' expm_pade_kernel  : P_b = expmat(Q t_b), Pade(6) + squarings arma::expmat at :3226,:3243,:3359,:3383
-//   K2e exp_pl_kernel     : pruning with P(t_b)                      makePLold :2877-2895 / makePLexp :2899-2906
+//   K2e exp_pl_nodes_kernel : pruning with P(t_b), level by level   makePLold :2877-2895 / makePLexp :2899-2906
 //   K5  exp_sample_kernel : per sample: node states top-down (sampleinternalnodesEXP :2910-2961) and the
 //                           end-point-conditioned uniformisation sampler (newunifSample :93-208);
 //                           one LANE per i.i.d. sample, topology wave-uniform, B^k e_j table in LDS.
@@ -149,38 +149,11 @@ hipError_t launch_expm_pade(int n, const double* Q, const double* t, const int32
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2e: pruning with P(t_b); the result is shared by every sample, so one thread walks the tree once.
+// K2e: pruning with P(t_b); the result is shared by every sample.  Level by level: a WAVE per node of one height level (children
+// strictly below), lane i computing row i of both matrix-vector products, each sum left to right from j = 0.  (One thread per
+// node walked 2 n^2 dependent multiply-adds: 1.2 ms per level at 61 states, 21 of the 38 ms of a sumstatEXP call on 300 tips.)
+// n <= 64.
 // ------------------------------------------------------------------------------------------------
-__global__ void exp_pl_kernel(int n, int n_node, int n_tips, const UpStep* __restrict__ up, const double* __restrict__ P,
-                              double* __restrict__ PL, int rescale) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  for (int k = 0; k < n_node; ++k) {
-    const UpStep st = up[k];
-    const int ca = st.child[0] >= 0 ? st.child[0] + n_tips : ~st.child[0];
-    const int cb = st.child[1] >= 0 ? st.child[1] + n_tips : ~st.child[1];
-    const double* Pa = P + (size_t)st.edge[0] * n * n;
-    const double* Pb = P + (size_t)st.edge[1] * n * n;
-    const double* va = PL + (size_t)ca * n;
-    const double* vb = PL + (size_t)cb * n;
-    double* dst = PL + (size_t)(st.parent + n_tips) * n;
-    for (int i = 0; i < n; ++i) {
-      double a = Pa[i * n] * va[0];
-      for (int j = 1; j < n; ++j) a += Pa[i * n + j] * va[j];
-      double b = Pb[i * n] * vb[0];
-      for (int j = 1; j < n; ++j) b += Pb[i * n + j] * vb[j];
-      dst[i] = a * b;                                                           // :2903
-    }
-    if (rescale) {      // not in the reference: row / sum(row), the sampler-equivalent rescaling of makePLrcpp_bigtree :525
-      double sum = dst[0];
-      for (int i = 1; i < n; ++i) sum += dst[i];
-      for (int i = 0; i < n; ++i) dst[i] = dst[i] / sum;
-    }
-  }
-}
-
-// the same pass level by level: a WAVE per node of one height level (children strictly below), lane i computing row i of both
-// matrix-vector products with the sums in the order above -- identical values.  (One thread per node walked 2 n^2 dependent
-// multiply-adds: 1.2 ms per level at 61 states, 21 of the 38 ms of a sumstatEXP call on 300 tips.)  n <= 64.
 __global__ __launch_bounds__(64) void exp_pl_nodes_kernel(int n, int n_tips, const UpStep* __restrict__ up, const int32_t* __restrict__ order, int begin,
                                                            int end, const double* __restrict__ P, double* __restrict__ PL, int rescale) {
   __shared__ double s_row[64];
@@ -226,12 +199,6 @@ hipError_t launch_exp_pl_levels(int n, int n_tips, const UpStep* up, const int32
     if (cnt > 0) hipLaunchKernelGGL(exp_pl_nodes_kernel, dim3(cnt), dim3(64), 0, stream, n, n_tips, up, order, level_off[l],
                                     level_off[l + 1], P, PL, rescale);
   }
-  return hipGetLastError();
-}
-
-hipError_t launch_exp_pl(int n, int n_node, int n_tips, const UpStep* up, const double* P, double* PL, int rescale,
-                         hipStream_t stream) {
-  hipLaunchKernelGGL(exp_pl_kernel, dim3(1), dim3(64), 0, stream, n, n_node, n_tips, up, P, PL, rescale);
   return hipGetLastError();
 }
 

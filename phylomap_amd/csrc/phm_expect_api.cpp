@@ -21,7 +21,7 @@ struct ExInput {
   std::vector<int32_t> obs, sq, child_row;
   std::vector<phm::UpStep> up;                          // grouped by height
   std::vector<int32_t> up_off;
-  std::vector<phm::ExDown> down;                        // grouped by the depth of the child
+  std::vector<phm::ExDown> down;                        // grouped by the depth of the parent
   std::vector<int32_t> down_off;
   std::vector<int64_t> w_off;
   std::vector<double> w;
@@ -63,28 +63,15 @@ int32_t ex_validate(const phm_tree* x, int32_t n, const double* Q, const double*
   in.cols = n + n * (n - 1);
   in.per_site = o.tips_per_replica != 0;
   in.states = x->states;
-  for (int b = 0; b < in.E; ++b)
-    if (!std::isfinite(x->edge_length[b]) || x->edge_length[b] < 0.0)
-      return fail(PHM_ERR_BAD_INPUT, "edge.length must be finite and non-negative (edge row " + std::to_string(b + 1) + ")");
+  int32_t st = check_edge_lengths(x);
+  if (st) return st;
   in.edge_length.assign(x->edge_length, x->edge_length + in.E);
-  double qmax = 0.0;
-  for (int i = 0; i < n * n; ++i) {
-    if (!std::isfinite(Q[i])) return fail(PHM_ERR_BAD_INPUT, "Q must be finite");
-    qmax = std::max(qmax, std::fabs(Q[i]));
-  }
-  cm_to_rm(Q, n, in.Qr);
-  in.qoff.assign((size_t)n * n, 0.0);
+  st = check_generator(Q, n, in.Qr);
+  if (st) return st;
+  in.qoff = in.Qr;
   in.mu = 0.0;
   for (int i = 0; i < n; ++i) {
-    double row = 0.0;
-    for (int j = 0; j < n; ++j) {
-      const double q = in.Qr[(size_t)i * n + j];
-      row += q;
-      if (j == i) continue;
-      if (q < 0.0) return fail(PHM_ERR_BAD_INPUT, "Q: off-diagonal entries must be >= 0 (row " + std::to_string(i + 1) + ")");
-      in.qoff[(size_t)i * n + j] = q;
-    }
-    if (std::fabs(row) > 1e-12 * qmax) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " does not sum to 0");
+    in.qoff[(size_t)i * n + i] = 0.0;
     in.mu = std::max(in.mu, -in.Qr[(size_t)i * n + i]);
   }
   if (!(in.mu > 0.0)) return fail(PHM_ERR_BAD_INPUT, "Q: no state is left at a positive rate (max(-q_ii) must be > 0)");
@@ -92,18 +79,12 @@ int32_t ex_validate(const phm_tree* x, int32_t n, const double* Q, const double*
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) in.B[(size_t)i * n + j] = (i == j ? 1.0 : 0.0) + in.Qr[(size_t)i * n + j] / in.mu;
   double psum = 0.0;
-  for (int i = 0; i < n; ++i) {
-    if (!(pid[i] >= 0.0) || !std::isfinite(pid[i])) return fail(PHM_ERR_ZERO_PROB, "pid must be finite and non-negative");
-    psum += pid[i];
-  }
-  if (!(psum > 0.0)) return fail(PHM_ERR_ZERO_PROB, "pid sums to zero");
+  st = check_root_prior(pid, n, psum);
+  if (st) return st;
   in.pid.resize(n);
   for (int i = 0; i < n; ++i) in.pid[i] = pid[i] / psum;
-  in.obs.resize(n);
-  for (int i = 0; i < n; ++i) {
-    in.obs[i] = observe ? observe[i] : i + 1;
-    if (in.obs[i] < 1 || in.obs[i] > n) return fail(PHM_ERR_BAD_INPUT, "observe: values must be in 1..n");
-  }
+  st = check_observe(observe, n, in.obs);
+  if (st) return st;
   const int64_t n_states_in = (int64_t)(in.per_site ? in.S : 1) * in.T;
   for (int64_t k = 0; k < n_states_in; ++k)
     if (in.states[k] < 0 || in.states[k] > n) return fail(PHM_ERR_BAD_INPUT, "x$states must be in 0..n (0: missing)");
@@ -131,42 +112,22 @@ int ex_squarings(const double* Q_rm, int n, double t) {
 void ex_prepare(ExInput& in) {
   const phm::Schedule& s = in.sched;
   const int T = in.T;
-  std::vector<int32_t> height(s.n_node, 0), up_of(s.n_node, -1);
-  std::vector<std::vector<int32_t>> by_h;
-  for (int k = 0; k < s.n_node; ++k) {
-    const phm::UpStep& u = s.up[k];
-    int h = 0;
-    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) h = std::max(h, height[u.child[c]] + 1);
-    height[u.parent] = h;
-    up_of[u.parent] = k;
-    if ((int)by_h.size() <= h) by_h.resize(h + 1);
-    by_h[h].push_back(k);
-  }
-  in.up_off.assign(1, 0);
-  for (auto& v : by_h) {
-    for (int k : v) in.up.push_back(s.up[k]);
-    in.up_off.push_back((int32_t)in.up.size());
-  }
+  std::vector<int32_t> order, up_of(s.n_node, -1);
+  phm::height_levels(s.up, order, in.up_off);
+  for (int32_t k : order) in.up.push_back(s.up[k]);
+  for (int k = 0; k < s.n_node; ++k) up_of[s.up[k].parent] = k;
   auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
-  std::vector<int32_t> depth(s.n_node, 0);
-  std::vector<std::vector<phm::ExDown>> by_d;
+  phm::depth_levels(s, order, in.down_off);
   in.child_row.assign(in.E, 0);
-  for (const phm::DownStep& d : s.down) {
+  for (int32_t k : order) {
+    const phm::DownStep& d = s.down[k];
     const phm::UpStep& u = s.up[up_of[d.parent]];
     const int side = u.edge[0] == d.edge ? 1 : 0;                // the sibling branch
-    const int dd = depth[d.parent] + 1;
-    if (d.child >= 0) depth[d.child] = dd;
     phm::ExDown x = {};
     x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
     x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
-    if ((int)by_d.size() <= dd) by_d.resize(dd + 1);
-    by_d[dd].push_back(x);
+    in.down.push_back(x);
     in.child_row[d.edge] = x.child;
-  }
-  in.down_off.assign(1, 0);
-  for (auto& v : by_d) {
-    in.down.insert(in.down.end(), v.begin(), v.end());
-    in.down_off.push_back((int32_t)in.down.size());
   }
   in.w_off.assign(1, 0);
   in.sq.resize(in.E);
@@ -178,18 +139,6 @@ void ex_prepare(ExInput& in) {
     in.w_off.push_back((int64_t)in.w.size());
     in.sq[b] = ex_squarings(in.Qr.data(), in.n, in.edge_length[b]);
   }
-}
-
-struct Events {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-template <typename T>
-hipError_t upload(DevBuf& d, const std::vector<T>& h) {
-  hipError_t e = d.alloc(sizeof(T) * h.size());
-  if (e == hipSuccess && !h.empty()) e = hipMemcpy(d.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
-  return e;
 }
 
 // Sites [first, first + count) of the call on one device; outputs point at the caller's full arrays (S sites per column).
@@ -206,17 +155,17 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
   HIPCHK(upload(dB, in.B)); HIPCHK(upload(dq, in.qoff)); HIPCHK(upload(dpid, in.pid)); HIPCHK(upload(dobs, in.obs));
   HIPCHK(upload(dup, in.up)); HIPCHK(upload(ddown, in.down)); HIPCHK(upload(dchild, in.child_row));
   HIPCHK(upload(dwoff, in.w_off)); HIPCHK(upload(dw, in.w));
-  Events ev;
-  for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreate(&x));
-  double kernel_ms = 0.0;
-  HIPCHK(hipEventRecord(ev.e[0], nullptr));
+  KernelTimer tm;
+  double kernel_ms = 0.0, ms = 0.0;
+  HIPCHK(tm.start());
   HIPCHK(phm::launch_expm_pade(n, dQ.as<double>(), dt.as<double>(), dsq.as<int32_t>(), E, dwork.as<double>(), dP.as<double>(),
                                derr.as<uint32_t>(), nullptr));
-  HIPCHK(hipEventRecord(ev.e[1], nullptr));
+  HIPCHK(tm.stop());
   uint32_t derrh = 0;
   HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
   if (derrh) return fail(PHM_ERR_BAD_INPUT, "phm_expected_stats: singular Pade denominator in expm(Q t_b)");
-  { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1])); kernel_ms += ms; }
+  HIPCHK(tm.elapsed(ms));
+  kernel_ms += ms;
   dwork.reset();
 
   // sites per chunk: what fits in half the free HBM next to the branch-stage scratch
@@ -255,7 +204,7 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
     pp.n = n; pp.n_tips = T; pp.Sp = Sp;
     pp.P = dP.as<double>(); pp.L = dL.as<double>(); pp.sL = dsL.as<double>(); pp.O = dO.as<double>(); pp.sO = dsO.as<double>();
     pp.F = dF.as<double>(); pp.sF = dsF.as<double>(); pp.ll = dll.as<double>(); pp.lam = dlam.as<double>();
-    HIPCHK(hipEventRecord(ev.e[0], nullptr));
+    HIPCHK(tm.start());
     HIPCHK(phm::launch_ex_tips(pp, dtips.as<uint8_t>(), dobs.as<int32_t>(), nullptr));
     for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
       HIPCHK(phm::launch_ex_up(pp, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
@@ -263,13 +212,14 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
     for (size_t l = 0; l + 1 < in.down_off.size(); ++l)
       HIPCHK(phm::launch_ex_down(pp, ddown.as<phm::ExDown>() + in.down_off[l], in.down_off[l + 1] - in.down_off[l], nullptr));
     if (node_post) HIPCHK(phm::launch_ex_post(pp, NT, dpost.as<double>(), nullptr));
-    HIPCHK(hipEventRecord(ev.e[1], nullptr));
+    HIPCHK(tm.stop());
     HIPCHK(hipMemcpy(ll_h.data(), dll.p, sizeof(double) * Sc, hipMemcpyDeviceToHost));
     for (int64_t k = 0; k < Sc; ++k)
       if (!std::isfinite(ll_h[k]))
         return fail(PHM_ERR_ZERO_PROB, "phm_expected_stats: site " + std::to_string(site0 + k + 1) + " has probability 0 under Q (its tips are impossible)");
     std::memcpy(loglik + site0, ll_h.data(), sizeof(double) * Sc);
-    { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1])); kernel_ms += ms; }
+    HIPCHK(tm.elapsed(ms));
+    kernel_ms += ms;
     if (node_post)                                                 // [state][row][Sp] -> site + S (row + NT state)
       HIPCHK(hipMemcpy2D(node_post + site0, sizeof(double) * S, dpost.p, sizeof(double) * Sp, sizeof(double) * Sc, (size_t)NT * n,
                          hipMemcpyDeviceToHost));
@@ -280,25 +230,21 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
     bp.root = T + in.sched.root;
     bp.out = dout.as<double>();
     HIPCHK(hipMemset(dtot.p, 0, sizeof(double) * cols * Sp));
-    float branch_ms = 0.f;
     for (int e0 = 0; e0 < E; e0 += ne_max) {
       const int ne = std::min(ne_max, E - e0);
       bp.e0 = e0; bp.n_out_edges = ne;
-      HIPCHK(hipEventRecord(ev.e[2], nullptr));
+      HIPCHK(tm.start());
       HIPCHK(phm::launch_ex_branch(bp, ne, nullptr));
       HIPCHK(phm::launch_ex_reduce(dout.as<double>(), cols, ne, Sp, dtot.as<double>(), nullptr));
-      HIPCHK(hipEventRecord(ev.e[3], nullptr));
+      HIPCHK(tm.stop());
       if (branch_stats)                                            // [col][e][Sp] -> site + S (edge + E col)
         for (int col = 0; col < cols; ++col)
           HIPCHK(hipMemcpy2D(branch_stats + site0 + S * ((size_t)e0 + (size_t)E * col), sizeof(double) * S,
                              dout.as<double>() + (size_t)col * ne * Sp, sizeof(double) * Sp, sizeof(double) * Sc, ne,
                              hipMemcpyDeviceToHost));
-      HIPCHK(hipEventSynchronize(ev.e[3]));
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev.e[2], ev.e[3]));
-      branch_ms += ms;
+      HIPCHK(tm.elapsed(ms));
+      kernel_ms += ms;
     }
-    kernel_ms += branch_ms;
     HIPCHK(hipMemcpy2D(stats + site0, sizeof(double) * S, dtot.p, sizeof(double) * Sp, sizeof(double) * Sc, cols,
                        hipMemcpyDeviceToHost));
   }

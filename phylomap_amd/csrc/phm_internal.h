@@ -1,6 +1,6 @@
 // phm_internal.h -- shared by the translation units behind the C-ABI (phm_engine.cpp, phm_drivers.cpp, phm_expm_api.cpp,
-// phm_sim_api.cpp): error reporting, options, device buffers, the engine object, the shard runner.  Not installed;
-// include/phylomap_hip.h is the public interface.
+// phm_sim_api.cpp, phm_expect_api.cpp): error reporting, options, device buffers and timing, input checks, the engine object, the
+// shard runner.  Not installed; include/phylomap_hip.h is the public interface.
 #pragma once
 
 #include "../../include/phylomap_hip.h"
@@ -60,6 +60,40 @@ struct DevBuf {
     return e;
   }
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A device buffer of exactly `count` elements, filled from the host (count 0: an empty buffer, nothing copied)
+template <typename T>
+hipError_t upload(DevBuf& d, const T* h, size_t count) {
+  hipError_t e = d.alloc(sizeof(T) * count);
+  if (e == hipSuccess && count) e = hipMemcpy(d.p, h, sizeof(T) * count, hipMemcpyHostToDevice);
+  return e;
+}
+template <typename T>
+hipError_t upload(DevBuf& d, const std::vector<T>& h) { return upload(d, h.data(), h.size()); }
+
+// The time between two points of the null stream: the launches a one-shot entry point reports (phm_last_kernel_ms, kernel_ms
+// of the expm calls).  An event call is a HIP call like any other: the caller checks each one, and one that fails fails the call.
+struct KernelTimer {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  KernelTimer() = default;
+  KernelTimer(const KernelTimer&) = delete;
+  KernelTimer& operator=(const KernelTimer&) = delete;
+  ~KernelTimer() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+  hipError_t start() {
+    for (hipEvent_t& x : ev)
+      if (!x) { const hipError_t e = hipEventCreate(&x); if (e != hipSuccess) return e; }
+    return hipEventRecord(ev[0], nullptr);
+  }
+  hipError_t stop() { return hipEventRecord(ev[1], nullptr); }
+  // waits for the stop event; ms: start .. stop
+  hipError_t elapsed(double& ms) {
+    float f = 0.f;
+    hipError_t e = hipEventSynchronize(ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&f, ev[0], ev[1]);
+    if (e == hipSuccess) ms = f;
+    return e;
+  }
 };
 
 // page-locked host staging (async copies of a few KB between sweeps: a pageable hipMemcpy costs a synchronous ~15-30 us each)
@@ -203,6 +237,55 @@ inline int32_t validate_tree_paths(const phm_tree* x, int n, int n_tip_vectors) 
       if (x->mapnames[i] < 1 || x->mapnames[i] > n) return fail(PHM_ERR_BAD_INPUT, "x$mapnames must be in 1..n");
       if (!std::isfinite(x->maps[i]) || x->maps[i] < 0.0) return fail(PHM_ERR_BAD_INPUT, "x$maps must be finite and non-negative");
     }
+  }
+  return PHM_OK;
+}
+
+// ---- input checks of the one-shot entry points (phm_sim_api.cpp, phm_expect_api.cpp, phm_expm_api.cpp) ----
+inline int32_t check_edge_lengths(const phm_tree* x) {
+  for (int b = 0; b < x->n_edge; ++b)
+    if (!std::isfinite(x->edge_length[b]) || x->edge_length[b] < 0.0)
+      return fail(PHM_ERR_BAD_INPUT, "edge.length must be finite and non-negative (edge row " + std::to_string(b + 1) + ")");
+  return PHM_OK;
+}
+
+// Q (column-major) a generator: finite, off-diagonal entries >= 0, rows summing to 0 within 1e-12 max|q|; Qr: Q row-major
+inline int32_t check_generator(const double* Q, int n, std::vector<double>& Qr) {
+  double qmax = 0.0;
+  for (int i = 0; i < n * n; ++i) {
+    if (!std::isfinite(Q[i])) return fail(PHM_ERR_BAD_INPUT, "Q must be finite");
+    qmax = std::max(qmax, std::fabs(Q[i]));
+  }
+  cm_to_rm(Q, n, Qr);
+  for (int i = 0; i < n; ++i) {
+    double row = 0.0;
+    for (int j = 0; j < n; ++j) {
+      const double q = Qr[(size_t)i * n + j];
+      row += q;
+      if (j != i && q < 0.0) return fail(PHM_ERR_BAD_INPUT, "Q: off-diagonal entries must be >= 0 (row " + std::to_string(i + 1) + ")");
+    }
+    if (std::fabs(row) > 1e-12 * qmax) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " does not sum to 0");
+  }
+  return PHM_OK;
+}
+
+// the root prior: finite, non-negative, a positive sum (psum)
+inline int32_t check_root_prior(const double* pid, int n, double& psum) {
+  psum = 0.0;
+  for (int i = 0; i < n; ++i) {
+    if (!(pid[i] >= 0.0) || !std::isfinite(pid[i])) return fail(PHM_ERR_ZERO_PROB, "pid must be finite and non-negative");
+    psum += pid[i];
+  }
+  if (!(psum > 0.0)) return fail(PHM_ERR_ZERO_PROB, "pid sums to zero");
+  return PHM_OK;
+}
+
+// observe (NULL: the identity): obs[i], the 1-based state true state i is seen as at a tip
+inline int32_t check_observe(const int32_t* observe, int n, std::vector<int32_t>& obs) {
+  obs.resize(n);
+  for (int i = 0; i < n; ++i) {
+    obs[i] = observe ? observe[i] : i + 1;
+    if (obs[i] < 1 || obs[i] > n) return fail(PHM_ERR_BAD_INPUT, "observe: values must be in 1..n");
   }
   return PHM_OK;
 }

@@ -95,6 +95,58 @@ bool build_schedule(int32_t T, int32_t n_node, int32_t E, const int32_t* edge, S
   return true;
 }
 
+std::vector<int32_t> node_heights(const std::vector<UpStep>& up) {
+  std::vector<int32_t> height(up.size(), 0);
+  for (const UpStep& u : up) {
+    int h = 0;
+    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) h = std::max(h, height[u.child[c]] + 1);
+    height[u.parent] = h;
+  }
+  return height;
+}
+
+// positions i with level[i] >= 0 grouped by level, stable
+static void group_by_level(const std::vector<int32_t>& level, std::vector<int32_t>& order, std::vector<int32_t>& off) {
+  int levels = 0;
+  for (int32_t l : level) levels = std::max(levels, l + 1);
+  off.assign(levels + 1, 0);
+  for (int32_t l : level) if (l >= 0) off[l + 1]++;
+  for (int l = 0; l < levels; ++l) off[l + 1] += off[l];
+  order.resize(off[levels]);
+  std::vector<int32_t> pos(off.begin(), off.end() - 1);
+  for (size_t i = 0; i < level.size(); ++i) if (level[i] >= 0) order[pos[level[i]]++] = (int32_t)i;
+}
+
+void height_levels(const std::vector<UpStep>& up, std::vector<int32_t>& order, std::vector<int32_t>& off) {
+  const std::vector<int32_t> height = node_heights(up);
+  std::vector<int32_t> level(up.size());
+  for (size_t k = 0; k < up.size(); ++k) level[k] = height[up[k].parent];
+  group_by_level(level, order, off);
+}
+
+// internal_only leaves no level empty: the parent of an edge to an internal node is itself reached one level earlier
+void depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<int32_t>& off, bool internal_only) {
+  std::vector<int32_t> depth(s.n_node, 0), level(s.down.size());
+  for (size_t k = 0; k < s.down.size(); ++k) {      // parents before children
+    const DownStep& d = s.down[k];
+    level[k] = internal_only && d.child < 0 ? -1 : depth[d.parent];
+    if (d.child >= 0) depth[d.child] = depth[d.parent] + 1;
+  }
+  group_by_level(level, order, off);
+}
+
+// heights, parents and positions in s.up of the internal nodes
+static void node_links(const Schedule& s, std::vector<int32_t>& height, std::vector<int32_t>& parent, std::vector<int32_t>& step_of) {
+  height = node_heights(s.up);
+  parent.assign(s.n_node, -1);
+  step_of.assign(s.n_node, -1);
+  for (int k = 0; k < s.n_node; ++k) {
+    const UpStep& u = s.up[k];
+    step_of[u.parent] = k;
+    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) parent[u.child[c]] = u.parent;
+  }
+}
+
 bool check_reference_orders(const Schedule& s, const int32_t* edge, const int32_t* nen,
                             const int32_t* nodelist, int32_t root, std::string& err) {
   const int32_t T = s.n_tips, E = s.n_edge, nn = 2 * T - 1;
@@ -200,16 +252,8 @@ int32_t poisson_capacity(double lambda, double tail) {
 void build_cluster_plan(const Schedule& s, int32_t max_nodes, ClusterPlan& plan) {
   const int Nn = s.n_node;
   plan = ClusterPlan();
-  // s.up lists children before parents: one pass gives heights and the parent of every internal node
-  std::vector<int32_t> height(Nn, 0), parent(Nn, -1), step_of(Nn, -1);
-  for (int k = 0; k < Nn; ++k) {
-    const UpStep& u = s.up[k];
-    step_of[u.parent] = k;
-    int h = 0;
-    for (int c = 0; c < 2; ++c)
-      if (u.child[c] >= 0) { h = std::max(h, height[u.child[c]] + 1); parent[u.child[c]] = u.parent; }
-    height[u.parent] = h;
-  }
+  std::vector<int32_t> height, parent, step_of;
+  node_links(s, height, parent, step_of);
   std::vector<int32_t> cluster_of(Nn, -1), rsize(Nn, 0);
   std::vector<std::vector<int32_t>> members;             // per cluster: internal indices
   std::vector<int32_t> croot;                            // per cluster: its root node
@@ -279,18 +323,9 @@ void build_band_plan(const Schedule& s, int32_t band, ClusterPlan& plan) {
   const int Nn = s.n_node;
   plan = ClusterPlan();
   if (band < 1) band = 1;
-  std::vector<int32_t> height(Nn, 0), parent(Nn, -1), step_of(Nn, -1);
-  int max_h = 0;
-  for (int k = 0; k < Nn; ++k) {
-    const UpStep& u = s.up[k];
-    step_of[u.parent] = k;
-    int h = 0;
-    for (int c = 0; c < 2; ++c)
-      if (u.child[c] >= 0) { h = std::max(h, height[u.child[c]] + 1); parent[u.child[c]] = u.parent; }
-    height[u.parent] = h;
-    max_h = std::max(max_h, h);
-  }
-  const int n_tiers = max_h / band + 1;
+  std::vector<int32_t> height, parent, step_of;
+  node_links(s, height, parent, step_of);
+  const int n_tiers = *std::max_element(height.begin(), height.end()) / band + 1;
   // parents before children: a node joins its parent's cluster when both lie in the same band, else it starts a cluster
   std::vector<int32_t> cluster_of(Nn, -1);
   std::vector<std::vector<int32_t>> members;

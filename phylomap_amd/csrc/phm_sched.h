@@ -66,6 +66,15 @@ struct Schedule {
 bool build_schedule(int32_t n_tips, int32_t n_node, int32_t n_edge, const int32_t* edge, Schedule& s,
                     std::string& err);
 
+// Level orders of the tree passes, stable inside a level; off: the level boundaries in order (levels + 1 entries).
+// Heights of the internal nodes of `up` (children before parents; internal indices 0 .. up.size() - 1): children strictly below
+// their parent.
+std::vector<int32_t> node_heights(const std::vector<UpStep>& up);
+// positions in `up` grouped by the height of their node
+void height_levels(const std::vector<UpStep>& up, std::vector<int32_t>& order, std::vector<int32_t>& off);
+// positions in s.down grouped by the depth of their parent node (root: 0); internal_only: the edges to an internal node alone
+void depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<int32_t>& off, bool internal_only = false);
+
 // Checks that the caller's nen / nodelist / root (R/sumstatMCMC.R:1-18) describe this tree:
 // nen a permutation with sibling edges adjacent and children before parents, nodelist parents before
 // children, root the node that is nobody's child.

@@ -25,46 +25,29 @@ int32_t sim_validate(const phm_tree* x, int32_t n, const double* Q, const double
   std::string serr;
   if (!phm::build_schedule(x->n_tips, x->n_node, x->n_edge, x->edge, in.sched, serr)) return fail(PHM_ERR_BAD_INPUT, "tree: " + serr);
   in.n = n; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge;
-  for (int b = 0; b < in.E; ++b)
-    if (!std::isfinite(x->edge_length[b]) || x->edge_length[b] < 0.0)
-      return fail(PHM_ERR_BAD_INPUT, "edge.length must be finite and non-negative (edge row " + std::to_string(b + 1) + ")");
+  int32_t st = check_edge_lengths(x);
+  if (st) return st;
   in.edge_length.assign(x->edge_length, x->edge_length + in.E);
-  double qmax = 0.0;
-  for (int i = 0; i < n * n; ++i) {
-    if (!std::isfinite(Q[i])) return fail(PHM_ERR_BAD_INPUT, "Q must be finite");
-    qmax = std::max(qmax, std::fabs(Q[i]));
-  }
-  in.qoff.assign((size_t)n * n, 0.0);
+  st = check_generator(Q, n, in.qoff);
+  if (st) return st;
   in.inv_rate.assign(n, 0.0);
   for (int i = 0; i < n; ++i) {
-    double row = 0.0, off = 0.0;
-    for (int j = 0; j < n; ++j) {
-      const double q = Q[i + (size_t)j * n];                        // column-major
-      row += q;
-      if (j == i) continue;
-      if (q < 0.0) return fail(PHM_ERR_BAD_INPUT, "Q: off-diagonal entries must be >= 0 (row " + std::to_string(i + 1) + ")");
-      in.qoff[(size_t)i * n + j] = q;
-      off += q;
-    }
-    if (std::fabs(row) > 1e-12 * qmax) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " does not sum to 0");
-    const double qii = Q[i + (size_t)i * n];
+    double* row = &in.qoff[(size_t)i * n];
+    const double qii = row[i];
+    row[i] = 0.0;
+    double off = 0.0;
+    for (int j = 0; j < n; ++j) off += row[j];
     if (qii < 0.0 && !(off > 0.0)) return fail(PHM_ERR_BAD_INPUT, "Q: row " + std::to_string(i + 1) + " leaves its state but has no target");
     in.inv_rate[i] = qii < 0.0 ? 1.0 / (-qii) : 0.0;                  // 0: absorbing (q_ss = 0)
   }
   double psum = 0.0;
-  for (int i = 0; i < n; ++i) {
-    if (!(pid[i] >= 0.0) || !std::isfinite(pid[i])) return fail(PHM_ERR_ZERO_PROB, "pid must be finite and non-negative");
-    psum += pid[i];
-  }
-  if (!(psum > 0.0)) return fail(PHM_ERR_ZERO_PROB, "pid sums to zero");
+  st = check_root_prior(pid, n, psum);
+  if (st) return st;
   in.pid.assign(pid, pid + n);
-  in.tip_map.resize(n);
+  st = check_observe(observe, n, in.tip_map);
+  if (st) return st;
   in.node_map.resize(n);
-  for (int i = 0; i < n; ++i) {
-    in.node_map[i] = i + 1;
-    in.tip_map[i] = observe ? observe[i] : i + 1;
-    if (in.tip_map[i] < 1 || in.tip_map[i] > n) return fail(PHM_ERR_BAD_INPUT, "observe: values must be in 1..n");
-  }
+  for (int i = 0; i < n; ++i) in.node_map[i] = i + 1;
   return PHM_OK;
 }
 
@@ -76,22 +59,14 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
   if (st) return st;
   const int n = in.n, T = in.T, E = in.E, rows = in.T + in.Nn, cols = n + n * n + 1;
   const int pad = (R + 63) / 64 * 64;
-  DevBuf ddown, dq, dinv, dpid, dlen, dns, dstats, derr, dmap, dout;
-  HIPCHK(ddown.alloc(sizeof(phm::DownStep) * E)); HIPCHK(dq.alloc(sizeof(double) * n * n)); HIPCHK(dinv.alloc(sizeof(double) * n));
-  HIPCHK(dpid.alloc(sizeof(double) * n)); HIPCHK(dlen.alloc(sizeof(double) * E)); HIPCHK(dns.alloc((size_t)rows * pad));
-  HIPCHK(dstats.alloc(sizeof(double) * cols * (size_t)pad)); HIPCHK(derr.alloc(2 * sizeof(uint32_t)));
-  HIPCHK(dmap.alloc(sizeof(int32_t) * 2 * n));
-  HIPCHK(dout.alloc(sizeof(int32_t) * (size_t)R * (nodes ? rows : T)));
   std::vector<int32_t> maps(in.tip_map);
   maps.insert(maps.end(), in.node_map.begin(), in.node_map.end());
   const uint32_t err_init[2] = {0u, 0xFFFFFFFFu};
-  HIPCHK(hipMemcpy(ddown.p, in.sched.down.data(), ddown.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dq.p, in.qoff.data(), dq.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dinv.p, in.inv_rate.data(), dinv.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dpid.p, in.pid.data(), dpid.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dlen.p, in.edge_length.data(), dlen.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(derr.p, err_init, derr.bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dmap.p, maps.data(), dmap.bytes, hipMemcpyHostToDevice));
+  DevBuf ddown, dq, dinv, dpid, dlen, dns, dstats, derr, dmap, dout;
+  HIPCHK(upload(ddown, in.sched.down)); HIPCHK(upload(dq, in.qoff)); HIPCHK(upload(dinv, in.inv_rate)); HIPCHK(upload(dpid, in.pid));
+  HIPCHK(upload(dlen, in.edge_length)); HIPCHK(upload(derr, err_init, 2)); HIPCHK(upload(dmap, maps));
+  HIPCHK(dns.alloc((size_t)rows * pad)); HIPCHK(dstats.alloc(sizeof(double) * cols * (size_t)pad));
+  HIPCHK(dout.alloc(sizeof(int32_t) * (size_t)R * (nodes ? rows : T)));
   HIPCHK(hipMemset(dstats.p, 0, dstats.bytes));
   phm::SimParams p;
   p.n_states = n; p.n_tips = T; p.n_node = in.Nn; p.n_edge = E; p.root = in.sched.root;
@@ -105,18 +80,12 @@ int32_t sim_one_device(const SimInput& in, const phm_options& o, int32_t device,
     st = msh.setup(*mh, first, R, pad, p.maps);
     if (st) return st;
   }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIPCHK(hipEventCreate(&ev0));
-  if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail(PHM_ERR_NO_DEVICE, "hipEventCreate failed"); }
-  hipError_t le = hipEventRecord(ev0, nullptr);
-  if (le == hipSuccess) le = phm::launch_simulate(p, nullptr, maps_mode);
-  if (le == hipSuccess && mh) le = msh.after_kernel(*mh, pad, nullptr);      // sizing: counts -> offsets
-  if (le == hipSuccess) le = hipEventRecord(ev1, nullptr);
-  if (le == hipSuccess) le = hipEventSynchronize(ev1);
-  float ms = 0.f;
-  if (le == hipSuccess && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_phm_last_kernel_ms = ms;
-  (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-  HIPCHK(le);
+  KernelTimer tm;
+  HIPCHK(tm.start());
+  HIPCHK(phm::launch_simulate(p, nullptr, maps_mode));
+  if (mh) HIPCHK(msh.after_kernel(*mh, pad, nullptr));      // sizing: counts -> offsets
+  HIPCHK(tm.stop());
+  HIPCHK(tm.elapsed(g_phm_last_kernel_ms));
   uint32_t errh[2];
   HIPCHK(hipMemcpy(errh, derr.p, sizeof errh, hipMemcpyDeviceToHost));
   if (errh[0] & phm::DERR_CAPACITY)

@@ -199,6 +199,12 @@ def test_input_validation_happens_before_the_device():
     zb["edge"][2, 0] = zb["edge"][0, 0]                     # three children on one node
     with pytest.raises((_lib.PhmError, ValueError)):
         api.sumstatMCMC(zb, Q, pid, Om, 3)
+    zb = dict(z, **{"edge.length": np.array(z["edge.length"], dtype=np.float64)})
+    zb["edge.length"][3] = -1.0
+    for maps in (False, True):                              # sumstatEXP: the input before the shard plan (device 7)
+        with pytest.raises(_lib.PhmError) as e:
+            api.sumstatEXP(zb, Q, pid, 64, maps=maps, devices=[0, 7])
+        assert e.value.status == 1 and "edge row 4" in str(e.value)
 
 
 def test_multi_tree_driver_refuses_a_tree_without_paths():
