@@ -340,6 +340,27 @@ int32_t phm_maketreelistEXP_maps(const phm_tree* x, int32_t n, const double* Q, 
                                  const double* d, const phm_options* opt, double* out,
                                  int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
 
+/* ---- stochastic maps of the MCMC samplers ----
+ * The fixed-Q one-shot drivers (variant PHM_MCMC, PHM_MCMC_BIGTREE, PHM_MCMC_SPARSE, PHM_MCMC_KS or PHM_MCMC_BF; anything else is
+ * PHM_ERR_UNSUPPORTED) that also return the chains' sampled histories at the iterations map_iters: J >= 1 strictly increasing
+ * 0-based values below N, or NULL with n_map_iters = 0 for every iteration (J = N); S * J must fit in int32 (S = n_replicas).
+ * History h = s * J + j is chain s at iteration map_iters[j]; row k = h * E + b its map on edge row b, in the format and with the
+ * two-phase contract of the section 14 entry points above (map_off holds S*J*E + 1 offsets).  The map of a row is the path that
+ * iteration's branch step makes of the branch after its interior states are resampled and equal neighbours merged, before the
+ * virtual jumps are re-inserted: the first segment has the parent's state (the child's throughout on a branch of one old segment:
+ * updatenodestates' "child wins"), the last the child's (a tip's observed state; with PHM_MCMC_KS the hidden state sampled that
+ * iteration), consecutive segments differ, each dwell is the sum of the old segments it merges, added left to right.  The
+ * transitions between consecutive segments of history (s, j), summed over its rows, are the off-diagonal counts of row
+ * map_iters[j] of chain s in `out`.  At most 65 535 segments per row.  mapping: PHM_MAP_AUTO or PHM_MAP_TILES (the (tile, branch)
+ * kernels run either way), anything else is PHM_ERR_UNSUPPORTED; every other argument and option means what it means for the
+ * plain driver of the variant (sites, reduce, cap_tail, no_recovery, devices).  `out` is bit-identical to the plain driver's with
+ * mapping = PHM_MAP_TILES; its counts equal the plain driver's under any mapping.  Every argument check runs before any device call.
+ * phm_last_kernel_ms: the device time of the sweeps, the replays included. */
+int32_t phm_maketreelistMCMC_maps(int32_t variant, const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
+                                  const double* B, double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
+                                  const int32_t* map_iters, int32_t n_map_iters, const phm_options* opt, double* out,
+                                  int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
+
 /* ---- exact conditional expectations given the tips ----
  * For a fixed Q, per site (one tip vector): E[dwell_i | tips], E[N_ij | tips] summed over the tree and per branch, log p(tips | Q)
  * and P(state of node k | tips), by an up (pruning) pass, a down (outside) pass and one uniformization integral per branch

@@ -25,7 +25,7 @@ EXPORTS = [
     "phm_engine_time_pruning", "phm_tree_orders",
     "phm_engine_create_multi", "phm_maketreelistMCMCmt", "phm_maketreelistMCMCksmt", "phm_engine_phase_ms",
     "phm_last_kernel_ms", "phm_set_debug_options", "phm_sparse_kernel_source", "phm_simulate_histories",
-    "phm_expected_stats", "phm_simulate_histories_maps", "phm_maketreelistEXP_maps",
+    "phm_expected_stats", "phm_simulate_histories_maps", "phm_maketreelistEXP_maps", "phm_maketreelistMCMC_maps",
 ]
 
 
@@ -151,6 +151,8 @@ def load():
         L.phm_simulate_histories_maps.argtypes = L.phm_simulate_histories.argtypes + [
             C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.phm_maketreelistEXP_maps.argtypes = L.phm_maketreelistEXP.argtypes + [
+            C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.phm_maketreelistMCMC_maps.argtypes = [C.c_int32] + mc[:10] + [C.POINTER(C.c_int32), C.c_int32] + mc[10:] + [
             C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.phm_expected_stats.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_double),

@@ -20,10 +20,17 @@ from . import _lib
 from .treeorder import makenodelist, myreorder, pruningwiseedgeorder  # noqa: F401  (Python twins of phm_tree_orders)
 
 
-def _mcmc(fn_name, z, Q, pid, Omega, N, sites=None, **opt):
+_MCMC_VARIANT = {"phm_maketreelistMCMC": _lib.PHM_MCMC, "phm_maketreelistMCMC_bigtree": _lib.PHM_MCMC_BIGTREE,
+                 "phm_SPARSEmaketreelistMCMC": _lib.PHM_MCMC_SPARSE, "phm_maketreelistMCMCks_sweep": _lib.PHM_MCMC_KS,
+                 "phm_maketreelistMCMCbf_sweep": _lib.PHM_MCMC_BF}
+
+
+def _mcmc(fn_name, z, Q, pid, Omega, N, sites=None, maps=False, map_iters=None, **opt):
     """``sites``: optional S x n_tips matrix of 1-based tip states -- S sites of an alignment on the same tree, one chain each
     (``n_replicas = S``, ``tips_per_replica``); the initial paths of ``z`` must be compatible with every site (e.g. internal
-    segments in a state from which every tip state is reachable)."""
+    segments in a state from which every tip state is reachable).  ``maps=True``: returns ``(out, maps)`` with the chains'
+    histories at the 0-based iterations ``map_iters`` (default: every iteration) as a ``maps.Maps`` -- history ``s * J + j`` is
+    chain s at ``map_iters[j]`` (phm_maketreelistMCMC_maps: a sizing call, then a filling call; the (tile, branch) mapping)."""
     L = _lib.load()
     if sites is not None:
         sites = np.ascontiguousarray(np.asarray(sites).round(), dtype=np.int32)
@@ -43,42 +50,52 @@ def _mcmc(fn_name, z, Q, pid, Omega, N, sites=None, **opt):
         cols = n + n * n + 3                                                  # dwell, n x n counts, Q[0,1], Q[1,0], root state
     single = bool(o.reduce) or S == 1
     out = np.zeros((N, cols), order="F") if single else np.zeros((S, cols, N))
-    st = getattr(L, fn_name)(C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
-                             _lib._p(B, C.c_double), float(Omega), _lib._p(nen, C.c_int32),
-                             _lib._p(nodelist, C.c_int32), root, int(N), C.byref(o), _lib._p(out, C.c_double))
-    _lib.check(st)
-    return out if single else out.transpose(0, 2, 1)
+    head = (C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double), float(Omega),
+            _lib._p(nen, C.c_int32), _lib._p(nodelist, C.c_int32), root, int(N))
+    if not maps:
+        _lib.check(getattr(L, fn_name)(*head, C.byref(o), _lib._p(out, C.c_double)))
+        return out if single else out.transpose(0, 2, 1)
+    if map_iters is None:
+        its, J = None, int(N)
+    else:
+        its = np.ascontiguousarray(np.atleast_1d(map_iters), dtype=np.int32)
+        J = int(its.size)
+    args = (_MCMC_VARIANT[fn_name],) + head + (_lib._p(its, C.c_int32) if its is not None else None, 0 if its is None else J,
+                                              C.byref(o), _lib._p(out, C.c_double))
+    m = _two_phase_maps(L.phm_maketreelistMCMC_maps, args, S * J, ft.E)
+    return (out if single else out.transpose(0, 2, 1)), m
 
 
-def sumstatMCMC(z, Q, pid, Omega, N, **opt):
-    """R/sumstatMCMC.R:21-29 -> phm_maketreelistMCMC."""
-    return _mcmc("phm_maketreelistMCMC", z, Q, pid, Omega, N, **opt)
+def sumstatMCMC(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
+    """R/sumstatMCMC.R:21-29 -> phm_maketreelistMCMC.  ``maps=True``: ``(out, maps)`` with the sampled histories at the 0-based
+    iterations ``map_iters`` (default: all), as for every fixed-Q MCMC driver below."""
+    return _mcmc("phm_maketreelistMCMC", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
-def sumstatMCMC_bigtree(z, Q, pid, Omega, N, **opt):
+def sumstatMCMC_bigtree(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
     """R/sumstatMCMC_bigtree.R -> phm_maketreelistMCMC_bigtree (row-normalised partial likelihoods)."""
-    return _mcmc("phm_maketreelistMCMC_bigtree", z, Q, pid, Omega, N, **opt)
+    return _mcmc("phm_maketreelistMCMC_bigtree", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
-def SPARSEsumstatMCMC(z, Q, pid, Omega, N, **opt):
+def SPARSEsumstatMCMC(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
     """R/SPARSEsumstatMCMC.R:21-29 -> phm_SPARSEmaketreelistMCMC."""
-    return _mcmc("phm_SPARSEmaketreelistMCMC", z, Q, pid, Omega, N, **opt)
+    return _mcmc("phm_SPARSEmaketreelistMCMC", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
-def sumstatMCMCks_sweep(z, Q, pid, Omega, N, **opt):
+def sumstatMCMCks_sweep(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
     """The tree sweep of ``sumstatMCMCks`` (R/sumstatMCMCks.R, src/phylomap.cpp:1802-1872) with Q held FIXED:
     hidden-rates Q of even size (``synth.make2sQ``), tips observed only up to parity and re-sampled every sweep,
     n x n transition counters including self pairs, result layout of man/sumstatMCMCks.Rd:19.  ``sumstatMCMCks`` below
     adds the per-iteration Gibbs/MH updates of Q (src/phylomap.cpp:1862-1866) and is the drop-in for the R function."""
-    return _mcmc("phm_maketreelistMCMCks_sweep", z, Q, pid, Omega, N, **opt)
+    return _mcmc("phm_maketreelistMCMCks_sweep", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
-def sumstatMCMCbf_sweep(z, Q, pid, Omega, N, **opt):
+def sumstatMCMCbf_sweep(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
     """The tree sweep of ``sumstatMCMCbf`` (treesamplebf, src/phylomap.cpp:1169-1179) with Q held FIXED, for ANY number of
     states: tips observed, row-normalised pruning, every consecutive pair of segment states counted -- self pairs, i.e.
     virtual jumps, included (shortenerbf :1010-1014) -- into n x n counters.  Columns: n dwell sums, n*n counts (row-major
     from, to), Q[0,1], Q[1,0], root state (0-based); at n = 2 that is the layout of R/sumstatMCMCbf.R:33."""
-    return _mcmc("phm_maketreelistMCMCbf_sweep", z, Q, pid, Omega, N, **opt)
+    return _mcmc("phm_maketreelistMCMCbf_sweep", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
 def _qupdate(fn_name, z, Q, pid, Omega, N, prior, cols, **opt):

@@ -1,6 +1,7 @@
 // phm_drivers.cpp -- the reference-shaped entry points (one per exported driver of src/phylomap.cpp) on top of the engine:
 // fixed-Q drivers, the Q-updating drivers (bf / ks / DIC) and the multi-tree drivers (mt / ksmt); host-side glue only.
 #include "phm_internal.h"
+#include "phm_maps_host.h"
 
 #include <chrono>
 #include <cstdio>
@@ -73,32 +74,117 @@ int32_t run_engine_shards(ShardSet& set, const phm_tree* x, const phm_model& mod
   });
 }
 
+struct McmcMaps;
+int32_t mcmc_maps_setup(McmcMaps& mm, phm_engine* e, size_t i);
+int32_t mcmc_maps_finish(McmcMaps& mm, ShardRun& r, size_t i);
+
+// The stochastic maps of one phm_maketreelistMCMC_maps call: the recorded iterations and the caller's side of
+// the two phases, in history units (history h = s * J + j: chain s at the j-th recorded iteration).
+struct McmcMaps {
+  phm_maps::Host h;
+  std::vector<int32_t> iters;            // the recorded iterations, increasing
+  std::vector<phm_shard> hist_shards;    // shard i's histories: [first * J, (first + count) * J)
+  std::vector<phm_maps::Shard> bufs;
+  std::vector<DevBuf> tcnt;              // sizing with J > 1: the counts by history, [edge][S*J]
+};
+
+// shard i's buffers and its engine's request (the engine of a one-shot call is fresh: no iteration has run)
+int32_t mcmc_maps_setup(McmcMaps& mm, phm_engine* e, size_t i) {
+  const int J = (int)mm.iters.size();
+  const int64_t S = mm.hist_shards[i].count / J, E = mm.h.E;
+  const int64_t pad = e->S_pad;
+  if (mm.h.mode == phm::MAPS_COUNT) {      // counts [J][edge][S_pad], offsets of S*J*E rows (+ the counts by history when J > 1)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const int64_t H = S * J;
+    const double need = 2.0 * E * (double)pad * J + (J > 1 ? 2.0 * E * (double)H : 0.0) + 8.0 * ((double)H * E + 1) +
+                        (double)phm::maps_offsets_work_bytes((int)H, (int)E);
+    if (need > 0.9 * (double)free_b)
+      return fail(PHM_ERR_OOM, "maps: the sizing buffers of " + std::to_string(H) + " histories (" + std::to_string((int64_t)(need / 1048576.0)) +
+                                   " MiB) do not fit in the free HBM (" + std::to_string(free_b >> 20) + " MiB)");
+  }
+  phm::MapsDev dev;
+  const int32_t st = mm.bufs[i].setup(mm.h, mm.hist_shards[i].first, mm.hist_shards[i].count, pad * J, dev);
+  if (st) return st;
+  if (mm.h.mode == phm::MAPS_COUNT && J > 1) HIPCHK(mm.tcnt[i].alloc(sizeof(uint16_t) * (size_t)E * S * J));
+  phm_engine::MapsRequest& q = e->maps;
+  q.mode = mm.h.mode; q.dev = dev; q.J = J;
+  q.j_of_iter.assign(e->max_iters, -1);
+  for (int j = 0; j < J; ++j) q.j_of_iter[mm.iters[j]] = j;
+  return PHM_OK;
+}
+
+// after the engine's sweeps and its status: offsets (sizing) or segments (filling) home
+int32_t mcmc_maps_finish(McmcMaps& mm, ShardRun& r, size_t i) {
+  phm_maps::Shard& b = mm.bufs[i];
+  const int J = (int)mm.iters.size();
+  const int64_t E = mm.h.E, H = b.count, S = H / J;
+  if (mm.h.mode == phm::MAPS_COUNT) {
+    const uint16_t* cnt = b.cnt.as<uint16_t>();
+    int pad = r.e->S_pad;                  // a recovered engine forwards to one of the same layout
+    if (J > 1) {
+      HIPCHK(phm::launch_mcmc_maps_transpose(cnt, (int)S, J, (int)E, pad, mm.tcnt[i].as<uint16_t>(), r.stream));
+      cnt = mm.tcnt[i].as<uint16_t>(); pad = (int)H;
+    }
+    HIPCHK(phm::launch_maps_offsets(cnt, (int)H, (int)E, pad, b.off.as<int64_t>(), b.work.p, r.stream));
+    HIPCHK(hipStreamSynchronize(r.stream));
+  } else if (mm.h.mode == phm::MAPS_WRITE) {
+    unsigned long long badh = 0;
+    HIPCHK(hipMemcpy(&badh, b.bad.p, sizeof badh, hipMemcpyDeviceToHost));
+    if (badh != ~0ull) {
+      const int64_t k = b.first * E + (int64_t)badh, h = k / E;
+      return fail(PHM_ERR_BAD_INPUT, "phm_maketreelistMCMC_maps: the segment count of row " + std::to_string(k) + " (history " + std::to_string(h) +
+                                         ": chain " + std::to_string(h / J) + " at iteration " + std::to_string(mm.iters[h % J]) + ", edge row " +
+                                         std::to_string(k % E + 1) + ") differs from map_off; the offsets must come from a sizing call with the same inputs and seed");
+    }
+  }
+  return b.copy_home(mm.h, i, "phm_maketreelistMCMC_maps");
+}
+
 }  // namespace
 
 extern "C" {
 
 // ---- reference-shaped one-shot drivers -------------------------------------------------------------
+// mm (phm_maketreelistMCMC_maps): the engines replay the recorded sweeps into the maps of their shard
 static int32_t run_mcmc_oneshot(int variant, const phm_tree* x, int32_t n, const double* Q, const double* pid,
                                 const double* B, double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root,
-                                int32_t N, const phm_options* opt, double* out) {
+                                int32_t N, const phm_options* opt, double* out, McmcMaps* mm = nullptr) {
   if (!out) return fail(PHM_ERR_BAD_INPUT, "out is NULL");
   if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
   if (!x) return fail(PHM_ERR_BAD_INPUT, "tree is NULL");
-  const phm_options o = resolve_options(opt);
+  phm_options o = resolve_options(opt);
+  if (mm) o.mapping = PHM_MAP_TILES;
   phm_model model;
   model.n_states = n; model.Q = Q; model.pid = pid; model.B = B; model.Omega = Omega; model.variant = variant;
   ShardSet set;
   int32_t st = phm_plan_shards(o, std::max(1, (int)o.n_replicas), set.shards);
   if (st) return st;
+  if (mm) {
+    const int64_t J = (int64_t)mm->iters.size();
+    mm->hist_shards = set.shards;
+    for (phm_shard& sh : mm->hist_shards) { sh.first *= J; sh.count *= J; }
+    mm->h.shard_total.assign(set.shards.size(), 0);
+    mm->bufs = std::vector<phm_maps::Shard>(set.shards.size());
+    mm->tcnt = std::vector<DevBuf>(set.shards.size());
+  }
   std::string serr;
   st = run_engine_shards(set, x, model, o, N, [&](ShardRun& r, size_t i) -> int32_t {
     // the caller's nen / nodelist / root against the tree (host-only check, once)
     if (i == 0 && !phm::check_reference_orders(r.e->sched, x->edge, nen, nodelist, root, serr)) return fail(PHM_ERR_BAD_INPUT, serr);
+    if (mm) { const int32_t s1 = mcmc_maps_setup(*mm, r.e, i); if (s1) return s1; }
     int32_t s2 = phm_engine_run(r.e, N, r.stream);
     if (!s2) s2 = phm_engine_sync(r.e);
     if (!s2 && !o.reduce) s2 = phm_engine_read_stats(r.e, 0, N, out + (size_t)set.shards[i].first * N * r.e->cols);
+    if (!s2 && mm) {                       // phm_last_kernel_ms: the device time of the sweeps with their replays
+      phm_info inf;
+      s2 = phm_engine_info(r.e, &inf);
+      if (!s2) g_phm_last_kernel_ms = inf.last_run_ms;
+    }
+    if (!s2 && mm) s2 = mcmc_maps_finish(*mm, r, i);
     return s2;
   });
+  if (!st && mm) phm_maps::finish_sizing(mm->h, mm->hist_shards);
   if (st || !o.reduce) return st;
   // The fold of the per-tile sums, device after device.  The first fold starts from zero (launch_stats_reduce with init = NULL),
   // the reduction phm_engine_read_stats runs with reduce = 1: one shard gives its result bit for bit.
@@ -131,6 +217,44 @@ int32_t phm_SPARSEmaketreelistMCMC(const phm_tree* x, int32_t n, const double* Q
                                    double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
                                    const phm_options* opt, double* out) {
   return run_mcmc_oneshot(PHM_MCMC_SPARSE, x, n, Q, pid, B, Omega, nen, nodelist, root, N, opt, out);
+}
+
+// The fixed-Q drivers above with the chains' sampled histories as stochastic maps: every check below runs
+// before any device call; then the plain driver's run on the (tile, branch) kernels, a replay kernel ahead of the branch kernel on
+// each recorded iteration.
+int32_t phm_maketreelistMCMC_maps(int32_t variant, const phm_tree* x, int32_t n, const double* Q, const double* pid, const double* B,
+                                  double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
+                                  const int32_t* map_iters, int32_t n_map_iters, const phm_options* opt, double* out,
+                                  int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state) {
+  const char* who = "phm_maketreelistMCMC_maps";
+  if (variant != PHM_MCMC && variant != PHM_MCMC_BIGTREE && variant != PHM_MCMC_SPARSE && variant != PHM_MCMC_KS && variant != PHM_MCMC_BF)
+    return fail(PHM_ERR_UNSUPPORTED, std::string(who) + ": variant must be PHM_MCMC, PHM_MCMC_BIGTREE, PHM_MCMC_SPARSE, PHM_MCMC_KS or PHM_MCMC_BF");
+  if (!out) return fail(PHM_ERR_BAD_INPUT, "out is NULL");
+  if (N < 1) return fail(PHM_ERR_BAD_INPUT, "N must be >= 1");
+  if (!x) return fail(PHM_ERR_BAD_INPUT, "tree is NULL");
+  McmcMaps mm;
+  if (!map_iters) {
+    if (n_map_iters != 0) return fail(PHM_ERR_BAD_INPUT, std::string(who) + ": map_iters is NULL but n_map_iters is not 0");
+    mm.iters.resize(N);
+    for (int i = 0; i < N; ++i) mm.iters[i] = i;
+  } else {
+    if (n_map_iters < 1) return fail(PHM_ERR_BAD_INPUT, std::string(who) + ": n_map_iters must be >= 1 with map_iters");
+    for (int j = 0; j < n_map_iters; ++j) {
+      if (map_iters[j] < 0 || map_iters[j] >= N)
+        return fail(PHM_ERR_BAD_INPUT, std::string(who) + ": map_iters[" + std::to_string(j) + "] = " + std::to_string(map_iters[j]) + " is not in 0..N-1");
+      if (j > 0 && map_iters[j] <= map_iters[j - 1])
+        return fail(PHM_ERR_BAD_INPUT, std::string(who) + ": map_iters must be strictly increasing (index " + std::to_string(j) + ")");
+    }
+    mm.iters.assign(map_iters, map_iters + n_map_iters);
+  }
+  const phm_options o = resolve_options(opt);
+  if (o.mapping != PHM_MAP_AUTO && o.mapping != PHM_MAP_TILES)
+    return fail(PHM_ERR_UNSUPPORTED, std::string(who) + ": the maps run on the (tile, branch) kernels: mapping PHM_MAP_AUTO or PHM_MAP_TILES");
+  const int64_t S = std::max(1, (int)o.n_replicas), J = (int64_t)mm.iters.size();
+  if (S * J > INT32_MAX) return fail(PHM_ERR_BAD_INPUT, std::string(who) + ": n_replicas * (recorded iterations) must fit in int32");
+  const int32_t st = phm_maps::validate(who, S * J, x->n_edge, map_off, map_cap, map_dwell, map_state, mm.h);
+  if (st) return st;
+  return run_mcmc_oneshot(variant, x, n, Q, pid, B, Omega, nen, nodelist, root, N, opt, out, &mm);
 }
 
 }  // extern "C"

@@ -1249,8 +1249,12 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
     for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
       const int it = e->iters_done + i;
       hipEvent_t* pev = e->phase_timing ? &e->phase_ev[5 * (size_t)i] : nullptr;
-      small_n(e, [&](auto& p) { le = phm::launch_tiles_sweep(p.tl, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev); });
-      if (e->wide()) le = phm::launch_wtiles_sweep(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev);
+      phm::McmcMapsLaunch ml;                // a recorded iteration of the stochastic maps: the replay kernel before the branch kernel
+      const bool rec = e->maps.mode != phm::MAPS_OFF && it < (int)e->maps.j_of_iter.size() && e->maps.j_of_iter[it] >= 0;
+      if (rec) { ml.mode = e->maps.mode; ml.j = e->maps.j_of_iter[it]; ml.J = e->maps.J; ml.dev = e->maps.dev; ++launches; }
+      const phm::McmcMapsLaunch* mlp = rec ? &ml : nullptr;
+      small_n(e, [&](auto& p) { le = phm::launch_tiles_sweep(p.tl, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev, mlp); });
+      if (e->wide()) le = phm::launch_wtiles_sweep(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev, mlp);
       const bool clusters = !e->nw_tier_off.empty();
       const int tiers = (int)e->nw_tier_off.size() - 1;
       if (clusters && e->wide())             // 5 .. 32 states on a deep tree: the node draws by tier, the pruning pass too when it runs on the band kernel
@@ -1307,6 +1311,9 @@ static int32_t recover_capacity(phm_engine* e) {
   }
   if (st) return (st == PHM_ERR_OOM) ? fail(PHM_ERR_CAPACITY, "a branch outgrew its dwell capacity and larger slots do not fit in HBM: " + g_phm_err) : st;
   r->recoveries = e->recoveries + 1;
+  r->maps = e->maps;                     // the replay records the same iterations into the same buffers; a row flagged by the failed run is not
+  if (r->maps.mode == phm::MAPS_WRITE && r->maps.dev.bad_row)      // a row of the recovered one
+    st = hipMemsetAsync(r->maps.dev.bad_row, 0xFF, sizeof(unsigned long long), stream) == hipSuccess ? PHM_OK : fail(PHM_ERR_NO_DEVICE, "hipMemsetAsync failed");
   size_t h = 0;
   for (int it = 0; it < T && !st;) {
     while (!st && h < hist.size() && hist[h].first <= it) { st = phm_engine_set_model(r, hist[h].second.data()); ++h; }

@@ -20,6 +20,7 @@
 
 #include "phm_exp.h"
 #include "phm_mcmc.h"
+#include "phm_mcmc_maps.h"
 #include "phm_narrow.h"
 #include "phm_qupdate.h"
 #include "phm_sched.h"
@@ -391,6 +392,14 @@ struct phm_engine {
   int last_launches = 0;
   int64_t bytes = 0;
   unsigned long long seg_total = 0;
+  // stochastic maps of the MCMC samplers: the replay of the recorded sweeps (phm_mcmc_maps.hip), (tile, branch)
+  // layouts only.  Set by phm_maketreelistMCMC_maps on the buffers of its shard; a capacity recovery carries it into the replacement.
+  struct MapsRequest {
+    int mode = phm::MAPS_OFF;
+    phm::MapsDev dev;                      // seg_cnt [J][edge][S_pad] when counting; offsets, segments and bad_row when writing
+    std::vector<int32_t> j_of_iter;        // per iteration: its place among the recorded ones, -1 = not recorded
+    int J = 0;
+  } maps;
   // frees every device buffer (the host-side description of the problem stays: sched, cols, ...)
   void release_device() {
     DevBuf* all[] = {&d_roots, &d_mask, &d_up, &d_down, &d_col, &d_row, &d_tips, &d_mcount, &d_dw0, &d_dw1, &d_cursor, &d_PL, &d_nstate,

@@ -3,6 +3,8 @@
 // taken from its own slot instead of the tile's sequential stream and the chain powers read from the long tables.
 #include "phm_tiles.h"
 
+#include "phm_mcmc_maps.h"
+
 namespace phm {
 
 namespace {
@@ -704,7 +706,7 @@ hipError_t launch_tiles_init(int n_edge, int n_tiles, int64_t rows, const int32_
 template <int NS>
 hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t>& up_off,
                               const std::vector<int32_t>& down_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
-                              hipEvent_t* phase_ev) {
+                              hipEvent_t* phase_ev, const McmcMapsLaunch* maps) {
   constexpr int WPB = TILES_BLOCK / 64;
   auto blocks = [&](int64_t items) { return dim3((unsigned)((items + WPB - 1) / WPB)); };
   auto pblocks = [&](int64_t items) { return dim3((unsigned)std::min<int64_t>((items + WPB - 1) / WPB, TILES_PERSISTENT_WGS)); };      // node draws: persistent waves, 8 per SIMD
@@ -736,6 +738,10 @@ hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t
     }
   }
   mark(2);
+  if (maps) {
+    const hipError_t me = launch_mcmc_maps_tiles<NS>(p, *maps, it, stream);
+    if (me != hipSuccess) return me;
+  }
   if (p.mstate) {
     if (p.ks) hipLaunchKernelGGL((tiles_branch_kernel<NS, true, true>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
     else hipLaunchKernelGGL((tiles_branch_kernel<NS, false, true>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
@@ -751,8 +757,11 @@ hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t
   return hipGetLastError();
 }
 
-template hipError_t launch_tiles_sweep<2>(const TileParams<2>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*);
-template hipError_t launch_tiles_sweep<3>(const TileParams<3>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*);
-template hipError_t launch_tiles_sweep<4>(const TileParams<4>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*);
+template hipError_t launch_tiles_sweep<2>(const TileParams<2>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*,
+                                              const McmcMapsLaunch*);
+template hipError_t launch_tiles_sweep<3>(const TileParams<3>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*,
+                                              const McmcMapsLaunch*);
+template hipError_t launch_tiles_sweep<4>(const TileParams<4>&, const std::vector<int32_t>&, const std::vector<int32_t>&, const std::vector<int32_t>&, int, hipStream_t, hipEvent_t*,
+                                              const McmcMapsLaunch*);
 
 }  // namespace phm

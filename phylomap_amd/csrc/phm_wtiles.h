@@ -113,11 +113,14 @@ struct WtSparseUp {
   RtcUpParams params;
 };
 
+struct McmcMapsLaunch;      // phm_mcmc_maps.h
+
 // phase_ev: optional 5 events, as in launch_tiles_sweep
 // tier_off: boundaries of the cluster tiers (empty, or p.cl_nodes null: one launch per tree level)
+// maps: a recorded sweep of the stochastic maps, as in launch_tiles_sweep
 hipError_t launch_wtiles_sweep(const WtParams& p, const WtBand& band, const WtSparseUp& sparse, const std::vector<int32_t>& up_off,
                                const std::vector<int32_t>& down_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
-                               hipEvent_t* phase_ev = nullptr);
+                               hipEvent_t* phase_ev = nullptr, const McmcMapsLaunch* maps = nullptr);
 // the pruning (up) sweep alone, for bench.py's roofline block
 hipError_t launch_wtiles_up(const WtParams& p, const WtBand& band, const WtSparseUp& sparse, const std::vector<int32_t>& up_off,
                             const std::vector<int32_t>& tier_off, hipStream_t stream);

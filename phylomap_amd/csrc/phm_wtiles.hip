@@ -1,6 +1,8 @@
 // phm_wtiles.hip -- 5..64 states, one lane per replica, a wavefront per (tile of 64 replicas, item); see phm_wtiles.h.
 #include "phm_wtiles.h"
 
+#include "phm_mcmc_maps.h"
+
 #include <mutex>
 #include <utility>
 
@@ -1474,7 +1476,7 @@ hipError_t launch_wtiles_up(const WtParams& p, const WtBand& band, const WtSpars
 
 hipError_t launch_wtiles_sweep(const WtParams& p, const WtBand& band, const WtSparseUp& sparse, const std::vector<int32_t>& up_off,
                                const std::vector<int32_t>& down_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
-                               hipEvent_t* phase_ev) {
+                               hipEvent_t* phase_ev, const McmcMapsLaunch* maps) {
   constexpr int WPB = WT_BLOCK / 64;
   auto blocks = [&](int64_t items) { return dim3((unsigned)((items + WPB - 1) / WPB)); };
   auto mark = [&](int i) { if (phase_ev) (void)hipEventRecord(phase_ev[i], stream); };
@@ -1510,6 +1512,10 @@ hipError_t launch_wtiles_sweep(const WtParams& p, const WtBand& band, const WtSp
     }
   }
   mark(2);
+  if (maps) {
+    const hipError_t me = launch_mcmc_maps_wtiles(p, *maps, it, stream);
+    if (me != hipSuccess) return me;
+  }
   {
     const bool small = p.n_states <= 32;
     const bool red = p.cnt_tile != nullptr;

@@ -1,9 +1,10 @@
-"""Stochastic maps of sampled and simulated histories: what ``api.simulate_histories(..., maps=True)``
-and ``api.sumstatEXP(..., maps=True)`` return, and the reference's helpers around a history (R/sourceme.R:1-60:
-``makemappededge``, ``nodestatesmake``, ``divtophy``).
+"""Stochastic maps of sampled and simulated histories (DESIGN.md sections 14 and 15): what ``api.simulate_histories(..., maps=True)``,
+``api.sumstatEXP(..., maps=True)`` and the fixed-Q MCMC drivers (``api.sumstatMCMC(..., maps=True)`` and its kin) return, and the
+reference's helpers around a history (R/sourceme.R:1-60: ``makemappededge``, ``nodestatesmake``, ``divtophy``).
 
 Row ``r * E + b`` is history r's map on edge row b: segments ``off[k]:off[k+1]`` of ``dwell`` (time) and ``state`` (1-based,
-the ``mapnames`` convention), from the parent end to the child end."""
+the ``mapnames`` convention), from the parent end to the child end.  From the MCMC drivers, history ``h = s * J + j`` is chain s
+at the j-th of the J recorded iterations (``map_iters[j]``)."""
 from __future__ import annotations
 
 import numpy as np
