@@ -179,9 +179,9 @@ typedef struct phm_debug_options {
   int32_t q_timing;            /* 1 = the rate-updating drivers print the mean host time of the phases of an iteration to stderr */
   double  pade_pivot_min;      /* > 0: smallest pivot phm_expm_pade_mfma's unpivoted block elimination accepts (default 1e-3;
                                   1e300 sends every matrix to the pivoted kernel) */
-  int32_t expect_chunk;        /* > 0: phm_expected_stats runs at most this many sites (rounded up to 64) per pass and this many
-                                  branches per branch-stage launch (default 0: sites by free HBM, branches by a 256 MB scratch);
-                                  the results do not depend on it */
+  int32_t expect_chunk;        /* > 0: phm_expected_stats and phm_expected_through_time run at most this many sites (rounded up to
+                                  64) per pass and this many branches, points or sub-branches per launch (default 0: sites by free
+                                  HBM, the rest by a 256 MB scratch); the results do not depend on it */
   int32_t reserved[3];
 } phm_debug_options;
 
@@ -381,6 +381,33 @@ int32_t phm_maketreelistMCMC_maps(int32_t variant, const phm_tree* x, int32_t n_
 int32_t phm_expected_stats(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
                            const int32_t* observe, const phm_options* opt,
                            double* stats, double* loglik, double* branch_stats, double* node_post);
+
+/* ---- exact state probabilities and expected statistics through time ----
+ * For a fixed Q, per site: WHEN things happen.  Depth runs from the root: d(root) = 0, d(child) = d(parent) + t_b (double, down-pass
+ * order).  Tree, tips, Q, pid, observe, options and limits are phm_expected_stats' and checked the same way.  Outputs, column-major
+ * with the site index fastest (S = n_replicas sites); at least one must be non-NULL:
+ *   occupancy: NULL or S x n_bounds x n, the expected number of lineages in state i at depth bounds[k]: the state posterior at every
+ *     branch with d_parent < bounds[k] <= d_child (a node at the bound counts once, through its parent branch; zero-length branches
+ *     never count), plus the root's posterior at a bound of 0.  Summed over i it is the number of lineages at that depth.
+ *   bin_stats: NULL or S x (n_bounds - 1) x (n + n(n-1)), E[dwell_i] and E[N_ij] within depths [bounds[k], bounds[k+1]) in
+ *     phm_expected_stats' column order; parts of branches outside [bounds[0], bounds[n_bounds-1]) are not reported.
+ *   point_post: NULL or S x n_points x n, P(state at the point | tips) for the point at distance point_pos[p] from the parent end of
+ *     0-based edge row point_edge[p] (0 <= point_pos[p] <= t_b: the parent's and the child's node posteriors at the ends).
+ *   loglik: NULL or S values, phm_expected_stats' loglik bit for bit.
+ * bounds: n_bounds finite values >= 0, strictly increasing; n_bounds >= 1 with occupancy, >= 2 with bin_stats (0 and NULL are
+ * allowed otherwise).  point_edge / point_pos: n_points values, read and checked whenever n_points > 0; n_points >= 1 with
+ * point_post.  A bad bound or point is PHM_ERR_BAD_INPUT naming its 0-based index.  Every check runs before any device call.
+ * n_devices / devices[] shard the sites (every row is the one-device row bit for bit); phm_debug_options.expect_chunk caps the
+ * chunks; phase_timing = 1 prints the device time of the passes, the along-branch vectors, the branch stage and the reductions to
+ * stderr.  phm_last_kernel_ms: device time of all of them, P(t_b) and P(s) included. */
+int32_t phm_expected_through_time(const phm_tree* x, int32_t n_states, const double* Q, const double* pid,
+                                  const int32_t* observe, const phm_options* opt,
+                                  int32_t n_bounds, const double* bounds,
+                                  double* occupancy,   /* S x n_bounds x n, or NULL */
+                                  double* bin_stats,   /* S x (n_bounds-1) x (n + n(n-1)), or NULL */
+                                  int64_t n_points, const int32_t* point_edge, const double* point_pos,
+                                  double* point_post,  /* S x n_points x n, or NULL */
+                                  double* loglik);     /* S, or NULL */
 
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q

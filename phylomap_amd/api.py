@@ -13,6 +13,7 @@ call is a drop-in for the R function (one chain, one tip vector).
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -299,15 +300,9 @@ def simulate_state_tree(z, Q, pid, observe=None, **opt):
     return synth.with_tip_states(z, tips[0])
 
 
-def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, nodes=False, **opt):
-    """Exact E[dwell_i | tips, Q] and E[N_ij | tips, Q] (DESIGN.md section 13) -> phm_expected_stats: what the samplers'
-    posterior means converge to, with no sampling.  Reads ``z['edge']``, ``z['edge.length']``, ``z['Nnode']`` and, without
-    ``sites``, ``z['states']``.  ``sites``: S x n_tips tip states (0 = missing, else 1..n; e.g. the tips of
-    ``simulate_histories``), one site per row.  ``observe``: n values in 1..n, the tip state each true state is seen as.
-    Returns ``(stats, loglik)``, plus ``branch`` with ``per_branch=True`` and ``nodes`` with ``nodes=True``: stats
-    [S, n + n(n-1)] in man/sumstatMCMC.Rd:18 column order, loglik [S] = log p(tips | Q), branch [S, n_edge, n + n(n-1)] by
-    edge row, nodes [S, n_tips + Nnode, n] = P(state of node | tips) by ape node id.  Options: device, devices."""
-    L = _lib.load()
+def _expect_args(z, Q, pid, sites, observe, opt):
+    """What phm_expected_stats and phm_expected_through_time share: the tree with its tip states (``z['states']`` or ``sites``),
+    Q, pid, observe and the options.  ``keep`` holds the arrays the tree points into."""
     Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
     n = Q.shape[0]
     pid = np.ascontiguousarray(pid, dtype=np.float64)
@@ -331,13 +326,27 @@ def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, node
         raise ValueError("observe must have one entry per state")
     o = _lib.make_options(**opt)
     S = max(1, int(o.n_replicas))                  # without sites: n_replicas sites that share z['states']
+    return SimpleNamespace(keep=(flat_edge, el, tips), tree=tree, Q=Q, pid=pid, obs=obs, opt=o, n=n, E=E, NT=T + Nn, S=S)
+
+
+def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, nodes=False, **opt):
+    """Exact E[dwell_i | tips, Q] and E[N_ij | tips, Q] (DESIGN.md section 13) -> phm_expected_stats: what the samplers'
+    posterior means converge to, with no sampling.  Reads ``z['edge']``, ``z['edge.length']``, ``z['Nnode']`` and, without
+    ``sites``, ``z['states']``.  ``sites``: S x n_tips tip states (0 = missing, else 1..n; e.g. the tips of
+    ``simulate_histories``), one site per row.  ``observe``: n values in 1..n, the tip state each true state is seen as.
+    Returns ``(stats, loglik)``, plus ``branch`` with ``per_branch=True`` and ``nodes`` with ``nodes=True``: stats
+    [S, n + n(n-1)] in man/sumstatMCMC.Rd:18 column order, loglik [S] = log p(tips | Q), branch [S, n_edge, n + n(n-1)] by
+    edge row, nodes [S, n_tips + Nnode, n] = P(state of node | tips) by ape node id.  Options: device, devices."""
+    L = _lib.load()
+    a = _expect_args(z, Q, pid, sites, observe, opt)
+    n, S = a.n, a.S
     cols = n + n * (n - 1)
     stats = np.zeros((S, cols), order="F")
     ll = np.zeros(S)
-    br = np.zeros((S, E, cols), order="F") if per_branch else None
-    post = np.zeros((S, T + Nn, n), order="F") if nodes else None
-    _lib.check(L.phm_expected_stats(C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
-                                    _lib._p(obs, C.c_int32), C.byref(o), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
+    br = np.zeros((S, a.E, cols), order="F") if per_branch else None
+    post = np.zeros((S, a.NT, n), order="F") if nodes else None
+    _lib.check(L.phm_expected_stats(C.byref(a.tree), n, _lib._p(a.Q, C.c_double), _lib._p(a.pid, C.c_double),
+                                    _lib._p(a.obs, C.c_int32), C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
                                     _lib._p(br, C.c_double), _lib._p(post, C.c_double)))
     out = [stats, ll]
     if per_branch:
@@ -345,3 +354,36 @@ def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, node
     if nodes:
         out.append(post)
     return tuple(out)
+
+
+def expected_through_time(z, Q, pid, bounds=None, points=None, sites=None, observe=None, **opt):
+    """Exact state probabilities and expected statistics through time -> phm_expected_through_time.
+    Depth runs from the root: 0 there, a child's depth is its parent's plus the edge length (``maps.node_depths``).
+    ``bounds``: K >= 1 strictly increasing depths >= 0, giving ``occupancy`` [S, K, n] (the expected number of lineages in each
+    state at each bound; a node at a bound counts through its parent branch, bound 0 counts the root) and, with K >= 2, ``bins``
+    [S, K - 1, n + n(n-1)] (E[dwell_i] and E[N_ij] within depths [bounds[k], bounds[k+1]) in ``expected_sumstat``'s columns).
+    ``points``: (edge_rows, positions), 0-based edge rows and distances from the parent end (0 <= position <= t_b), giving
+    ``points`` [S, P, n] = P(state at the point | tips).  ``loglik`` [S] always.  ``z``, ``sites``, ``observe`` and the options
+    are ``expected_sumstat``'s.  Returns a dict of those keys."""
+    L = _lib.load()
+    a = _expect_args(z, Q, pid, sites, observe, opt)
+    n, S = a.n, a.S
+    out = {}
+    bnd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1)
+    K = 0 if bnd is None else bnd.size
+    occ = out["occupancy"] = np.zeros((S, K, n), order="F") if K >= 1 else None
+    bins = out["bins"] = np.zeros((S, K - 1, n + n * (n - 1)), order="F") if K >= 2 else None
+    pe = pp = post = None
+    if points is not None:
+        pe = np.ascontiguousarray(points[0], dtype=np.int32).reshape(-1)
+        pp = np.ascontiguousarray(points[1], dtype=np.float64).reshape(-1)
+        if pe.size != pp.size:
+            raise ValueError("points: as many edge rows as positions")
+        post = out["points"] = np.zeros((S, pe.size, n), order="F")
+    ll = out["loglik"] = np.zeros(S)
+    _lib.check(L.phm_expected_through_time(C.byref(a.tree), n, _lib._p(a.Q, C.c_double), _lib._p(a.pid, C.c_double),
+                                           _lib._p(a.obs, C.c_int32), C.byref(a.opt), K, _lib._p(bnd, C.c_double),
+                                           _lib._p(occ, C.c_double), _lib._p(bins, C.c_double), 0 if pe is None else pe.size,
+                                           _lib._p(pe, C.c_int32), _lib._p(pp, C.c_double), _lib._p(post, C.c_double),
+                                           _lib._p(ll, C.c_double)))
+    return {k: v for k, v in out.items() if v is not None}

@@ -54,6 +54,26 @@ struct ExBranchParams {
   int32_t n_out_edges;                         // rows per column of `out`
 };
 
+// Points inside branches.  Item k of a launch is the point s on edge row edge[k]; P holds P(s) at [2k] and
+// P(t_b - s) at [2k + 1].  post == NULL: a = P(s)^T F_b and beta = P(t_b - s) L_c, each rescaled like the passes' vectors with its
+// base-2 exponent (sF_b, sL_c included) beside it.  Otherwise the state posterior a (.) beta / sum(a (.) beta).
+struct ExAlongParams {
+  int32_t n, Sp;
+  const double* P;                             // [2 items][n][n] row-major
+  const int32_t* edge;                         // [items] edge row of each item
+  const int32_t* child;                        // [n_edge] node row of each edge's child
+  const double* F;                             // the passes' F, sF, L, sL (ExPassParams)
+  const double* sF;
+  const double* L;
+  const double* sL;
+  double* a;                                   // [item][n][Sp]
+  double* sa;                                  // [item][Sp]
+  double* beta;                                // [item][n][Sp]
+  double* sbeta;                               // [item][Sp]
+  double* post;                                // NULL, or [state][rows][Sp]
+  int32_t rows;                                // items per state row of post
+};
+
 // L rows of the tips: 1 where observe[a] == y, all ones for y = 0 (tips [T][Sp], obs [n])
 hipError_t launch_ex_tips(const ExPassParams& p, const uint8_t* tips, const int32_t* obs, hipStream_t stream);
 // one height level of the up pass: `steps` (device) holds `count` UpStep entries
@@ -68,5 +88,11 @@ hipError_t launch_ex_post(const ExPassParams& p, int rows, double* post, hipStre
 hipError_t launch_ex_branch(const ExBranchParams& p, int count, hipStream_t stream);
 // tot[col][Sp] += out[col][e][Sp] for e = 0 .. count - 1, in edge order
 hipError_t launch_ex_reduce(const double* out, int cols, int count, int Sp, double* tot, hipStream_t stream);
+// along-branch vectors or posteriors of `count` items (ExAlongParams)
+hipError_t launch_ex_along(const ExAlongParams& p, int count, hipStream_t stream);
+// tot[col][r][Sp] += x[col][q - q0][Sp] over the items q of range r (off[r] <= q < off[r + 1]) that lie in [q0, q0 + count), in
+// order, for r = r_begin .. r_end - 1; tot has n_ranges rows per column.  The occupancy per boundary and the statistics per bin.
+hipError_t launch_ex_range_sum(const double* x, int cols, int count, int64_t q0, const int64_t* off, int r_begin, int r_end,
+                               int n_ranges, int Sp, double* tot, hipStream_t stream);
 
 }  // namespace phm

@@ -292,6 +292,76 @@ __global__ __launch_bounds__(EX_BLOCK) void ex_reduce_kernel(const double* __res
   tot[(size_t)col * Sp + s] = acc;
 }
 
+// Section 16: one lane per (item, site), the item uniform over the block (its edge record and P entries are scalar loads).  The
+// products run in the passes' order: a as O_c = P(t_b)^T F_b, beta as the up pass's P L, so a point at s = t_b repeats O_c's sums.
+__global__ __launch_bounds__(EX_BLOCK) void ex_along_kernel(ExAlongParams p, int k0) {
+  const int s = blockIdx.x * EX_BLOCK + threadIdx.x;
+  if (s >= p.Sp) return;
+  const int k = k0 + blockIdx.y;
+  const int n = p.n;
+  const size_t Sp = p.Sp;
+  const int b = p.edge[k], c = p.child[b];
+  const double* __restrict__ Pf = p.P + (size_t)2 * k * n * n;          // P(s)
+  const double* __restrict__ Pb = Pf + (size_t)n * n;                    // P(t_b - s)
+  const double* __restrict__ F = p.F + (size_t)b * n * Sp + s;
+  const double* __restrict__ L = p.L + (size_t)c * n * Sp + s;
+  if (p.post) {                                                          // ex_post_kernel's order on (a, beta)
+    const size_t ld = (size_t)p.rows * Sp;
+    double* out = p.post + (size_t)k * Sp + s;
+    for (int i = 0; i < n; ++i) {                                        // beta, parked in the output
+      double v = 0.0;
+      for (int j = 0; j < n; ++j) v = fma(Pb[i * n + j], L[(size_t)j * Sp], v);
+      out[i * ld] = v;
+    }
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+      double a = 0.0;
+      for (int j = 0; j < n; ++j) a = fma(Pf[j * n + i], F[(size_t)j * Sp], a);
+      const double be = out[i * ld];
+      sum = fma(a, be, sum);
+      out[i * ld] = a * be;
+    }
+    const double inv = 1.0 / sum;
+    for (int i = 0; i < n; ++i) out[i * ld] = out[i * ld] * inv;
+    return;
+  }
+  double* a = p.a + (size_t)k * n * Sp + s;
+  double mx = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double v = 0.0;
+    for (int j = 0; j < n; ++j) v = fma(Pf[j * n + i], F[(size_t)j * Sp], v);
+    a[(size_t)i * Sp] = v;
+    mx = fmax(mx, v);
+  }
+  p.sa[(size_t)k * Sp + s] = p.sF[(size_t)b * Sp + s] + ex_rescale(a, n, Sp, mx);
+  double* be = p.beta + (size_t)k * n * Sp + s;
+  mx = 0.0;
+  for (int i = 0; i < n; ++i) {
+    double v = 0.0;
+    for (int j = 0; j < n; ++j) v = fma(Pb[i * n + j], L[(size_t)j * Sp], v);
+    be[(size_t)i * Sp] = v;
+    mx = fmax(mx, v);
+  }
+  p.sbeta[(size_t)k * Sp + s] = p.sL[(size_t)c * Sp + s] + ex_rescale(be, n, Sp, mx);
+}
+
+// Lane (site, column, range): a dependent chain over the range's items in order, continued from tot across launches, so the sum
+// does not depend on how the items were chunked.
+__global__ __launch_bounds__(EX_BLOCK) void ex_range_sum_kernel(const double* __restrict__ x, int count, int64_t q0,
+                                                                const int64_t* __restrict__ off, int r0, int n_ranges, int Sp,
+                                                                double* __restrict__ tot) {
+  const int s = blockIdx.x * EX_BLOCK + threadIdx.x;
+  if (s >= Sp) return;
+  const int col = blockIdx.y, r = r0 + blockIdx.z;
+  const int64_t lo = max(off[r], q0), hi = min(off[r + 1], q0 + (int64_t)count);
+  if (lo >= hi) return;
+  const double* xc = x + (size_t)col * count * Sp + s;
+  double* t = tot + ((size_t)col * n_ranges + r) * Sp + s;
+  double acc = *t;
+  for (int64_t q = lo; q < hi; ++q) acc += xc[(size_t)(q - q0) * Sp];
+  *t = acc;
+}
+
 inline dim3 site_grid(int Sp, int y) { return dim3((Sp + EX_BLOCK - 1) / EX_BLOCK, y); }
 
 template <int NP>
@@ -355,6 +425,22 @@ hipError_t launch_ex_reduce(const double* out, int cols, int count, int Sp, doub
   if (count <= 0) return hipSuccess;
   if (cols > EX_GRID_Y) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ex_reduce_kernel, site_grid(Sp, cols), dim3(EX_BLOCK), 0, stream, out, count, Sp, tot);
+  return hipGetLastError();
+}
+
+hipError_t launch_ex_along(const ExAlongParams& p, int count, hipStream_t stream) {
+  for (int k0 = 0; k0 < count; k0 += EX_GRID_Y)
+    hipLaunchKernelGGL(ex_along_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, k0);
+  return hipGetLastError();
+}
+
+hipError_t launch_ex_range_sum(const double* x, int cols, int count, int64_t q0, const int64_t* off, int r_begin, int r_end,
+                               int n_ranges, int Sp, double* tot, hipStream_t stream) {
+  if (count <= 0 || r_end <= r_begin) return hipSuccess;
+  if (cols > EX_GRID_Y) return hipErrorInvalidValue;
+  for (int r0 = r_begin; r0 < r_end; r0 += EX_GRID_Y)
+    hipLaunchKernelGGL(ex_range_sum_kernel, dim3((Sp + EX_BLOCK - 1) / EX_BLOCK, cols, std::min(EX_GRID_Y, r_end - r0)),
+                       dim3(EX_BLOCK), 0, stream, x, count, q0, off, r0, n_ranges, Sp, tot);
   return hipGetLastError();
 }
 

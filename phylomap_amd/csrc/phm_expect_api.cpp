@@ -1,34 +1,13 @@
 // phm_expect_api.cpp -- C-ABI of the exact conditional expectations (phm_expected_stats): validation and
 // everything that depends on the branch alone (level schedules, Poisson weights, Pade squaring counts) on the host, then per
-// device P(t_b) once, and per chunk of sites the up pass, the down pass and the branch stage (phm_expect.hip).
-#include "phm_internal.h"
-#include "phm_expect.h"
+// device P(t_b) once, and per chunk of sites the up pass, the down pass and the branch stage (phm_expect.hip).  The host pieces
+// declared in phm_expect_host.h, which phm_expected_through_time shares, are defined here.
+#include "phm_expect_host.h"
 
-namespace {
+namespace phm_ex {
 
-constexpr double EX_TAIL = 0x1p-60;                    // omitted Poisson mass of a branch's truncated sum
-constexpr double EX_MAX_JUMP_MEAN = 1e6;               // max(-q_ii) t_b: the branch stage runs M_b ~ this many steps
-constexpr size_t EX_SCRATCH = size_t(256) << 20;       // per-(branch, site) values of one branch-stage launch
-
-// What every device of a call shares, checked and derived once on the host.
-struct ExInput {
-  int n = 0, T = 0, Nn = 0, E = 0, NT = 0, S = 0, cols = 0;
-  bool per_site = false;
-  const int32_t* states = nullptr;
-  double mu = 0.0;
-  phm::Schedule sched;
-  std::vector<double> Qr, B, qoff, pid, edge_length;
-  std::vector<int32_t> obs, sq, child_row;
-  std::vector<phm::UpStep> up;                          // grouped by height
-  std::vector<int32_t> up_off;
-  std::vector<phm::ExDown> down;                        // grouped by the depth of the parent
-  std::vector<int32_t> down_off;
-  std::vector<int64_t> w_off;
-  std::vector<double> w;
-};
-
-// pmf of Poisson(x) at 0 .. M + 1 and M: the first m with sum_{k >= m + 2} pmf(k) <= 2^-60.  Computed outward from the mode with
-// pmf(mode) = 1 and normalised by the sum, so x in the thousands keeps full relative precision (no lgamma cancellation).
+// Computed outward from the mode with pmf(mode) = 1 and normalised by the sum, so x in the thousands keeps full relative precision
+// (no lgamma cancellation).
 void poisson_weights(double x, std::vector<double>& p, int& M) {
   if (!(x > 0.0)) { p.assign({1.0, 0.0}); M = 0; return; }
   const int64_t mode = (int64_t)std::floor(x), half = (int64_t)std::ceil(12.0 * std::sqrt(x)) + 40;
@@ -48,10 +27,9 @@ void poisson_weights(double x, std::vector<double>& p, int& M) {
   for (int64_t k = 0; k <= m + 1; ++k) p[k] = r[k] / sum;
 }
 
-int32_t ex_validate(const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* observe, const phm_options& o,
-                    const double* stats, const double* loglik, ExInput& in) {
-  const std::string fn = "phm_expected_stats: ";
-  if (!x || !Q || !pid || !stats || !loglik) return fail(PHM_ERR_BAD_INPUT, fn + "NULL argument (only observe, branch_stats and node_post may be NULL)");
+int32_t ex_validate(const std::string& fn, const phm_tree* x, int32_t n, const double* Q, const double* pid, const int32_t* observe,
+                    const phm_options& o, ExInput& in) {
+  if (!x || !Q || !pid) return fail(PHM_ERR_BAD_INPUT, fn + "NULL argument (x, Q and pid are required)");
   if (n < 2 || n > phm::EX_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, fn + "n_states must be in 2..64");
   if (o.reduce != 0) return fail(PHM_ERR_BAD_INPUT, fn + "reduce must be 0 (expectations are per site)");
   if (o.n_replicas < 0 || o.n_replicas > (1 << 22)) return fail(PHM_ERR_BAD_INPUT, fn + "n_replicas must be in 0..4194304");
@@ -94,8 +72,8 @@ int32_t ex_validate(const phm_tree* x, int32_t n, const double* Q, const double*
   return PHM_OK;
 }
 
-// Squarings of expm(Q t) so that the Pade(6) argument has norm <= 1/2 (phm_expm_pade's own count, pade_squarings, is
-// arma::expmat's, which leaves norms up to ~log2 of the norm and costs 1e-13 .. 1e-12 in P on fast branches).
+// phm_expm_pade's own count, pade_squarings, is arma::expmat's, which leaves norms up to ~log2 of the norm and costs 1e-13 .. 1e-12
+// in P on fast branches.
 int ex_squarings(const double* Q_rm, int n, double t) {
   double norm = 0.0;
   for (int i = 0; i < n; ++i) {
@@ -108,7 +86,6 @@ int ex_squarings(const double* Q_rm, int n, double t) {
   return s;
 }
 
-// Level schedules, child rows, Poisson weights and Pade squaring counts (host, once per call)
 void ex_prepare(ExInput& in) {
   const phm::Schedule& s = in.sched;
   const int T = in.T;
@@ -141,93 +118,144 @@ void ex_prepare(ExInput& in) {
   }
 }
 
+int32_t ex_device_setup(const std::string& fn, const ExInput& in, ExDevice& d, KernelTimer& tm, double& kernel_ms) {
+  const size_t nn = (size_t)in.n * in.n;
+  const int E = in.E;
+  DevBuf dwork, derr;
+  HIPCHK(upload(d.dQ, in.Qr)); HIPCHK(upload(d.dt, in.edge_length)); HIPCHK(upload(d.dsq, in.sq));
+  HIPCHK(dwork.alloc(sizeof(double) * nn * 5 * E)); HIPCHK(d.dP.alloc(sizeof(double) * nn * E));
+  HIPCHK(derr.alloc(sizeof(uint32_t))); HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
+  HIPCHK(upload(d.dB, in.B)); HIPCHK(upload(d.dq, in.qoff)); HIPCHK(upload(d.dpid, in.pid)); HIPCHK(upload(d.dobs, in.obs));
+  HIPCHK(upload(d.dup, in.up)); HIPCHK(upload(d.ddown, in.down)); HIPCHK(upload(d.dchild, in.child_row));
+  HIPCHK(upload(d.dwoff, in.w_off)); HIPCHK(upload(d.dw, in.w));
+  double ms = 0.0;
+  HIPCHK(tm.start());
+  HIPCHK(phm::launch_expm_pade(in.n, d.dQ.as<double>(), d.dt.as<double>(), d.dsq.as<int32_t>(), E, dwork.as<double>(), d.dP.as<double>(),
+                               derr.as<uint32_t>(), nullptr));
+  HIPCHK(tm.stop());
+  uint32_t derrh = 0;
+  HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
+  if (derrh) return fail(PHM_ERR_BAD_INPUT, fn + "singular Pade denominator in expm(Q t_b)");
+  HIPCHK(tm.elapsed(ms));
+  kernel_ms += ms;
+  return PHM_OK;
+}
+
+int32_t ex_sites_per_chunk(size_t per_site, int64_t count, int64_t& Sc_max) {
+  const int chunk = g_phm_debug.expect_chunk;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = free_b / 2 > EX_SCRATCH ? free_b / 2 - EX_SCRATCH : 0;
+  Sc_max = std::max<int64_t>(64, (int64_t)(budget / per_site) / 64 * 64);
+  if (chunk > 0) Sc_max = std::min<int64_t>(Sc_max, ((int64_t)chunk + 63) / 64 * 64);
+  Sc_max = std::min<int64_t>(Sc_max, (count + 63) / 64 * 64);
+  return PHM_OK;
+}
+
+size_t ex_pass_bytes(const ExInput& in) {
+  return sizeof(double) * ((size_t)in.NT * (2 * in.n + 2) + (size_t)in.E * (in.n + 1) + 2) + in.T;
+}
+
+int32_t ExPasses::alloc(const ExInput& in, size_t Spm) {
+  const size_t n = in.n, NT = in.NT, E = in.E;
+  HIPCHK(dL.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsL.alloc(sizeof(double) * NT * Spm));
+  HIPCHK(dO.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsO.alloc(sizeof(double) * NT * Spm));
+  HIPCHK(dF.alloc(sizeof(double) * E * n * Spm)); HIPCHK(dsF.alloc(sizeof(double) * E * Spm));
+  HIPCHK(dll.alloc(sizeof(double) * Spm)); HIPCHK(dlam.alloc(sizeof(double) * Spm)); HIPCHK(dtips.alloc((size_t)in.T * Spm));
+  tips_h.assign((size_t)in.T * Spm, 0);
+  ll_h.assign(Spm, 0.0);
+  return PHM_OK;
+}
+
+phm::ExPassParams ExPasses::params(const ExInput& in, const ExDevice& dev, int Sp) const {
+  phm::ExPassParams pp;
+  pp.n = in.n; pp.n_tips = in.T; pp.Sp = Sp;
+  pp.P = dev.dP.as<double>(); pp.L = dL.as<double>(); pp.sL = dsL.as<double>(); pp.O = dO.as<double>(); pp.sO = dsO.as<double>();
+  pp.F = dF.as<double>(); pp.sF = dsF.as<double>(); pp.ll = dll.as<double>(); pp.lam = dlam.as<double>();
+  return pp;
+}
+
+int32_t ex_run_passes(const std::string& fn, const ExInput& in, const ExDevice& dev, ExPasses& ps, int64_t site0, int64_t Sc, int Sp,
+                      double* node_post, double* loglik, KernelTimer& tm, double& kernel_ms) {
+  const int T = in.T;
+  std::fill(ps.tips_h.begin(), ps.tips_h.end(), (uint8_t)0);     // padding sites: every tip missing
+  for (int64_t k = 0; k < Sc; ++k) {
+    const int32_t* y = in.states + (in.per_site ? (site0 + k) * T : 0);
+    for (int t = 0; t < T; ++t) ps.tips_h[(size_t)t * Sp + k] = (uint8_t)y[t];
+  }
+  HIPCHK(hipMemcpy(ps.dtips.p, ps.tips_h.data(), (size_t)T * Sp, hipMemcpyHostToDevice));
+  const phm::ExPassParams pp = ps.params(in, dev, Sp);
+  HIPCHK(tm.start());
+  HIPCHK(phm::launch_ex_tips(pp, ps.dtips.as<uint8_t>(), dev.dobs.as<int32_t>(), nullptr));
+  for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
+    HIPCHK(phm::launch_ex_up(pp, dev.dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
+  HIPCHK(phm::launch_ex_root(pp, T + in.sched.root, dev.dpid.as<double>(), nullptr));
+  for (size_t l = 0; l + 1 < in.down_off.size(); ++l)
+    HIPCHK(phm::launch_ex_down(pp, dev.ddown.as<phm::ExDown>() + in.down_off[l], in.down_off[l + 1] - in.down_off[l], nullptr));
+  if (node_post) HIPCHK(phm::launch_ex_post(pp, in.NT, node_post, nullptr));
+  HIPCHK(tm.stop());
+  HIPCHK(hipMemcpy(ps.ll_h.data(), ps.dll.p, sizeof(double) * Sc, hipMemcpyDeviceToHost));
+  for (int64_t k = 0; k < Sc; ++k)
+    if (!std::isfinite(ps.ll_h[k]))
+      return fail(PHM_ERR_ZERO_PROB, fn + "site " + std::to_string(site0 + k + 1) + " has probability 0 under Q (its tips are impossible)");
+  if (loglik) std::memcpy(loglik + site0, ps.ll_h.data(), sizeof(double) * Sc);
+  double ms = 0.0;
+  HIPCHK(tm.elapsed(ms));
+  kernel_ms += ms;
+  return PHM_OK;
+}
+
+}  // namespace phm_ex
+
+namespace {
+
+using namespace phm_ex;
+
+const std::string EX_FN = "phm_expected_stats: ";
+
 // Sites [first, first + count) of the call on one device; outputs point at the caller's full arrays (S sites per column).
 int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t count, double* stats, double* loglik,
                       double* branch_stats, double* node_post) {
   int32_t st = select_device(device);
   if (st) return st;
-  const int n = in.n, T = in.T, E = in.E, NT = in.NT, cols = in.cols;
-  const size_t nn = (size_t)n * n, S = (size_t)in.S;
-  DevBuf dQ, dt, dsq, dwork, dP, derr, dB, dq, dpid, dobs, dup, ddown, dchild, dwoff, dw;
-  HIPCHK(upload(dQ, in.Qr)); HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dsq, in.sq));
-  HIPCHK(dwork.alloc(sizeof(double) * nn * 5 * E)); HIPCHK(dP.alloc(sizeof(double) * nn * E));
-  HIPCHK(derr.alloc(sizeof(uint32_t))); HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
-  HIPCHK(upload(dB, in.B)); HIPCHK(upload(dq, in.qoff)); HIPCHK(upload(dpid, in.pid)); HIPCHK(upload(dobs, in.obs));
-  HIPCHK(upload(dup, in.up)); HIPCHK(upload(ddown, in.down)); HIPCHK(upload(dchild, in.child_row));
-  HIPCHK(upload(dwoff, in.w_off)); HIPCHK(upload(dw, in.w));
+  const int n = in.n, E = in.E, NT = in.NT, cols = in.cols;
+  const size_t S = (size_t)in.S;
+  ExDevice dev;
   KernelTimer tm;
   double kernel_ms = 0.0, ms = 0.0;
-  HIPCHK(tm.start());
-  HIPCHK(phm::launch_expm_pade(n, dQ.as<double>(), dt.as<double>(), dsq.as<int32_t>(), E, dwork.as<double>(), dP.as<double>(),
-                               derr.as<uint32_t>(), nullptr));
-  HIPCHK(tm.stop());
-  uint32_t derrh = 0;
-  HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
-  if (derrh) return fail(PHM_ERR_BAD_INPUT, "phm_expected_stats: singular Pade denominator in expm(Q t_b)");
-  HIPCHK(tm.elapsed(ms));
-  kernel_ms += ms;
-  dwork.reset();
+  st = ex_device_setup(EX_FN, in, dev, tm, kernel_ms);
+  if (st) return st;
 
-  // sites per chunk: what fits in half the free HBM next to the branch-stage scratch
-  const int chunk = g_phm_debug.expect_chunk;
-  const size_t per_site = sizeof(double) * ((size_t)NT * (2 * n + 2) + (size_t)E * (n + 1) + 2 + cols + (node_post ? (size_t)NT * n : 0)) + T;
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const size_t budget = free_b / 2 > EX_SCRATCH ? free_b / 2 - EX_SCRATCH : 0;
-  int64_t Sc_max = std::max<int64_t>(64, (int64_t)(budget / per_site) / 64 * 64);
-  if (chunk > 0) Sc_max = std::min<int64_t>(Sc_max, ((int64_t)chunk + 63) / 64 * 64);
-  Sc_max = std::min<int64_t>(Sc_max, (count + 63) / 64 * 64);
+  int64_t Sc_max = 0;
+  st = ex_sites_per_chunk(ex_pass_bytes(in) + sizeof(double) * (cols + (node_post ? (size_t)NT * n : 0)), count, Sc_max);
+  if (st) return st;
   const size_t Spm = (size_t)Sc_max;
-  DevBuf dL, dsL, dO, dsO, dF, dsF, dll, dlam, dtips, dtot, dpost, dout;
-  HIPCHK(dL.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsL.alloc(sizeof(double) * NT * Spm));
-  HIPCHK(dO.alloc(sizeof(double) * NT * n * Spm)); HIPCHK(dsO.alloc(sizeof(double) * NT * Spm));
-  HIPCHK(dF.alloc(sizeof(double) * (size_t)E * n * Spm)); HIPCHK(dsF.alloc(sizeof(double) * E * Spm));
-  HIPCHK(dll.alloc(sizeof(double) * Spm)); HIPCHK(dlam.alloc(sizeof(double) * Spm)); HIPCHK(dtips.alloc((size_t)T * Spm)); HIPCHK(dtot.alloc(sizeof(double) * cols * Spm));
+  ExPasses ps;
+  st = ps.alloc(in, Spm);
+  if (st) return st;
+  DevBuf dtot, dpost, dout;
+  HIPCHK(dtot.alloc(sizeof(double) * cols * Spm));
   if (node_post) HIPCHK(dpost.alloc(sizeof(double) * NT * n * Spm));
+  const int chunk = g_phm_debug.expect_chunk;
   int ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, EX_SCRATCH / (sizeof(double) * cols * Spm)}));
   if (chunk > 0) ne_max = std::min(ne_max, chunk);
   HIPCHK(dout.alloc(sizeof(double) * cols * (size_t)ne_max * Spm));
-  std::vector<uint8_t> tips_h((size_t)T * Spm);
-  std::vector<double> ll_h(Spm);
 
   for (int64_t c0 = 0; c0 < count; c0 += Sc_max) {
     const int64_t Sc = std::min<int64_t>(Sc_max, count - c0);
     const int Sp = (int)((Sc + 63) / 64 * 64);
     const int64_t site0 = first + c0;                              // global id of this chunk's first site
-    std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);           // padding sites: every tip missing
-    for (int64_t k = 0; k < Sc; ++k) {
-      const int32_t* y = in.states + (in.per_site ? (site0 + k) * T : 0);
-      for (int t = 0; t < T; ++t) tips_h[(size_t)t * Sp + k] = (uint8_t)y[t];
-    }
-    HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Sp, hipMemcpyHostToDevice));
-    phm::ExPassParams pp;
-    pp.n = n; pp.n_tips = T; pp.Sp = Sp;
-    pp.P = dP.as<double>(); pp.L = dL.as<double>(); pp.sL = dsL.as<double>(); pp.O = dO.as<double>(); pp.sO = dsO.as<double>();
-    pp.F = dF.as<double>(); pp.sF = dsF.as<double>(); pp.ll = dll.as<double>(); pp.lam = dlam.as<double>();
-    HIPCHK(tm.start());
-    HIPCHK(phm::launch_ex_tips(pp, dtips.as<uint8_t>(), dobs.as<int32_t>(), nullptr));
-    for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-      HIPCHK(phm::launch_ex_up(pp, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
-    HIPCHK(phm::launch_ex_root(pp, T + in.sched.root, dpid.as<double>(), nullptr));
-    for (size_t l = 0; l + 1 < in.down_off.size(); ++l)
-      HIPCHK(phm::launch_ex_down(pp, ddown.as<phm::ExDown>() + in.down_off[l], in.down_off[l + 1] - in.down_off[l], nullptr));
-    if (node_post) HIPCHK(phm::launch_ex_post(pp, NT, dpost.as<double>(), nullptr));
-    HIPCHK(tm.stop());
-    HIPCHK(hipMemcpy(ll_h.data(), dll.p, sizeof(double) * Sc, hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k < Sc; ++k)
-      if (!std::isfinite(ll_h[k]))
-        return fail(PHM_ERR_ZERO_PROB, "phm_expected_stats: site " + std::to_string(site0 + k + 1) + " has probability 0 under Q (its tips are impossible)");
-    std::memcpy(loglik + site0, ll_h.data(), sizeof(double) * Sc);
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    st = ex_run_passes(EX_FN, in, dev, ps, site0, Sc, Sp, node_post ? dpost.as<double>() : nullptr, loglik, tm, kernel_ms);
+    if (st) return st;
     if (node_post)                                                 // [state][row][Sp] -> site + S (row + NT state)
       HIPCHK(hipMemcpy2D(node_post + site0, sizeof(double) * S, dpost.p, sizeof(double) * Sp, sizeof(double) * Sc, (size_t)NT * n,
                          hipMemcpyDeviceToHost));
 
     phm::ExBranchParams bp;
-    bp.n = n; bp.Sp = Sp; bp.mu = in.mu; bp.B = dB.as<double>(); bp.qoff = dq.as<double>(); bp.w_off = dwoff.as<int64_t>();
-    bp.w = dw.as<double>(); bp.child = dchild.as<int32_t>(); bp.L = pp.L; bp.sL = pp.sL; bp.F = pp.F; bp.sF = pp.sF; bp.lam = pp.lam;
-    bp.root = T + in.sched.root;
+    bp.n = n; bp.Sp = Sp; bp.mu = in.mu; bp.B = dev.dB.as<double>(); bp.qoff = dev.dq.as<double>(); bp.w_off = dev.dwoff.as<int64_t>();
+    bp.w = dev.dw.as<double>(); bp.child = dev.dchild.as<int32_t>(); bp.L = ps.dL.as<double>(); bp.sL = ps.dsL.as<double>();
+    bp.F = ps.dF.as<double>(); bp.sF = ps.dsF.as<double>(); bp.lam = ps.dlam.as<double>();
+    bp.root = in.T + in.sched.root;
     bp.out = dout.as<double>();
     HIPCHK(hipMemset(dtot.p, 0, sizeof(double) * cols * Sp));
     for (int e0 = 0; e0 < E; e0 += ne_max) {
@@ -261,8 +289,9 @@ extern "C" {
 int32_t phm_expected_stats(const phm_tree* x, int32_t n_states, const double* Q, const double* pid, const int32_t* observe,
                            const phm_options* opt, double* stats, double* loglik, double* branch_stats, double* node_post) {
   const phm_options o = resolve_options(opt);
+  if (!x || !Q || !pid || !stats || !loglik) return fail(PHM_ERR_BAD_INPUT, EX_FN + "NULL argument (only observe, branch_stats and node_post may be NULL)");
   ExInput in;
-  int32_t st = ex_validate(x, n_states, Q, pid, observe, o, stats, loglik, in);
+  int32_t st = ex_validate(EX_FN, x, n_states, Q, pid, observe, o, in);
   if (st) return st;
   ex_prepare(in);
   std::vector<phm_shard> shards;
