@@ -409,6 +409,24 @@ int32_t phm_expected_through_time(const phm_tree* x, int32_t n_states, const dou
                                   double* point_post,  /* S x n_points x n, or NULL */
                                   double* loglik);     /* S, or NULL */
 
+/* ---- log-likelihood of many rate matrices in one call ----
+ * log p(tips_s | Q_k, pid_k) for K models: what a maximum-likelihood fit evaluates (the points of a finite-difference gradient,
+ * line-search candidates, several starts, one model per simulated dataset).  Section 13's up pass with the models across the
+ * lanes (2..8 states; 9..64 states are computed one model after the other, not batched).  Tree, tips (n_replicas and
+ * tips_per_replica give the S sites), observe and options as phm_expected_stats.
+ *   Q: n x n x K, each matrix column-major, model slowest; checked per model like phm_expected_stats' (a bad model is
+ *     PHM_ERR_BAD_INPUT naming its 0-based index), except that a model that leaves no state (P = I) is legal and there is no
+ *     limit on max(-q_ii) * t_b.
+ *   pid: n x n_pid root priors (normalised here), n_pid = 1 (shared) or K.
+ *   site_of_model NULL ("cross"): every model on every site; out is S x K column-major (site fastest).
+ *   site_of_model = K site indices in 0..S-1 ("paired"): model k on site site_of_model[k] alone; out has K values.
+ * An evaluation of probability 0, or of a model for which some expm(Q_k t_b) meets a zero pivot, is -inf and does not fail the
+ * call.  Every check runs before any device call.  n_devices / devices[] shard the models and phm_debug_options.expect_chunk
+ * caps the chunks of models and sites; every output value is the same bit for bit whatever they are.
+ * phm_last_kernel_ms: device time of the call. */
+int32_t phm_loglik_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid, int32_t n_pid,
+                          const int32_t* observe, const int32_t* site_of_model, const phm_options* opt, double* out);
+
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q
  * (column-major, edited in place) given a statistics row: n dwell sums then n*n counts, row-major (from,to). */

@@ -387,3 +387,54 @@ def expected_through_time(z, Q, pid, bounds=None, points=None, sites=None, obser
                                            _lib._p(pe, C.c_int32), _lib._p(pp, C.c_double), _lib._p(post, C.c_double),
                                            _lib._p(ll, C.c_double)))
     return {k: v for k, v in out.items() if v is not None}
+
+
+def loglik_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **opt):
+    """log p(tips_s | Q_k, pid_k) for K rate matrices in one call -> phm_loglik_models: the likelihood a
+    fit evaluates, with the models across the lanes (2..8 states; wider models run one after the other).  ``Qs``: [K, n, n] (or
+    one n x n matrix).  ``pid``: n values shared by every model, or [K, n].  ``z``, ``sites``, ``observe`` and the options are
+    ``expected_sumstat``'s.  ``site_of_model`` None ("cross"): every model on every site, returns [K, S].  ``site_of_model`` = K
+    0-based site indices ("paired"): model k on its own site alone, returns [K].  An impossible evaluation is ``-inf``."""
+    L = _lib.load()
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError("pid must have n entries, shared or one row per model")
+    som = None
+    if site_of_model is not None:
+        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
+        if som.size != K:
+            raise ValueError("site_of_model must have one entry per model")
+    out = np.zeros(K if som is not None else (K, a.S))
+    _lib.check(L.phm_loglik_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
+                                   _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), C.byref(a.opt), _lib._p(out, C.c_double)))
+    return out
+
+
+def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None,
+           **opt):
+    """Maximum-likelihood fit of a parametrised rate matrix (``ratemodel.RateModel``) to the tips, by ``fit.fit`` over
+    ``loglik_models``: every iteration evaluates all starts' (and, with ``per_site=True``, all sites') gradient points and
+    line-search candidates in one call.  Joint fit over the sites (default): cross mode summed over the sites.
+    ``per_site=True``: one fit per site in lock-step, paired mode; every result gets a leading site axis.  Returns ``fit.fit``'s
+    dict (theta, Q, loglik, aic, iterations, converged, at_bound, grad, starts, calls)."""
+    from . import fit as _fit
+    a = _expect_args(z, np.zeros((model.n, model.n)), np.zeros(model.n), sites, observe, dict(opt))
+    S = a.S
+    edge_len = np.asarray(z["edge.length"], dtype=np.float64)
+    rate0 = (a.NT - int(z["Nnode"])) / float(np.sum(edge_len))       # number of tips / tree length
+    if per_site:
+        def batch(Qs, owner):
+            return loglik_models(z, Qs, pid, sites=sites, observe=observe, site_of_model=owner, **opt)
+    else:
+        def batch(Qs, owner):
+            return loglik_models(z, Qs, pid, sites=sites, observe=observe, **opt).sum(axis=1)
+    r = _fit.fit(batch, model, S if per_site else 1, rate0, starts=starts, seed=seed, gtol=gtol, max_iter=max_iter, bounds=bounds)
+    return r if per_site else _fit.first_problem(r)
