@@ -2,7 +2,8 @@
  * phm_oracle.c -- CPU ORACLE (TEST INFRASTRUCTURE, NOT PRODUCT CODE).  See phm_oracle.h.
  *
  * Plain-C restatement of the hot path of vnminin/phylomap, src/phylomap.cpp.
- * "parity unpinned": the reference has no tests/golden vectors and cannot be built here.
+ * Its reading of the reference is pinned against the reference's own C++ built on a stand-in for Rcpp / Armadillo
+ * (oracle/ref/, tests/test_reference_pin_cpu.py); what stays unpinned without R is listed in phm_oracle.h.
  *
  * Arithmetic contract (DESIGN.md "Arithmetic spec"; the HIP kernels restate the same):
  *   - IEEE binary64, round-to-nearest, NO fused multiply-add (build with -ffp-contract=off);
@@ -162,12 +163,19 @@ double orc_exp(double x) {
 }
 
 
+/* Branch coverage for the tests (ORC_COV_* in phm_oracle.h): every restated branch whose being taken a test wants to ASSERT, not
+ * assume, ORs one bit into a process-wide word; orc_coverage_take() returns the word and clears it. */
+static uint32_t g_cov = 0;
+#define COV(bit) (g_cov |= (uint32_t)(bit))
+uint32_t orc_coverage_take(void) { uint32_t c = g_cov; g_cov = 0; return c; }
+
 /* ------------------------------------------------------------------------------------------ */
 /* "R-stream" mode (rng.mode = 2): R's default generator consumed sequentially in the reference's draw order, so that a
  * machine WITH R + phylomap can be compared sample for sample (tools/r_parity/).  Restated from the published R sources
  * (RNG.c: Mersenne-Twister with set.seed's LCG scrambling; sexp.c: Ahrens-Dieter exp_rand) -- third-party code that is
- * not under /root/reference and could NOT be checked here (no R in the build image): UNVERIFIED.  Covers what the
- * fixed-Q MCMC variants draw: unif_rand (via runif / RcppArmadillo::sample) and exp_rand (via Rcpp::rexp).            */
+ * not part of the reference tree and could NOT be checked against R itself (no R in the build image): pinned to R's published
+ * outputs only.  The stand-in build of the reference (oracle/ref/) draws from these same routines, so the ORDER in which every
+ * driver consumes them is pinned; covers unif_rand (via runif / RcppArmadillo::sample) and exp_rand (via Rcpp::rexp).   */
 /* ------------------------------------------------------------------------------------------ */
 static uint32_t r_mt[624];
 static int r_mti = 625;
@@ -333,6 +341,7 @@ static double r_rgamma(double a, double scale) {
   if (isnan(a) || isnan(scale)) return NAN;
   if (a <= 0.0 || scale <= 0.0) return (scale == 0. || a == 0.) ? 0. : NAN;
   if (!isfinite(a) || !isfinite(scale)) return INFINITY;
+  COV(a < 1 ? ORC_COV_RGAMMA_LT1 : ORC_COV_RGAMMA_GE1);
   if (a < 1) {                                                         /* GS */
     e = 1.0 + exp_m1 * a;
     for (;;) {
@@ -407,6 +416,14 @@ int orc_rstream_selftest(uint32_t seed, int n_unif, int n_exp, double* unif_out,
   for (int i = 0; i < n_exp; ++i) exp_out[i] = r_exp_rand();
   return 0;
 }
+
+/* The R-stream primitives by name, for the stand-in build of the reference (oracle/ref/): its unif_rand / exp_rand / norm_rand /
+ * Rf_rgamma / Rf_dpois forward here, so that R's generators are restated once.  One process-wide stream, as in R. */
+void   orc_r_set_seed(uint32_t seed) { r_set_seed(seed); }
+double orc_r_unif_rand(void) { return r_unif_rand(); }
+double orc_r_exp_rand(void) { return r_exp_rand(); }
+double orc_r_norm_rand(void) { return r_norm_rand(); }
+double orc_r_rgamma(double a, double scale) { return r_rgamma(a, scale); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* RNG front end                                                                               */
@@ -537,9 +554,14 @@ static int sampleOnce(const double* w, int n, double u, int* err) {
   double cum = 0.0;
   int i;
   for (i = 0; i < n; ++i) { cum += w[i] / total; if (u < cum) break; }
-  if (i >= n) { *err |= ORC_ERR_SAMPLEONCE; i = n - 1; }   /* reference would index out of range */
+  if (i >= n) { *err |= ORC_ERR_SAMPLEONCE; i = n - 1; COV(ORC_COV_SAMPLEONCE_OFF); }   /* reference would index out of range */
   return i;
 }
+
+/* per-function entry points: sampleOnce returns n where the reference runs off the end (:85-89); orc_sample_R is the R-stream
+ * categorical draw (RcppArmadillo::sample(sts,1,TRUE,p)) for a given uniform, *err receiving ORC_ERR_ZERO_PROB where it would throw */
+int orc_sampleOnce(const double* w, int n, double u) { int err = 0; int i = sampleOnce(w, n, u, &err); return err ? n : i; }
+int orc_sample_R(const double* p, int n, double u, int* err) { return sample_cat_R(p, n, u, err); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* Branch container: struct Branch + makeabranch, src/phylomap.cpp:18-34                        */
@@ -565,6 +587,7 @@ static void makeabranch(Branch* b, const double* maps, const int32_t* names, int
 static int shortener_arr(double* d, int32_t* s, int m, int n, double* stats, int64_t stride, int iter) {
   if (n < 0) {                 /* shortenerbf, src/phylomap.cpp:997-1028: count EVERY consecutive pair, self pairs */
     n = -n;                    /* included, into n + a*n + b BEFORE merging (:1010-1014); then merge as usual  */
+    if (m > 1) COV(ORC_COV_BF_COUNT);
     for (int i = 1; i < m; ++i) stats[(int64_t)(n + s[i - 1] * n + s[i]) * stride + iter] += 1.0;
     int w2 = 0;
     for (int i = 1; i < m; ++i) {
@@ -575,14 +598,14 @@ static int shortener_arr(double* d, int32_t* s, int m, int n, double* stats, int
   }
   int w = 0;
   for (int i = 1; i < m; ++i) {
-    if (s[i] != s[w]) { ++w; d[w] = d[i]; s[w] = s[i]; }
-    else d[w] = d[w] + d[i];                                   /* :54 */
+    if (s[i] != s[w]) { ++w; d[w] = d[i]; s[w] = s[i]; COV(ORC_COV_SHORT_KEEP); }
+    else { d[w] = d[w] + d[i]; COV(ORC_COV_SHORT_MERGE); }     /* :54 */
   }
   int mm = (m > 0) ? w + 1 : 0;
   for (int i = 1; i < mm; ++i) {
     int a = s[i - 1], b = s[i];
-    if (a < b) stats[(int64_t)(n + a * (n - 1) + b - 1) * stride + iter] += 1.0;   /* :65 */
-    if (a > b) stats[(int64_t)(n + a * (n - 1) + b) * stride + iter] += 1.0;       /* :66 */
+    if (a < b) { stats[(int64_t)(n + a * (n - 1) + b - 1) * stride + iter] += 1.0; COV(ORC_COV_COUNT_UP); }     /* :65 */
+    if (a > b) { stats[(int64_t)(n + a * (n - 1) + b) * stride + iter] += 1.0; COV(ORC_COV_COUNT_DOWN); }       /* :66 */
   }
   return mm;
 }
@@ -592,7 +615,7 @@ int orc_shortener(double* d, int32_t* s, int m, int n, double* stats_row) {
 
 /* matTospmat, src/phylomap.cpp:801-816: keep entries > 1e-7 only */
 void orc_matTospmat(const double* B, int n, double* out) {
-  for (int i = 0; i < n * n; ++i) out[i] = (B[i] > 1e-7) ? B[i] : 0.0;
+  for (int i = 0; i < n * n; ++i) { out[i] = (B[i] > 1e-7) ? B[i] : 0.0; if (B[i] != 0.0 && out[i] == 0.0) COV(ORC_COV_SPARSE_DROP); }
 }
 
 /* ------------------------------------------------------------------------------------------ */
@@ -603,7 +626,8 @@ void orc_matTospmat(const double* B, int n, double* out) {
 static void resamplebranchstates(Branch* br, const double* Bchain, const double* Brow, int n,
                                  rngctx* rc, uint32_t iter, uint32_t branch_id, double* scratch) {
   int ss = br->m;
-  if (ss <= 2) return;                                         /* :269-270 */
+  if (ss <= 2) { COV(ss == 1 ? ORC_COV_RESAMPLE_M1 : ORC_COV_RESAMPLE_M2); return; }   /* :269-270 */
+  COV(ORC_COV_RESAMPLE_DRAW);
   double* bpws = scratch;                                      /* n x ss, column j at bpws + j*n */
   double* p = scratch + (size_t)n * ss;
   for (int i = 0; i < n; ++i) bpws[i] = 0.0;
@@ -641,21 +665,25 @@ static void sampleabranch(Branch* br, const double* Bchain, const double* Brow, 
        element: it and every later segment are left untouched. */
     if (stuck || !(0.0 < segmentlength)) {
       stuck = 1;
+      COV(ORC_COV_VJ_STUCK);
       br_reserve(tmp, tmp->m + 1);
       tmp->d[tmp->m] = segmentlength; tmp->s[tmp->m] = s; tmp->m++;
       continue;
     }
     double r = Omega + Qdiag[s];                               /* :395 */
     double scale = 1.0 / r;                                    /* Rcpp::rexp(n, rate): scale = 1/rate */
+    if (!isfinite(scale)) COV(ORC_COV_VJ_ZERO_RATE);
     while (totallengthinserted < segmentlength) {
       double rl = scale * draw_e(rc, (uint32_t)iter, ENT_BEXP | branch_id, edraw++);   /* :398 */
       br_reserve(tmp, tmp->m + 1);
       if ((totallengthinserted + rl) < segmentlength) {
         tmp->d[tmp->m] = rl; tmp->s[tmp->m] = s; tmp->m++;
         totallengthinserted += rl;
+        COV(ORC_COV_VJ_INSERT);
       } else {
         tmp->d[tmp->m] = segmentlength - totallengthinserted; tmp->s[tmp->m] = s; tmp->m++;
         totallengthinserted = segmentlength;
+        COV(ORC_COV_VJ_FINISH);
       }
     }
   }
@@ -782,7 +810,7 @@ static void sampleinternalnodesMCMC(Branch* brs, int E, double* PL, const double
   }
   if (ks) {
     *root_out = (double)rm[root - 1];                                        /* :1350-1352 / :1123, 0-based */
-    for (int i = 0; i < E && ks == 1; ++i) {                                 /* ks: tips "don't remain the same" :1384-1397 */
+    for (int i = 0; i < E && (ks == 1 || ks == 3); ++i) {                    /* ks: tips "don't remain the same" :1384-1397; 3: :2027-2040 */
       if (edge2[i] <= T) {
         int cn = edge2[i] - 1, ps = rm[edge1[i] - 1];
         for (int c = 0; c < n; ++c) vecc[c] = 0.0;
@@ -1206,7 +1234,7 @@ int orc_maketreelistMCMCmt(const orc_tree* const* xs, int treecount, int n, cons
                            const double* B_cm, double Omega, const int32_t* nen_m, const int32_t* nodelist_m,
                            const int32_t* roots, int32_t N, int variant, const double* prior, int faithful_search,
                            orc_rng* rng, double* out) {
-  if (treecount < 1 || !xs || !prior || n < 2 || N < 0 || rng->mode != 0) return ORC_ERR_BAD_INPUT;
+  if (treecount < 1 || !xs || !prior || n < 2 || N < 0 || (rng->mode != 0 && rng->mode != 2)) return ORC_ERR_BAD_INPUT;
   if (variant != ORC_MCMC_MT && variant != ORC_MCMC_KSMT) return ORC_ERR_BAD_INPUT;
   const int mtks = (variant == ORC_MCMC_KSMT);
   if (mtks ? ((n & 1) || n < 4 || n > 64) : (n != 2)) return ORC_ERR_BAD_INPUT;   /* recordQmtNS hard-wires columns 6, 7 */
@@ -1215,7 +1243,13 @@ int orc_maketreelistMCMCmt(const orc_tree* const* xs, int treecount, int n, cons
   const int Nnode = xs[0]->n_node;
   for (int j = 0; j < treecount; ++j)
     if (xs[j]->n_node != Nnode || xs[j]->n_edge != xs[0]->n_edge || xs[j]->n_tips != xs[0]->n_tips) return ORC_ERR_BAD_INPUT;
-  g_rstream = 0;
+  /* R-stream mode: set.seed(seed_lo); one runif(1) that the reference draws and discards before its loop (:2332 / :2810); then per
+   * iteration every tree in list order -- root, nodelist, the tip re-draws of sampleinternalnodesMCMCmt (:2027-2040, which the
+   * two-state driver runs too: a tip's row of PL is one-hot there, so the draw cannot change the state but does consume a
+   * uniform), the branches -- then the tree choice (:2347) and the updates.  All trees share the one sequential stream. */
+  g_rstream = (rng->mode == 2);
+  if (g_rstream) { r_set_seed(rng->seed_lo); (void)r_unif_rand(); }
+  const int sweep_kind = mtks ? 1 : (g_rstream ? 3 : 2);
   int e = 0;
   double* Q = (double*)malloc(sizeof(double) * n * n);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) QQ(i, j) = Q_cm[i + (size_t)j * n];
@@ -1245,7 +1279,7 @@ int orc_maketreelistMCMCmt(const orc_tree* const* xs, int treecount, int n, cons
       record_Q(Q, n, kk, row, 1, 0);                                                           /* :2343 */
       rcs[j].iter_base = (uint32_t)it;                     /* the row is "iteration 0" of a one-row matrix; Philox sees `it` */
       chain_sweep(&ch[j], n, pid, Bc, B2, Omega, Qd, nen_m + (size_t)j * 2 * Nnode, nodelist_m + (size_t)j * (Nnode - 1),
-                  roots[j], 0, mtks ? 1 : 2, faithful_search, &rcs[j], row, 1, 0, &rootst);
+                  roots[j], 0, sweep_kind, faithful_search, &rcs[j], row, 1, 0, &rootst);
     }
     hstream h = { &rc0, (uint32_t)it, 0, 0 };
 #define HS(id) (h.ent = 0xFFFFFF00u | (uint32_t)(id), h.d = 0, &h)
@@ -1270,6 +1304,7 @@ int orc_maketreelistMCMCmt(const orc_tree* const* xs, int treecount, int n, cons
   }
   for (int j = 0; j < treecount; ++j) { e |= rcs[j].err; chain_free(&ch[j]); }
   e |= rc0.err;
+  g_rstream = 0;
   free(weights); free(rows); free(rcs); free(rngs); free(ch); free(Qd); free(Bc); free(B2); free(Q);
   return e;
 }
@@ -1464,7 +1499,7 @@ static int newunifSample(int startState, int endState, double elapsedTime, doubl
   int numJumps = 0;
   while (notExceed) {
     numJumps++;
-    if (numJumps > 300) return 1;                                            /* :120 */
+    if (numJumps > 300) { COV(ORC_COV_UNIF_CAP); return 1; }                 /* :120 */
     matvec(B2, bpws + (size_t)(numJumps - 1) * n, bpws + (size_t)numJumps * n, n);   /* :127 */
     pk = g_rstream ? r_dpois((double)numJumps, lam) : pk * lam / (double)numJumps;
     double nextProb = pk * bpws[(size_t)numJumps * n + startState] / transProb;      /* :128 */
@@ -1473,14 +1508,17 @@ static int newunifSample(int startState, int endState, double elapsedTime, doubl
   }
   out->m = 0;
   if (numJumps == 0 || (numJumps == 1 && startState == endState)) {          /* :138 */
+    COV(numJumps == 0 ? ORC_COV_UNIF_0JUMP : ORC_COV_UNIF_1JUMP_SAME);
     br_reserve(out, 1);
     out->d[0] = elapsedTime - 0.0; out->s[0] = startState; out->m = 1;
   } else if (numJumps == 1) {                                                /* :144 */
+    COV(ORC_COV_UNIF_1JUMP_DIFF);
     double tj = elapsedTime * draw_u(rc, (uint32_t)iteration, ent, dr++);    /* :147 */
     br_reserve(out, 2);
     out->d[0] = tj - 0.0; out->s[0] = startState;
     out->d[1] = elapsedTime - tj; out->s[1] = endState; out->m = 2;
   } else {
+    COV(ORC_COV_UNIF_MANY);
     for (int i = 0; i < numJumps; ++i) times[i] = elapsedTime * draw_u(rc, (uint32_t)iteration, ent, dr++);   /* :151 */
     for (int i = 1; i < numJumps; ++i) {                                     /* :152 ascending sort */
       double v = times[i]; int j = i - 1;

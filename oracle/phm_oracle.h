@@ -5,9 +5,15 @@
  * (src/phylomap.cpp).  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load this library; the product (phylomap_amd/) never does.
  *
- * PARITY STATUS: bit-level parity with the R package is "parity unpinned" -- the reference ships no tests / golden vectors
- * and cannot be built here (needs R, Rcpp, RcppArmadillo).  What the reference does hold are two known
- * answers, and the oracle reproduces both (tools/squamate_dic/):
+ * PARITY STATUS.  PINNED: this file's reading of src/phylomap.cpp -- control flow, draw order, index arithmetic, column layout,
+ * merge rules, rate updates -- for all ten exported drivers.  The reference's own translation unit, compiled unchanged on a
+ * functional stand-in for Rcpp / RcppArmadillo (oracle/ref/, oracle/ref_build.sh), agrees with R-stream mode (rng.mode = 2) in
+ * every integer column and status and bit for bit in every dwell sum and rate (tests/test_reference_pin_cpu.py; a recorded subset
+ * in tests/golden/ref/ holds on machines without the reference tree).  NOT PINNED (no R here; tools/r_parity/ is the procedure):
+ * R's own generators beyond their published values, Rcpp's and Armadillo's behaviour where the stand-in is written from memory
+ * (oracle/ref/README.md lists each), BLAS's summation order for n > 4, the tie order of sample()'s unstable sort beyond 16
+ * states, arma::expmat (the DIC drivers are pinned around it), ape::reorder and the interpreted helpers (the .R files under R/).
+ * The reference also holds two known answers, and the oracle reproduces both (tools/squamate_dic/):
  *   - exactly: R/simulate_2_state_tree.R:11 notes "n01 is 21" for set.seed(101) on the shipped squamate tree; the R random
  *     stream of this file (set.seed scrambling, Mersenne-Twister, unif_rand, Ahrens-Dieter exp_rand) driving the restated
  *     tip simulation gives n01 = 21;
@@ -37,6 +43,29 @@ extern "C" {
 #define ORC_ERR_TAPE        8   /* scripted RNG tape exhausted */
 #define ORC_ERR_SAMPLEONCE 16   /* sampleOnce ran off the end (src/phylomap.cpp:85-89 returns n) */
 
+/* branch-coverage bits (orc_coverage_take): which restated branches ran since the last call; tests assert on them */
+#define ORC_COV_SHORT_MERGE     (1u << 0)   /* shortener merged two equal neighbours (:54) */
+#define ORC_COV_SHORT_KEEP      (1u << 1)   /* shortener kept a real transition (:53) */
+#define ORC_COV_COUNT_UP        (1u << 2)   /* counted a -> b with a < b (:65) */
+#define ORC_COV_COUNT_DOWN      (1u << 3)   /* counted a -> b with a > b (:66) */
+#define ORC_COV_RESAMPLE_M1     (1u << 4)   /* resamplebranchstates left a 1-segment branch alone (:269) */
+#define ORC_COV_RESAMPLE_M2     (1u << 5)   /* ... a 2-segment branch (:270) */
+#define ORC_COV_RESAMPLE_DRAW   (1u << 6)   /* ... drew interior states */
+#define ORC_COV_VJ_INSERT       (1u << 7)   /* virtual-jump loop inserted a gap (:399-402) */
+#define ORC_COV_VJ_FINISH       (1u << 8)   /* ... closed a segment (:403-408) */
+#define ORC_COV_VJ_STUCK        (1u << 9)   /* ... met a segment of length <= 0 and stopped advancing (:397) */
+#define ORC_COV_UNIF_0JUMP      (1u << 10)  /* newunifSample drew 0 jumps (:138) */
+#define ORC_COV_UNIF_1JUMP_SAME (1u << 11)  /* ... 1 jump between equal end states (:138) */
+#define ORC_COV_UNIF_1JUMP_DIFF (1u << 12)  /* ... 1 jump between different end states (:144) */
+#define ORC_COV_UNIF_MANY       (1u << 13)  /* ... 2 or more jumps (:148) */
+#define ORC_COV_UNIF_CAP        (1u << 14)  /* ... ran into the 300-jump cap (:120) */
+#define ORC_COV_SAMPLEONCE_OFF  (1u << 15)  /* sampleOnce ran off the end (:85-89) */
+#define ORC_COV_SPARSE_DROP     (1u << 16)  /* matTospmat dropped a non-zero entry (:811) */
+#define ORC_COV_RGAMMA_LT1      (1u << 17)  /* Rf_rgamma with shape < 1 (GS) */
+#define ORC_COV_RGAMMA_GE1      (1u << 18)  /* Rf_rgamma with shape >= 1 (GD) */
+#define ORC_COV_BF_COUNT        (1u << 19)  /* shortenerbf counted consecutive pairs (:1010-1014) */
+#define ORC_COV_VJ_ZERO_RATE    (1u << 20)  /* Omega + Q[s,s] == 0: rexp(1, 0) is an infinite gap (:395-398) */
+
 /* variants of the fixed-Q MCMC driver */
 #define ORC_MCMC_PLAIN    0   /* maketreelistMCMC          src/phylomap.cpp:891-935 */
 #define ORC_MCMC_BIGTREE  1   /* maketreelistMCMC_bigtree  src/phylomap.cpp:942-986 */
@@ -56,8 +85,9 @@ extern "C" {
 /* RNG: mode 0 = counter-based Philox4x32-7 streams (the mode the GPU matches bit for bit);
  *      mode 1 = scripted tapes consumed in the reference's draw order (for hand KATs);
  *      mode 2 = "R stream": set.seed(seed_lo) + unif_rand / exp_rand / sorted RcppArmadillo::sample consumed sequentially
- *               in the reference's order (the fixed-Q MCMC variants and sumstatEXP, whose Rf_dpois is restated as dpois_raw with
- *               stirlerr / bd0).  UNVERIFIED: no R here; see tools/r_parity/. */
+ *               in the reference's order (every driver, the list drivers included; Rf_dpois restated as dpois_raw with
+ *               stirlerr / bd0, Rf_rgamma as GS / GD).  The order of consumption is pinned against the reference's own C++
+ *               (tests/test_reference_pin_cpu.py); the generators themselves only to R's published values (no R here). */
 typedef struct orc_rng {
   int32_t  mode;
   uint32_t seed_lo, seed_hi;   /* Philox key */
@@ -106,7 +136,20 @@ double orc_r_qnorm(double p);   /* R's qnorm5(p, 0, 1, TRUE, FALSE) (Wichura AS 
 /* set.seed(seed); rnorm(n_norm); rgamma(n_gamma, shape, scale = scale) -- Rf_rgamma (Ahrens-Dieter GD / GS) as restated for R-stream mode */
 int orc_rstream_gamma_selftest(uint32_t seed, int n_norm, int n_gamma, double shape, double scale, double* norm_out, double* gamma_out);
 
+/* R's generators by name (one process-wide stream, as in R): what the stand-in build of the reference (oracle/ref/) forwards its
+ * unif_rand / exp_rand / norm_rand / Rf_rgamma to, so that they are restated once */
+void   orc_r_set_seed(uint32_t seed);
+double orc_r_unif_rand(void);
+double orc_r_exp_rand(void);
+double orc_r_norm_rand(void);
+double orc_r_rgamma(double a, double scale);
+uint32_t orc_coverage_take(void);   /* OR of the ORC_COV_* bits since the last call; clears them */
+
 /* ---- per-function entry points for known-answer tests ---- */
+/* sampleOnce src/phylomap.cpp:81-90: the index, or n where the reference's loop runs off the end */
+int  orc_sampleOnce(const double* w, int n, double u);
+/* RcppArmadillo::sample(0:(n-1), 1, TRUE, p) for a given uniform, as R-stream mode draws it; *err gets ORC_ERR_ZERO_PROB where it throws */
+int  orc_sample_R(const double* p, int n, double u, int* err);
 /* shortener  src/phylomap.cpp:44-73; returns new segment count; stats row gets += counts */
 int  orc_shortener(double* d, int32_t* s, int m, int n, double* stats_row);
 /* matTospmat src/phylomap.cpp:801-816 (dense copy with entries <= 1e-7 zeroed) */

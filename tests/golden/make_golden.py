@@ -1,8 +1,8 @@
 """Generates tests/golden/*.npz with the CPU oracle (oracle/phm_oracle.c).
 
-The reference ships no tests or golden vectors and cannot be run here (no R toolchain), so these fixtures are
-SELF-GENERATED regression pins of the oracle ("parity unpinned" w.r.t. the R package): inputs (tree, Q, pid,
-Omega, seed) and the expected sufficient-statistic matrices.  Run from the repo root:
+The reference ships no tests or golden vectors, so these fixtures are SELF-GENERATED regression pins of the oracle in its
+counter-based mode: inputs (tree, Q, pid, Omega, seed) and the expected sufficient-statistic matrices.  (What the REFERENCE's
+own C++ writes is recorded apart, for the oracle's R-stream mode: tests/golden/make_ref_golden.py.)  Run from the repo root:
     python tests/golden/make_golden.py
 """
 import os

@@ -13,6 +13,11 @@ _SO = os.path.join(_ROOT, "oracle", "_build", "libphm_oracle.so")
 ERR_ZERO_PROB, ERR_UNIF_CAP, ERR_BAD_INPUT, ERR_TAPE, ERR_SAMPLEONCE = 1, 2, 4, 8, 16
 PLAIN, BIGTREE, SPARSE, KS, BF, MT, KSMT = 0, 1, 2, 3, 4, 5, 6
 FORCE_NORMALISE = 32      # OR-ed into PLAIN / SPARSE: rescaled pruning pass (not in the reference)
+# bits of orc_coverage_take() (ORC_COV_* in oracle/phm_oracle.h), in bit order
+COV = {name: 1 << bit for bit, name in enumerate(
+    ("SHORT_MERGE", "SHORT_KEEP", "COUNT_UP", "COUNT_DOWN", "RESAMPLE_M1", "RESAMPLE_M2", "RESAMPLE_DRAW", "VJ_INSERT", "VJ_FINISH", "VJ_STUCK",
+     "UNIF_0JUMP", "UNIF_1JUMP_SAME", "UNIF_1JUMP_DIFF", "UNIF_MANY", "UNIF_CAP", "SAMPLEONCE_OFF", "SPARSE_DROP", "RGAMMA_LT1", "RGAMMA_GE1",
+     "BF_COUNT", "VJ_ZERO_RATE"))}
 
 
 class Rng(C.Structure):
@@ -157,7 +162,7 @@ def maketreelistMCMC(z, Q, pid, B, Omega, nen, nodelist, root, N, variant=PLAIN,
 
 
 def maketreelistMCMCmt(treelist, Q, pid, B, Omega, nen_m, nodelist_m, roots, N, prior, variant=MT, seed=1, replica=0,
-                       faithful_search=False):
+                       faithful_search=False, rstream=False):
     """orc_maketreelistMCMCmt: nen_m / nodelist_m one row per tree (row-major), roots one entry per tree."""
     Q = np.asarray(Q, dtype=np.float64)
     n = Q.shape[0]
@@ -171,7 +176,7 @@ def maketreelistMCMCmt(treelist, Q, pid, B, Omega, nen_m, nodelist_m, roots, N, 
     prior = np.ascontiguousarray(prior, dtype=np.float64)
     cols = n + n * n + 2 + (3 * (n // 2 - 1) if variant == KSMT else 0) + 1
     out = np.zeros((N, cols), order="F")
-    rng, keep = make_rng(seed, replica)
+    rng, keep = make_rng(seed, replica, rstream=rstream)
     rc = lib().orc_maketreelistMCMCmt(arr, len(fts), n, _ptr(Qc, C.c_double), _ptr(pid, C.c_double), _ptr(Bc, C.c_double),
                                       C.c_double(Omega), _ptr(nen_m, C.c_int32), _ptr(nodelist_m, C.c_int32),
                                       _ptr(roots, C.c_int32), int(N), int(variant), _ptr(prior, C.c_double),
@@ -250,3 +255,40 @@ def makePL(z, n, Bchain, nen, seg_count, normalise):
     rc = lib().orc_makePL(C.byref(ft.c), n, _ptr(Bc, C.c_double), _ptr(nen, C.c_int32), _ptr(sc, C.c_int32),
                           int(normalise), _ptr(PL, C.c_double))
     return PL, rc
+
+
+def matTospmat(B):
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    out = np.zeros_like(B)
+    lib().orc_matTospmat(_ptr(B, C.c_double), B.shape[0], _ptr(out, C.c_double))
+    return out
+
+
+def makePLexp(z, n, P, nen):
+    ft = FlatTree(z)
+    P = np.ascontiguousarray(P, dtype=np.float64)
+    nen = np.ascontiguousarray(nen, dtype=np.int32)
+    PL = np.zeros((2 * ft.T - 1, n))
+    rc = lib().orc_makePLexp(C.byref(ft.c), n, _ptr(P, C.c_double), _ptr(nen, C.c_int32), _ptr(PL, C.c_double))
+    return PL, rc
+
+
+def sampleOnce(w, u):
+    """orc_sampleOnce: the index, or len(w) where the reference's loop runs off the end."""
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    return int(lib().orc_sampleOnce(_ptr(w, C.c_double), w.size, C.c_double(u)))
+
+
+def sample_R(p, u):
+    """The R-stream categorical draw for a given uniform -> (index, error bits)."""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    err = C.c_int(0)
+    i = int(lib().orc_sample_R(_ptr(p, C.c_double), p.size, C.c_double(u), C.byref(err)))
+    return i, err.value
+
+
+def r_stream(seed, n_unif=0, n_exp=0):
+    """set.seed(seed); runif(n_unif); rexp(n_exp) of the restated R generators."""
+    u, e = np.zeros(n_unif), np.zeros(n_exp)
+    lib().orc_rstream_selftest(C.c_uint32(seed), n_unif, n_exp, _ptr(u, C.c_double), _ptr(e, C.c_double))
+    return u, e
