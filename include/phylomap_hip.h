@@ -427,6 +427,23 @@ int32_t phm_expected_through_time(const phm_tree* x, int32_t n_states, const dou
 int32_t phm_loglik_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid, int32_t n_pid,
                           const int32_t* observe, const int32_t* site_of_model, const phm_options* opt, double* out);
 
+/* ---- expected statistics of many rate matrices in one call ----
+ * E[dwell_i | tips_s, Q_k] and E[N_ij | tips_s, Q_k], summed over the tree, with log p(tips_s | Q_k): what an exact score, an
+ * observed information matrix or an EM step needs at many Q.  Section 13's passes and branch stage with the models across the
+ * lanes (2..8 states; 9..64 states go one model after the other through phm_expected_stats, not batched).  Every argument up to
+ * opt is phm_loglik_models', checked the same way, with two limits of phm_expected_stats kept: max(-q_ii) * t_b above 1e6 for any
+ * model is PHM_ERR_UNSUPPORTED, and so is a model that leaves no state with more than 8 states.
+ *   loglik: S x K values (cross, site fastest) or K values (paired): phm_loglik_models' values bit for bit.
+ *   stats: n + n(n-1) columns per evaluation in phm_expected_stats' column order, column-major with the evaluation (the index
+ *     into loglik) fastest.  A structurally zero q_ij gives E[N_ij] = 0; a model that leaves no state (2..8 states) gives
+ *     dwell = t_b on the posterior state and zero counts.
+ * An evaluation that phm_loglik_models reports as -inf gets -inf and a row of NaN and does not fail the call.  Every check runs
+ * before any device call.  n_devices / devices[] shard the models and phm_debug_options.expect_chunk caps the chunks of models,
+ * sites and branches; every output value is the same bit for bit whatever they are.  phm_last_kernel_ms: device time of the call. */
+int32_t phm_expected_stats_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid,
+                                  int32_t n_pid, const int32_t* observe, const int32_t* site_of_model, const phm_options* opt,
+                                  double* stats, double* loglik);
+
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q
  * (column-major, edited in place) given a statistics row: n dwell sums then n*n counts, row-major (from,to). */

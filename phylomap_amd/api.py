@@ -418,13 +418,49 @@ def loglik_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **op
     return out
 
 
+def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **opt):
+    """Exact E[dwell_i | tips_s, Q_k] and E[N_ij | tips_s, Q_k] with log p(tips_s | Q_k) for K rate matrices in one call
+     -> phm_expected_stats_models: ``expected_sumstat`` with the models across the lanes (2..8 states; wider
+    models run one after the other).  Every argument is ``loglik_models``'.  Returns ``(stats, loglik)``: [K, S, n + n(n-1)] and
+    [K, S] ("cross"), or [K, n + n(n-1)] and [K] with ``site_of_model`` ("paired").  ``loglik`` is ``loglik_models``' value bit
+    for bit; an impossible evaluation is ``-inf`` with a row of NaN."""
+    L = _lib.load()
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError("pid must have n entries, shared or one row per model")
+    som = None
+    if site_of_model is not None:
+        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
+        if som.size != K:
+            raise ValueError("site_of_model must have one entry per model")
+    cols = n + n * (n - 1)
+    shape = (K,) if som is not None else (K, a.S)
+    ll = np.zeros(shape)
+    stats = np.zeros((cols,) + shape)                                # column slowest, evaluation (site fastest) within it
+    _lib.check(L.phm_expected_stats_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
+                                           _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), C.byref(a.opt),
+                                           _lib._p(stats, C.c_double), _lib._p(ll, C.c_double)))
+    return np.moveaxis(stats, 0, -1), ll
+
+
 def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None,
-           **opt):
+           gradient="fd", se=False, **opt):
     """Maximum-likelihood fit of a parametrised rate matrix (``ratemodel.RateModel``) to the tips, by ``fit.fit`` over
     ``loglik_models``: every iteration evaluates all starts' (and, with ``per_site=True``, all sites') gradient points and
     line-search candidates in one call.  Joint fit over the sites (default): cross mode summed over the sites.
     ``per_site=True``: one fit per site in lock-step, paired mode; every result gets a leading site axis.  Returns ``fit.fit``'s
-    dict (theta, Q, loglik, aic, iterations, converged, at_bound, grad, starts, calls)."""
+    dict (theta, Q, loglik, aic, iterations, converged, at_bound, grad, starts, calls, evals).
+    ``gradient="exact"``: the score from ``expected_sumstat_models`` at the line-search candidates replaces the 2p difference
+    points.  ``se=True`` adds ``fit.standard_errors``' keys: cov_log [p, p], se_log [p], ci [p, 2] and
+    se_ok, from the observed information in log theta (one call of 2p models per problem)."""
     from . import fit as _fit
     a = _expect_args(z, np.zeros((model.n, model.n)), np.zeros(model.n), sites, observe, dict(opt))
     S = a.S
@@ -433,8 +469,20 @@ def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, se
     if per_site:
         def batch(Qs, owner):
             return loglik_models(z, Qs, pid, sites=sites, observe=observe, site_of_model=owner, **opt)
+
+        def batch_stats(Qs, owner):
+            st, ll = expected_sumstat_models(z, Qs, pid, sites=sites, observe=observe, site_of_model=owner, **opt)
+            return ll, st
     else:
         def batch(Qs, owner):
             return loglik_models(z, Qs, pid, sites=sites, observe=observe, **opt).sum(axis=1)
-    r = _fit.fit(batch, model, S if per_site else 1, rate0, starts=starts, seed=seed, gtol=gtol, max_iter=max_iter, bounds=bounds)
+
+        def batch_stats(Qs, owner):
+            st, ll = expected_sumstat_models(z, Qs, pid, sites=sites, observe=observe, **opt)
+            return ll.sum(axis=1), st.sum(axis=1)
+    P = S if per_site else 1
+    r = _fit.fit(batch, model, P, rate0, starts=starts, seed=seed, gtol=gtol, max_iter=max_iter, bounds=bounds,
+                 gradient=gradient, batch_stats=batch_stats if gradient == "exact" else None)
+    if se:
+        r.update(_fit.standard_errors(batch_stats, model, r["theta"], np.arange(P, dtype=np.int32), r["at_bound"]))
     return r if per_site else _fit.first_problem(r)

@@ -3,42 +3,23 @@
 // P_k(t_b) once and, per chunk of sites, the tips / up / root launches of phm_loglik.hip.  2..8 states run with the models across
 // the lanes.  9..64 states are NOT batched: the models go one after the other through section 13's own launches
 // (ex_device_setup, and the tips / up / root part of ex_run_passes), for correctness only.
-#include "phm_expect_host.h"
-#include "phm_loglik.h"
+// The checked input and its validation (phm_loglik_host.h) are shared with phm_expected_stats_models (section 18) and defined here.
+#include "phm_loglik_host.h"
 
 #include <limits>
 
-namespace {
+namespace phm_ll {
 
 using namespace phm_ex;
 
-const std::string LL_FN = "phm_loglik_models: ";
-constexpr size_t LL_WORK = size_t(256) << 20;          // 5..8 states: Pade matrices of one P launch
-
-// What every device of a call shares.
-struct LlInput {
-  int n = 0, T = 0, Nn = 0, E = 0, NT = 0, S = 0, K = 0;
-  bool per_site = false, paired = false;
-  const int32_t* states = nullptr;
-  const int32_t* site_of_model = nullptr;
-  phm::Schedule sched;
-  std::vector<double> Qr;                               // [K][n * n] row-major
-  std::vector<double> pid;                              // [K][n] normalised
-  std::vector<double> edge_length;
-  std::vector<int32_t> obs;
-  std::vector<phm::UpStep> up;                          // grouped by height
-  std::vector<int32_t> up_off;
-  const int32_t* tips_of(int64_t site) const { return states + (per_site ? site * T : 0); }
-};
-
-int32_t ll_validate(const phm_tree* x, int32_t n, int32_t K, const double* Q, const double* pid, int32_t n_pid, const int32_t* observe,
-                    const int32_t* site_of_model, const phm_options& o, LlInput& in) {
-  if (n < 2 || n > phm::EX_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, LL_FN + "n_states must be in 2..64");
-  if (K < 1) return fail(PHM_ERR_BAD_INPUT, LL_FN + "n_models must be >= 1");
-  if (n_pid != 1 && n_pid != K) return fail(PHM_ERR_BAD_INPUT, LL_FN + "n_pid must be 1 (shared) or n_models");
-  if (o.reduce != 0) return fail(PHM_ERR_BAD_INPUT, LL_FN + "reduce must be 0");
-  if (o.n_replicas < 0 || o.n_replicas > (1 << 22)) return fail(PHM_ERR_BAD_INPUT, LL_FN + "n_replicas must be in 0..4194304");
-  if (!x->edge || !x->edge_length || !x->states) return fail(PHM_ERR_BAD_INPUT, LL_FN + "x$edge, x$edge.length and x$states are required");
+int32_t ll_validate(const std::string& fn, const phm_tree* x, int32_t n, int32_t K, const double* Q, const double* pid, int32_t n_pid,
+                    const int32_t* observe, const int32_t* site_of_model, const phm_options& o, LlInput& in) {
+  if (n < 2 || n > phm::EX_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, fn + "n_states must be in 2..64");
+  if (K < 1) return fail(PHM_ERR_BAD_INPUT, fn + "n_models must be >= 1");
+  if (n_pid != 1 && n_pid != K) return fail(PHM_ERR_BAD_INPUT, fn + "n_pid must be 1 (shared) or n_models");
+  if (o.reduce != 0) return fail(PHM_ERR_BAD_INPUT, fn + "reduce must be 0");
+  if (o.n_replicas < 0 || o.n_replicas > (1 << 22)) return fail(PHM_ERR_BAD_INPUT, fn + "n_replicas must be in 0..4194304");
+  if (!x->edge || !x->edge_length || !x->states) return fail(PHM_ERR_BAD_INPUT, fn + "x$edge, x$edge.length and x$states are required");
   std::string serr;
   if (!phm::build_schedule(x->n_tips, x->n_node, x->n_edge, x->edge, in.sched, serr)) return fail(PHM_ERR_BAD_INPUT, "tree: " + serr);
   in.n = n; in.K = K; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge; in.NT = in.T + in.Nn;
@@ -74,17 +55,21 @@ int32_t ll_validate(const phm_tree* x, int32_t n, int32_t K, const double* Q, co
   if (site_of_model)
     for (int k = 0; k < K; ++k)
       if (site_of_model[k] < 0 || site_of_model[k] >= in.S)
-        return fail(PHM_ERR_BAD_INPUT, LL_FN + "site_of_model[" + std::to_string(k) + "] must be in 0..S-1");
+        return fail(PHM_ERR_BAD_INPUT, fn + "site_of_model[" + std::to_string(k) + "] must be in 0..S-1");
   std::vector<int32_t> order;
   phm::height_levels(in.sched.up, order, in.up_off);
   for (int32_t k : order) in.up.push_back(in.sched.up[k]);
   return PHM_OK;
 }
 
-// out[(site, model)]: cross S x K with the site fastest, paired K
-inline double& ll_out(const LlInput& in, double* out, int64_t site, int64_t model) {
-  return in.paired ? out[model] : out[site + (int64_t)in.S * model];
-}
+}  // namespace phm_ll
+
+namespace {
+
+using namespace phm_ex;
+using namespace phm_ll;
+
+const std::string LL_FN = "phm_loglik_models: ";
 
 // 2..8 states: models [first, first + count) on one device, models across the lanes
 int32_t ll_lanes_device(const LlInput& in, int32_t device, int64_t first, int64_t count, double* out) {
@@ -267,7 +252,7 @@ int32_t phm_loglik_models(const phm_tree* x, int32_t n_states, int32_t n_models,
   const phm_options o = resolve_options(opt);
   if (!x || !Q || !pid || !out) return fail(PHM_ERR_BAD_INPUT, LL_FN + "NULL argument (only observe, site_of_model and opt may be NULL)");
   LlInput in;
-  int32_t st = ll_validate(x, n_states, n_models, Q, pid, n_pid, observe, site_of_model, o, in);
+  int32_t st = ll_validate(LL_FN, x, n_states, n_models, Q, pid, n_pid, observe, site_of_model, o, in);
   if (st) return st;
   std::vector<phm_shard> shards;
   st = phm_plan_shards(o, in.K, shards);

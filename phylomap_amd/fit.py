@@ -18,6 +18,13 @@ The optimiser works in x = log(theta) and minimises phi = -log l by BFGS:
 * a start whose first evaluation is not finite is dropped (its entry of ``starts`` keeps ``-inf``); a candidate that is not
   finite simply fails the line search.
 
+``gradient="exact"`` replaces the difference gradient by the exact score
+g_c = sum_ij dq_ij / dlog theta_c (E[N_ij] / q_ij - E[dwell_i]) (``RateModel.score``) from a batched statistics callable
+``batch_stats(Qs, owner) -> (loglik [K], stats [K, cols])``.  All four rungs of the ladder go through that one call, so whichever
+rung is accepted brings its gradient with it: an iteration is 4 evaluations (statistics included) where ``"fd"`` makes 2p + 4
+likelihood evaluations, there is no gradient-only call after a lower rung, and ``gtol`` is no longer held up at the 1e-7 of the
+differences.  ``"fd"`` stays the default and is what it was bit for bit.
+
 Start 0 is deterministic (every rate = rate0); the others are log-normal around it (sigma = 1 in log theta) from the Philox
 stream of ``seed``, the same for every problem, so a fit is reproducible bit for bit.
 """
@@ -114,27 +121,36 @@ def _advance(r, g, lo, hi, gtol):
     r.state = "search"
 
 
-def fit(batch, model, n_problems, rate0, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None):
+def fit(batch, model, n_problems, rate0, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None, gradient="fd", batch_stats=None):
     """Fits ``model`` on ``n_problems`` problems at once.  ``bounds``: (lower, upper) for theta, scalars or p values each
     (default ``DEFAULT_BOUNDS`` times ``rate0``).  Returns a dict with a leading problem axis: theta [P, p], Q [P, n, n],
     loglik [P], aic [P] (2p - 2 log l), iterations [P], converged [P], at_bound [P, p], grad [P, p] (the last finite-difference
-    gradient of log l in log theta), starts {"loglik": [P, R], "theta": [P, R, p]}, calls (likelihood calls made)."""
+    gradient of log l in log theta; the exact score with ``gradient="exact"``), starts {"loglik": [P, R], "theta": [P, R, p]},
+    calls (batched calls made), evals (models evaluated over all calls).  ``gradient="exact"`` needs ``batch_stats`` (module
+    docstring) and does not use ``batch``."""
     p, P, R = model.p, int(n_problems), int(starts)
     if R < 1:
         raise ValueError("starts must be >= 1")
+    if gradient not in ("fd", "exact"):
+        raise ValueError('gradient must be "fd" or "exact"')
+    exact = gradient == "exact"
+    if exact and batch_stats is None:
+        raise ValueError('gradient="exact" needs batch_stats')
     b = (DEFAULT_BOUNDS[0] * rate0, DEFAULT_BOUNDS[1] * rate0) if bounds is None else bounds
     lo = np.log(np.broadcast_to(np.asarray(b[0], dtype=np.float64), (p,))).copy()
     hi = np.log(np.broadcast_to(np.asarray(b[1], dtype=np.float64), (p,))).copy()
     X0 = start_points(p, rate0, R, seed, lo, hi)
     runs = [_Run(s, X0[r], p) for s in range(P) for r in range(R)]
-    calls = 0
+    calls = evals = 0
     for _ in range(int(max_iter)):
         rows, owner, plan = [], [], []
         for r in runs:
             if r.state == "done":
                 continue
             k0 = len(rows)
-            if r.state == "grad":
+            if exact:                                      # the point itself, or the ladder: each brings its own score
+                pts = r.x[None] if r.state == "grad" else np.clip(r.x[None] + np.outer(np.array(LADDER) * r.scale, r.d), lo, hi)
+            elif r.state == "grad":
                 pts = _fd_points(r.x, p)
                 if r.f is None:
                     pts = np.concatenate([r.x[None], pts])
@@ -147,10 +163,23 @@ def fit(batch, model, n_problems, rate0, starts=8, seed=0, gtol=1e-5, max_iter=2
         if not plan:
             break
         thetas = np.exp(np.asarray(rows))
-        vals = np.asarray(batch(model.Qs(thetas), np.asarray(owner, dtype=np.int32)), dtype=np.float64)
+        evals += len(rows)
+        if exact:
+            vals, stats = batch_stats(model.Qs(thetas), np.asarray(owner, dtype=np.int32))
+            vals, stats = np.asarray(vals, dtype=np.float64), np.asarray(stats, dtype=np.float64)
+        else:
+            vals = np.asarray(batch(model.Qs(thetas), np.asarray(owner, dtype=np.int32)), dtype=np.float64)
         calls += 1
         for r, k0, cnt in plan:
             v = vals[k0:k0 + cnt]
+            if exact and r.state == "grad":
+                if r.f is None:
+                    r.f = -float(v[0])
+                    if not math.isfinite(r.f):             # impossible under this start: dropped
+                        r.alive, r.state = False, "done"
+                        continue
+                _advance(r, -model.score(thetas[k0], stats[k0]), lo, hi, gtol)
+                continue
             if r.state == "grad":
                 if r.f is None:
                     r.f = -float(v[0])
@@ -182,14 +211,16 @@ def fit(batch, model, n_problems, rate0, starts=8, seed=0, gtol=1e-5, max_iter=2
             r.iters += 1
             if taken == 0:
                 r.scale = min(1.0, r.scale * 16.0)
-            if taken == 0:
+            if exact:
+                _advance(r, -model.score(thetas[k0 + taken], stats[k0 + taken]), lo, hi, gtol)
+            elif taken == 0:
                 _advance(r, _fd_grad(v[C:], p), lo, hi, gtol)
             else:
                 r.state = "grad"
 
     out = dict(theta=np.zeros((P, p)), Q=np.zeros((P, model.n, model.n)), loglik=np.full(P, -np.inf), aic=np.full(P, np.inf),
                iterations=np.zeros(P, dtype=np.int64), converged=np.zeros(P, dtype=bool), at_bound=np.zeros((P, p), dtype=bool),
-               grad=np.full((P, p), np.nan), starts=dict(loglik=np.full((P, R), -np.inf), theta=np.zeros((P, R, p))), calls=calls)
+               grad=np.full((P, p), np.nan), starts=dict(loglik=np.full((P, R), -np.inf), theta=np.zeros((P, R, p))), calls=calls, evals=evals)
     for s in range(P):
         mine = runs[s * R:(s + 1) * R]
         best = None
@@ -209,6 +240,67 @@ def fit(batch, model, n_problems, rate0, starts=8, seed=0, gtol=1e-5, max_iter=2
         out["iterations"][s], out["converged"][s] = r.iters, r.converged
         out["at_bound"][s] = (r.x <= lo + 1e-12) | (r.x >= hi - 1e-12)
     return out
+
+
+def information(batch_stats, model, theta, owner, h=1e-4):
+    """Observed information of log l in log theta at ``theta`` ([P, p], or [p] for one problem), problem ``owner[i]`` for row i:
+    J = -d score / d log theta by central differences of the exact score at theta exp(+-h e_c) -- one call of ``batch_stats`` with
+    2p models per problem -- symmetrised.  Truncation O(h^2) = 1e-8; rounding about 1e-10 / h = 1e-6 for a score good to 1e-10.
+    Returns [P, p, p] (or [p, p])."""
+    th = np.asarray(theta, dtype=np.float64)
+    one = th.ndim == 1
+    th = np.atleast_2d(th)
+    P, p = th.shape
+    owner = np.asarray(owner, dtype=np.int32).reshape(-1)
+    x = np.log(th)
+    pts = np.concatenate([_fd_points_h(x[i], p, h) for i in range(P)])
+    thetas = np.exp(pts)
+    _, stats = batch_stats(model.Qs(thetas), np.repeat(owner, 2 * p))
+    stats = np.asarray(stats, dtype=np.float64)
+    J = np.zeros((P, p, p))
+    for i in range(P):
+        g = np.array([model.score(thetas[i * 2 * p + k], stats[i * 2 * p + k]) for k in range(2 * p)])
+        for c in range(p):
+            J[i, c] = -(g[2 * c] - g[2 * c + 1]) / (2.0 * h)
+        J[i] = 0.5 * (J[i] + J[i].T)
+    return J[0] if one else J
+
+
+def _fd_points_h(x, p, h):
+    pts = np.repeat(x[None], 2 * p, axis=0)
+    for c in range(p):
+        pts[2 * c, c] += h
+        pts[2 * c + 1, c] -= h
+    return pts
+
+
+INFO_NOISE = 1e-6                     # what central differences (h = 1e-4) of a score good to 1e-10 resolve in an entry of J
+
+
+def standard_errors(batch_stats, model, theta, owner, at_bound, h=1e-4):
+    """Wald standard errors in log theta from ``information`` for theta [P, p]: cov_log [P, p, p] = J^-1 over the parameters that
+    are not on a bound (those are left out of the inversion; their rows, columns, se and interval are NaN), se_log [P, p] =
+    sqrt(diag), ci [P, p, 2] = theta exp(-+1.96 se_log), se_ok [P], information [P, p, p].  A J that is not positive definite
+    over the free parameters -- its smallest eigenvalue not above ``INFO_NOISE`` max(1, max |J_ij|), what the differences can tell
+    from zero: a flat direction -- gives NaN throughout and se_ok = False, not an exception."""
+    theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    at_bound = np.atleast_2d(np.asarray(at_bound, dtype=bool))
+    P, p = theta.shape
+    J = np.atleast_3d(information(batch_stats, model, theta, owner, h=h)).reshape(P, p, p)
+    cov = np.full((P, p, p), np.nan)
+    ok = np.zeros(P, dtype=bool)
+    for i in range(P):
+        free = ~at_bound[i]
+        if not np.any(free) or not np.all(np.isfinite(J[i][np.ix_(free, free)])):
+            continue
+        Jf = J[i][np.ix_(free, free)]
+        if float(np.min(np.linalg.eigvalsh(Jf))) <= INFO_NOISE * max(1.0, float(np.max(np.abs(Jf)))):
+            continue
+        cov[i][np.ix_(free, free)] = np.linalg.inv(Jf)
+        ok[i] = True
+    se = np.sqrt(np.einsum("kii->ki", cov))
+    ci = np.stack([theta * np.exp(-1.96 * se), theta * np.exp(1.96 * se)], axis=-1)
+    return dict(cov_log=cov, se_log=se, ci=ci, se_ok=ok, information=J)
 
 
 def first_problem(r):

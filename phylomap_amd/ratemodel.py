@@ -57,6 +57,23 @@ class RateModel:
             np.fill_diagonal(out[c], 0.0)
         return out
 
+    def score(self, theta, stats):
+        """The exact score in log theta from one row of expected statistics (n dwell columns, then the off-diagonal counts row
+        by row; summed over the sites of a joint fit): g_c = sum_ij dq_ij / dlog theta_c (E[N_ij] / q_ij - E[dwell_i]).  An
+        entry with q_ij = 0 has E[N_ij] = 0 and contributes nothing."""
+        n = self.n
+        stats = np.asarray(stats, dtype=np.float64).reshape(-1)
+        Q = self.Q(theta)
+        dQ = self.dQ_dlog(theta)
+        off = ~np.eye(n, dtype=bool)
+        counts = np.zeros((n, n))
+        counts[off] = stats[n:]                       # row-major over the off-diagonal entries: the column order
+        live = off & (Q > 0.0)
+        ratio = np.zeros((n, n))
+        ratio[live] = counts[live] / Q[live]
+        term = np.where(live, ratio - stats[:n, None], 0.0)
+        return np.array([float(np.sum(np.where(dQ[c] != 0.0, dQ[c] * term, 0.0))) for c in range(self.p)])
+
 
 def index_model(index_matrix, names=None):
     """corHMM's ``rate.mat``: an n x n integer matrix, 0 (or a negative / NA-like value) = structurally zero, c >= 1 = the c-th
