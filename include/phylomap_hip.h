@@ -444,6 +444,28 @@ int32_t phm_expected_stats_models(const phm_tree* x, int32_t n_states, int32_t n
                                   int32_t n_pid, const int32_t* observe, const int32_t* site_of_model, const phm_options* opt,
                                   double* stats, double* loglik);
 
+/* ---- exact sampler of histories over many rate matrices and sites ----
+ * D = draws independent histories per evaluation (model k, site s), each an exact draw from p(history | tips_s, Q_k, pid_k): the
+ * stochastic maps under a fitted Q with its uncertainty, under per-dataset fits or under a posterior sample of Q.  Every argument
+ * up to site_of_model is phm_loglik_models', checked the same way before any device call.  2..8 states (9..64:
+ * PHM_ERR_UNSUPPORTED); max(-q_ii) * t_b above 32768 for any model is PHM_ERR_UNSUPPORTED naming the model.  There is no jump cap
+ * below that.  An evaluation's index e is its index into loglik; history h = e * draws + d.  H = evaluations * draws.
+ *   loglik: phm_loglik_models' values bit for bit.
+ *   stats:  H x (n + n(n-1)), column-major with the history fastest, phm_expected_stats' column order.
+ *   nodes:  NULL, or H x (n_tips + n_node) history-major: the 1-based TRUE state of every node by ape node id, tips included (a
+ *           missing tip comes out sampled, and so does the hidden state behind an observe map).
+ *   map_off NULL: no maps.  Otherwise the two-phase contract of phm_simulate_histories_maps with R = H: a sizing call (map_dwell
+ *           and map_state NULL) writes the H * n_edge + 1 offsets, a filling call reads them; row h * n_edge + b.
+ * An evaluation whose log-likelihood is -inf is not drawn: NaN rows of stats, zeros in nodes, empty map rows; it does not fail the
+ * call.  Random numbers: phm_options.seed and replica_offset (added to the draw index d); every draw is addressed by the global
+ * evaluation (site * n_models + model) and d, so n_devices / devices[] (which shard the models) and
+ * phm_debug_options.expect_chunk (which caps the chunks of models, sites and tiles) change no output bit.
+ * phm_last_kernel_ms: device time of the whole call. */
+int32_t phm_sample_histories_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid,
+                                    int32_t n_pid, const int32_t* observe, const int32_t* site_of_model, int32_t draws,
+                                    const phm_options* opt, double* stats, double* loglik, int32_t* nodes,
+                                    int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
+
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q
  * (column-major, edited in place) given a statistics row: n dwell sums then n*n counts, row-major (from,to). */

@@ -451,6 +451,51 @@ def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=
     return np.moveaxis(stats, 0, -1), ll
 
 
+def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=None, nodes=False, maps=False, **opt):
+    """``draws`` exact, independent histories given the tips for each of K rate matrices (and each site) in one call (DESIGN.md
+    section 19) -> phm_sample_histories_models: stochastic maps under the models of a fit and its uncertainty
+    (``fit.sample_thetas``), of per-dataset fits or of a posterior sample of Q.  No burn-in, no jump cap (max(-q_ii) t_b up to
+    32 768), missing tips and ``observe`` maps allowed; 2..8 states.  ``Qs``, ``pid``, ``z``, ``sites``, ``observe`` and
+    ``site_of_model`` are ``loglik_models``'.  Returns ``(stats, loglik)``: [K, S, draws, n + n(n-1)] in ``expected_sumstat``'s
+    columns and [K, S] (``loglik_models``' values bit for bit); with ``site_of_model`` the S axis is absent.  ``nodes=True``
+    appends [K, S, draws, n_tips + Nnode] 1-based TRUE states by ape node id, tips included (a missing tip and the hidden state
+    behind ``observe`` come out sampled).  ``maps=True`` appends the histories as a ``maps.Maps`` (a sizing call, then a filling
+    call) whose history index is h = (k S + s) draws + d.  An impossible evaluation (``-inf``) has NaN statistics, zero nodes and
+    empty map rows.  Options: seed, replica_offset, device, devices."""
+    L = _lib.load()
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError("pid must have n entries, shared or one row per model")
+    som = None
+    if site_of_model is not None:
+        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
+        if som.size != K:
+            raise ValueError("site_of_model must have one entry per model")
+    D = int(draws)
+    cols = n + n * (n - 1)
+    shape = (K,) if som is not None else (K, a.S)
+    ll = np.zeros(shape)
+    hshape = shape + (max(D, 1),)
+    stats = np.zeros((cols,) + hshape)                               # column slowest, history fastest within it
+    nst = np.zeros(hshape + (a.NT,), dtype=np.int32) if nodes else None
+    args = (C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(a.obs, C.c_int32),
+            _lib._p(som, C.c_int32), D, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
+            _lib._p(nst, C.c_int32))
+    res = (np.moveaxis(stats, 0, -1), ll) + ((nst,) if nodes else ())
+    if not maps:
+        _lib.check(L.phm_sample_histories_models(*args, None, 0, None, None))
+        return res
+    return res + (_two_phase_maps(L.phm_sample_histories_models, args, int(np.prod(hshape)), a.E),)
+
+
 def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None,
            gradient="fd", se=False, **opt):
     """Maximum-likelihood fit of a parametrised rate matrix (``ratemodel.RateModel``) to the tips, by ``fit.fit`` over

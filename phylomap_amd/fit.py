@@ -308,3 +308,34 @@ def first_problem(r):
     out = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in r.items()}
     out["starts"] = {k: v[0] for k, v in r["starts"].items()}
     return out
+
+
+def sample_thetas(result, M, seed=0):
+    """``M`` draws of theta = exp(N(log theta_hat, cov_log)) from the result of a one-problem ``fit_ml(se=True)``: the models a
+    caller hands to ``api.sample_histories`` for stochastic maps under rate uncertainty.  The normals are Box-Muller pairs
+    (sqrt(-2 log u1) cos(2 pi u2), then the sine) over ``PhiloxStream(seed, 12)``, taken draw by draw and, within a draw, free
+    parameter by free parameter, and coloured by the lower Cholesky factor of cov_log over the free parameters.  A parameter on
+    a bound (NaN standard error) is held at theta_hat.  Raises ValueError when ``se_ok`` is false.  Returns [M, p]."""
+    theta = np.asarray(result["theta"], dtype=np.float64)
+    if theta.ndim != 1:
+        raise ValueError("sample_thetas takes the result of one problem (index a per-site result first)")
+    if "se_ok" not in result or not bool(np.all(result["se_ok"])):
+        raise ValueError("the fit has no usable covariance (se_ok is false): no draws")
+    cov = np.asarray(result["cov_log"], dtype=np.float64).reshape(theta.size, theta.size)
+    free = np.isfinite(np.asarray(result["se_log"], dtype=np.float64).reshape(-1))
+    pf = int(np.sum(free))
+    M = int(M)
+    out = np.repeat(theta[None], M, axis=0)
+    if pf == 0 or M < 1:
+        return out
+    chol = np.linalg.cholesky(cov[np.ix_(free, free)])
+    rng = PhiloxStream(seed, 12)
+    total = M * pf
+    z = np.empty(total + (total & 1))
+    for i in range(0, z.size, 2):
+        rad = math.sqrt(-2.0 * math.log(rng.uniform()))
+        ang = 2.0 * math.pi * rng.uniform()
+        z[i], z[i + 1] = rad * math.cos(ang), rad * math.sin(ang)
+    z = z[:total].reshape(M, pf)
+    out[:, free] = np.exp(np.log(theta[free])[None] + z @ chol.T)
+    return out
