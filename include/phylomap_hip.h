@@ -466,6 +466,32 @@ int32_t phm_sample_histories_models(const phm_tree* x, int32_t n_states, int32_t
                                     const phm_options* opt, double* stats, double* loglik, int32_t* nodes,
                                     int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
 
+/* ---- batched posterior sampling of the rates of an index model by exact data augmentation ----
+ * n_chains chains in lock-step, one per lane.  The model: q_ij = theta_c for index[i, j] = c in 1..n_params, 0 for index 0 (index:
+ * n x n column-major, diagonal ignored, every parameter owning at least one entry); the diagonal is minus the row's entries summed
+ * left to right.  Prior: theta_c ~ Gamma(shape prior[.][c][0], rate prior[.][c][1]), n_prior = 1 (shared) or n_chains rows.
+ * Iteration i of chain k: log p(tips | Q(theta)) (phm_loglik_models' value bit for bit), one exact history per site of the chain
+ * -- bit for bit the history phm_sample_histories_models(draws = 1, replica_offset = i + opt->replica_offset, same seed) returns
+ * for evaluation (site, chain k) among n_chains models -- and then theta_c ~ Gamma(shape + N_c, rate + W_c), N_c the history's
+ * jumps over the entries of parameter c and W_c its dwell times, dwell_i once per entry (i, j) of c (sites ascending, entries
+ * row-major).  A draw above theta_max (or not positive) is rejected and the old value kept, counted in rejected[chain][c].
+ *   site_of_chain = n_chains site indices ("paired": chain k sees site site_of_chain[k] alone; sites may repeat), or NULL
+ *     ("joint": every chain sees all S sites; log-likelihood and statistics are summed over the sites, ascending).
+ *   theta0 [chain][n_params] in (0, theta_max]; theta_max truncates the prior and bounds the table of the sampler:
+ *     (most rates in a row) * theta_max * (longest branch) above 32768 is PHM_ERR_UNSUPPORTED.
+ *   rows = ceil(iters / thin); row r is iteration r * thin: theta [rows][chain][n_params] (row 0: theta0), loglik [rows][chain],
+ *     stats NULL or [rows][chain][n + n(n-1)] (phm_expected_stats' columns: the history drawn under the row's theta).
+ *   chain_status[chain]: 1 for a chain whose log-likelihood came out -inf; its rows are NaN from there on, the call goes on.
+ * 2..8 states (more: PHM_ERR_UNSUPPORTED).  Bad index, prior, theta0, iters, thin or site: PHM_ERR_BAD_INPUT naming the chain or
+ * parameter; the rest is checked as phm_loglik_models checks it; all before any device call.  Rate draws are addressed by
+ * (parameter, chain, i + replica_offset): n_devices / devices[] (which shard the chains) and phm_debug_options.expect_chunk (which
+ * caps the chunks of chains and branches) change no output bit.  phm_last_kernel_ms: device time of the call. */
+int32_t phm_gibbs_rates(const phm_tree* x, int32_t n_states, const int32_t* index, int32_t n_params, int32_t n_chains,
+                        const double* theta0, const double* prior, int32_t n_prior, double theta_max, const double* pid,
+                        int32_t n_pid, const int32_t* observe, const int32_t* site_of_chain, int32_t iters, int32_t thin,
+                        const phm_options* opt, double* theta, double* loglik, double* stats, int32_t* rejected,
+                        int32_t* chain_status);
+
 /* ---- host-side rate-matrix update of the Q-updating variants (no device needed) ----
  * One iteration of updatel01/l10 (bf) or updateksl01/l10, updaterkappas, updatelkappas, updategammas (ks) applied to Q
  * (column-major, edited in place) given a statistics row: n dwell sums then n*n counts, row-major (from,to). */

@@ -13,6 +13,7 @@ call is a drop-in for the R function (one chain, one tip vector).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -531,3 +532,82 @@ def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, se
     if se:
         r.update(_fit.standard_errors(batch_stats, model, r["theta"], np.arange(P, dtype=np.int32), r["at_bound"]))
     return r if per_site else _fit.first_problem(r)
+
+
+def posterior_rates(z, model, pid, prior, iters, chains=4, sites=None, observe=None, per_site=False, theta0=None, theta_max=None,
+                    thin=1, stats=True, **opt):
+    """Posterior sample of the rates of an index model (``ratemodel.er`` / ``sym`` / ``ard`` / ``index_model``) by exact data
+    augmentation -> phm_gibbs_rates: the Bayesian counterpart of ``fit_ml``.  ``chains`` chains run in
+    lock-step, one per lane; every iteration draws an exact history given the tips and the chain's rates (``sample_histories``'
+    sampler: no burn-in of the history, no jump cap) and then every rate from its Gamma full conditional.
+    ``prior``: Gamma (shape, rate) per parameter, [p, 2] (or one pair for all) shared by the chains, or [C, p, 2].
+    Joint (default): every chain sees all the sites; C = chains.  ``per_site=True``: ``chains`` chains per site in one call
+    (paired mode), C = S * chains, chain s * chains + r on site s, and every result gets a leading site axis after the rows.
+    ``theta0``: [C, p] starts (default ``fit.start_points`` around tips / tree length, the same for every site).
+    ``theta_max``: a truncation of the prior -- every rate is confined to (0, theta_max], a draw of the conditional above it is
+    rejected and the old value kept (default 100 * tips / tree length); it also bounds the sampler's table:
+    (most rates in a row) * theta_max * (longest branch) <= 32 768.
+    Returns a dict: theta [rows, C, p] (row r = iteration r * thin; row 0 the starts), loglik [rows, C] (``loglik_models``'
+    value of the row's theta bit for bit, summed over the sites when joint: what DIC needs), stats [rows, C, n + n(n-1)] (the
+    history drawn under the row's theta in ``expected_sumstat``'s columns: the posterior of N_ij and dwell_i under rate
+    uncertainty; ``stats=False`` leaves it out), rejected [C, p], status [C] (1: impossible tips, NaN rows), theta_max, thin,
+    site_of_chain and model.  Iteration i's history of chain k is ``sample_histories(posterior.rate_matrices(model, theta[i]),
+    draws=1, replica_offset=i + replica_offset)``'s, so node states and maps of any iteration can be redrawn after the fact.
+    Options: seed, replica_offset, device, devices."""
+    from . import fit as _fit
+    if getattr(model, "index", None) is None:
+        raise ValueError("posterior_rates needs an index model (ratemodel.er, sym, ard or index_model)")
+    L = _lib.load()
+    n, p = model.n, model.p
+    a = _expect_args(z, np.zeros((n, n)), np.zeros(n), sites, observe, dict(opt))
+    S = a.S
+    T = a.NT - int(z["Nnode"])
+    rate0 = T / float(np.sum(np.asarray(z["edge.length"], dtype=np.float64)))
+    theta_max = 100.0 * rate0 if theta_max is None else float(theta_max)
+    per = int(chains)
+    if per < 1:
+        raise ValueError("chains must be >= 1")
+    Cn = S * per if per_site else per
+    som = np.ascontiguousarray(np.repeat(np.arange(S, dtype=np.int32), per)) if per_site else None
+    if theta0 is None:
+        lo, hi = math.log(_fit.DEFAULT_BOUNDS[0] * rate0), math.log(theta_max)
+        th0 = np.exp(_fit.start_points(p, min(rate0, theta_max), per, opt.get("seed", 0), lo, hi))
+        th0 = np.minimum(th0, theta_max)
+        if per_site:
+            th0 = np.tile(th0, (S, 1))
+    else:
+        th0 = np.asarray(theta0, dtype=np.float64)
+    th0 = np.ascontiguousarray(th0, dtype=np.float64).reshape(-1, p)
+    if th0.shape[0] != Cn:
+        raise ValueError(f"theta0 must be [{Cn}, {p}]")
+    pr = np.asarray(prior, dtype=np.float64)
+    if pr.ndim == 1:
+        pr = np.tile(pr.reshape(1, 2), (p, 1))
+    if pr.ndim == 2:
+        pr = pr[None]
+    if pr.shape[1:] != (p, 2) or pr.shape[0] not in (1, Cn):
+        raise ValueError("prior must be [p, 2] (shared) or [C, p, 2]")
+    pr = np.ascontiguousarray(pr)
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, Cn):
+        raise ValueError("pid must have n entries, shared or one row per chain")
+    idx = np.ascontiguousarray(np.asarray(model.index, dtype=np.int32).T)     # column-major
+    iters, thin = int(iters), int(thin)
+    rows = max(1, -(-iters // max(thin, 1)))
+    cols = n + n * (n - 1)
+    theta = np.zeros((rows, Cn, p))
+    ll = np.zeros((rows, Cn))
+    st = np.zeros((rows, Cn, cols)) if stats else None
+    rej = np.zeros((Cn, p), dtype=np.int32)
+    status = np.zeros(Cn, dtype=np.int32)
+    _lib.check(L.phm_gibbs_rates(C.byref(a.tree), n, _lib._p(idx, C.c_int32), p, Cn, _lib._p(th0, C.c_double),
+                                 _lib._p(pr, C.c_double), pr.shape[0], theta_max, _lib._p(pid, C.c_double), pid.shape[0],
+                                 _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), iters, thin, C.byref(a.opt),
+                                 _lib._p(theta, C.c_double), _lib._p(ll, C.c_double), _lib._p(st, C.c_double),
+                                 _lib._p(rej, C.c_int32), _lib._p(status, C.c_int32)))
+    out = dict(theta=theta, loglik=ll, stats=st, rejected=rej, status=status)
+    if per_site:
+        lead = dict(theta=1, loglik=1, stats=1, rejected=0, status=0)         # axes before the chain axis
+        out = {k: (None if v is None else v.reshape(v.shape[:lead[k]] + (S, per) + v.shape[lead[k] + 1:])) for k, v in out.items()}
+    out.update(theta_max=theta_max, thin=thin, site_of_chain=som, model=model, per_site=bool(per_site), chains=per)
+    return out

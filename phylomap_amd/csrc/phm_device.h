@@ -25,6 +25,8 @@ constexpr uint32_t ENT_NODE   = 0u;
 constexpr uint32_t ENT_BSTATE = 1u << 30;
 constexpr uint32_t ENT_BEXP   = 2u << 30;
 constexpr uint32_t ENT_BUNIF  = 3u << 30;
+// phm_gibbs_rates' host-side rate draws share the address space of phm_sample.hip's histories (ENT_NODE, ENT_BUNIF) and take the
+// value 2 << 30, free there, as ENT_RATE (phm_qupdate.h)
 
 // Philox4x32 with SEVEN rounds (Random123; Salmon et al. 2011): the fewest rounds at which the generator passes BigCrush
 // ("Crush-resistant"), ten being Random123's default safety margin.  The round function and key schedule are pinned by the

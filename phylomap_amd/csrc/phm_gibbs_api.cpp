@@ -1,0 +1,379 @@
+// phm_gibbs_api.cpp -- C-ABI of the batched posterior sampler of the rates of an index model by exact data augmentation
+// (phm_gibbs_rates).  C chains run in lock-step, one chain per lane.  Iteration i of chain k: Q_k = Q(theta_k),
+// section 17's P, tips, up and root launches, unchanged, on the chunk's buffers; one exact history per evaluation by section 19's
+// kernels in their packed form (phm_sample.hip, lane = chain); then, on the host, the conjugate Gamma draw of every rate from the
+// history's counts and dwell times (HostStream::gamma of phm_qupdate.h).  A chunk of chains runs ALL its iterations on buffers
+// allocated once; per iteration there is one upload (Q) and one download (statistics, log-likelihoods and the error word).
+// Every random number is addressed by global indices only: histories by (site * C + chain, iteration + replica_offset) as
+// phm_sample_histories_models with draws = 1 addresses them, rates by (ENT_RATE | parameter, chain, iteration + replica_offset).
+#include "phm_loglik_host.h"
+#include "phm_sample.h"
+
+#include <limits>
+
+namespace {
+
+using namespace phm_ex;
+using namespace phm_ll;
+
+const std::string GB_FN = "phm_gibbs_rates: ";
+
+struct GbInput {
+  LlInput ll;                                           // K = chains, site_of_model = site_of_chain, Qr = Q(theta0)
+  int p = 0, cols = 0, fx_exp = 0, depth = 0, rows = 0, iters = 0, thin = 1, n_prior = 1;
+  double theta_max = 0.0, t_max = 0.0;
+  std::vector<int32_t> index;                           // [n * n] row-major, 0 = structural zero (and the diagonal)
+  std::vector<int32_t> order, level_off;                // s.down positions by the depth of the parent
+  const double* theta0 = nullptr;
+  const double* prior = nullptr;
+  phm_options opt;
+  double* theta = nullptr;
+  double* loglik = nullptr;
+  double* stats = nullptr;
+  int32_t* rejected = nullptr;
+  int32_t* status = nullptr;
+};
+
+// row-major Q(theta) with stride `stride` between entries: q_ij = theta[index - 1], the diagonal minus the row's off-diagonal
+// entries summed left to right
+inline void fill_q(const GbInput& g, const double* th, double* Q, size_t stride) {
+  const int n = g.ll.n;
+  for (int i = 0; i < n; ++i) {
+    double row = 0.0;
+    for (int j = 0; j < n; ++j) {
+      if (j == i) continue;
+      const int c = g.index[(size_t)i * n + j];
+      const double q = c > 0 ? th[c - 1] : 0.0;
+      Q[(size_t)(i * n + j) * stride] = q;
+      row += q;
+    }
+    Q[(size_t)(i * n + i) * stride] = -row;
+  }
+}
+
+int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count) {
+  int32_t st = select_device(device);
+  if (st) return st;
+  const LlInput& in = g.ll;
+  const int n = in.n, E = in.E, NT = in.NT, T = in.T, cols = g.cols, np = g.p;
+  const size_t nn = (size_t)n * n;
+  const int64_t C = in.K;
+  const int64_t S_eval = in.paired ? 1 : in.S;           // sites per chain
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  KernelTimer tm;
+  double kernel_ms = 0.0, ms = 0.0;
+  using Clock = std::chrono::steady_clock;
+  const bool q_timing = g_phm_debug.q_timing != 0;      // host clock of the phases of an iteration, printed to stderr
+  double up_ms = 0.0, run_ms = 0.0, host_ms = 0.0;
+  int launches = 0;
+  auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
+  DevBuf dt, dobs, dup, ddown, dorder, derr;
+  HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dobs, in.obs)); HIPCHK(upload(dup, in.up));
+  HIPCHK(upload(ddown, in.sched.down)); HIPCHK(upload(dorder, g.order));
+  HIPCHK(derr.alloc(sizeof(uint32_t)));
+  HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
+
+  // Chunks of chains by free HBM: section 17's buffers and the table (to the depth theta_max allows) per chain, and per evaluation
+  // L, sL, ll and the sampler's lane.  Every site of a chain sits in the chunk (joint mode sums over them every iteration).
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const bool ws = n > phm::LL_REG_MAX;
+  const size_t budget = free_b / 2 > (ws ? LL_WORK : 0) ? free_b / 2 - (ws ? LL_WORK : 0) : 0;
+  const size_t per_model = sizeof(double) * ((size_t)E * nn + 2 * nn + n + 1 + ((size_t)g.depth + 1) * nn) + sizeof(uint32_t) + sizeof(int32_t);
+  const size_t per_eval = sizeof(double) * ((size_t)NT * (n + 1) + 1) + (in.paired ? (size_t)T : 0) + (size_t)NT +
+                          sizeof(double) * (cols + 1 + n) + sizeof(uint32_t) * ((size_t)n * (n - 1) + 1);
+  int64_t Kc_max = (int64_t)(budget / (per_model + per_eval * (size_t)S_eval)) / 64 * 64;
+  Kc_max = std::min<int64_t>(Kc_max, ((int64_t)1 << 22) / S_eval / 64 * 64);       // evaluations of a chunk: 32-bit offsets
+  if (Kc_max < 64) return fail(PHM_ERR_OOM, GB_FN + "64 chains with all their sites do not fit the device; run fewer sites per call");
+  const int chunk = g_phm_debug.expect_chunk;
+  if (chunk > 0) Kc_max = std::min<int64_t>(Kc_max, ((int64_t)chunk + 63) / 64 * 64);
+  Kc_max = std::min<int64_t>(Kc_max, (count + 63) / 64 * 64);
+  const size_t Kpm = (size_t)Kc_max, Evm = Kpm * (size_t)S_eval;
+  int ne_max = E;
+  if (ws) ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, LL_WORK / (sizeof(double) * 4 * nn * Kpm)}));
+  ne_max = std::min(ne_max, 65535);
+  if (chunk > 0) ne_max = std::min(ne_max, chunk);
+
+  DevBuf dQ, dpid, dP, dwork, dbad, dL, dsL, dll, dtips, dmu, dB, dbeta, ddepth, dtile, dlane, dnst, ddw, dcnt, dout;
+  HIPCHK(dQ.alloc(sizeof(double) * nn * Kpm)); HIPCHK(dpid.alloc(sizeof(double) * n * Kpm));
+  HIPCHK(dP.alloc(sizeof(double) * (size_t)E * nn * Kpm)); HIPCHK(dbad.alloc(sizeof(uint32_t) * Kpm));
+  if (ws) HIPCHK(dwork.alloc(sizeof(double) * 4 * nn * Kpm * (size_t)ne_max));
+  HIPCHK(dL.alloc(sizeof(double) * (size_t)NT * n * Evm)); HIPCHK(dsL.alloc(sizeof(double) * (size_t)NT * Evm));
+  HIPCHK(dll.alloc(sizeof(double) * Evm));
+  HIPCHK(dtips.alloc(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)S_eval));
+  HIPCHK(dmu.alloc(sizeof(double) * Kpm)); HIPCHK(dB.alloc(sizeof(double) * nn * Kpm));
+  HIPCHK(dbeta.alloc(sizeof(double) * ((size_t)g.depth + 1) * nn * Kpm)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Kpm));
+  HIPCHK(dtile.alloc(sizeof(phm::SmTile) * (Evm / 64))); HIPCHK(dlane.alloc(sizeof(uint32_t) * Evm));
+  HIPCHK(dnst.alloc((size_t)NT * Evm));
+  HIPCHK(ddw.alloc(sizeof(unsigned long long) * n * Evm)); HIPCHK(dcnt.alloc(sizeof(uint32_t) * (size_t)n * (n - 1) * Evm));
+  const size_t out_max = (size_t)(cols + 1) * Evm + 1;
+  HIPCHK(dout.alloc(sizeof(double) * out_max));
+  PinnedBuf hQ, hout;                                    // the two per-iteration copies go through page-locked memory
+  HIPCHK(hQ.reserve(sizeof(double) * nn * Kpm)); HIPCHK(hout.reserve(sizeof(double) * out_max));
+  double* Qh = hQ.as<double>();
+  const double* outh = hout.as<double>();
+  std::vector<double> pidh((size_t)n * Kpm), th((size_t)np * Kpm);
+  std::vector<uint8_t> tips_h(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)S_eval);
+  std::vector<phm::SmTile> tiles(Evm / 64);
+  std::vector<uint32_t> lane_id(Evm);
+
+  phm::SmParams sp = {};
+  phm::LlParams& p = sp.ll;
+  sp.n_node = in.Nn; sp.n_edge = E; sp.root_row = T + in.sched.root;
+  sp.seed_lo = (uint32_t)(g.opt.seed & 0xFFFFFFFFull); sp.seed_hi = (uint32_t)(g.opt.seed >> 32);
+  sp.fx_scale = std::ldexp(1.0, 61 - g.fx_exp); sp.fx_inv = std::ldexp(1.0, g.fx_exp - 61);
+  sp.tiles = dtile.as<phm::SmTile>(); sp.down = ddown.as<phm::DownStep>(); sp.order = dorder.as<int32_t>();
+  sp.mu = dmu.as<double>(); sp.B = dB.as<double>(); sp.beta = dbeta.as<double>(); sp.depth_of = ddepth.as<int32_t>();
+  sp.nstate = dnst.as<uint8_t>(); sp.dwfx = ddw.as<unsigned long long>(); sp.cnt = dcnt.as<uint32_t>();
+  sp.out = dout.as<double>(); sp.nodes = nullptr; sp.err = derr.as<uint32_t>();
+  sp.packed = 1; sp.t_max = g.t_max; sp.depth = g.depth; sp.lane_id = dlane.as<uint32_t>();
+
+  for (int64_t c0 = 0; c0 < count; c0 += Kc_max) {
+    const int64_t Kc = std::min<int64_t>(Kc_max, count - c0);
+    const int Kp = (int)((Kc + 63) / 64 * 64);
+    const int64_t m0 = first + c0;                       // global index of this chunk's first chain
+    const size_t npad = (size_t)S_eval * Kp;             // lanes of the chunk: evaluation s * Kp + k is lane s * Kp + k
+    const int nt = (int)(npad / 64);
+    std::fill(Qh, Qh + nn * Kp, 0.0);
+    std::fill(pidh.begin(), pidh.end(), 0.0);
+    for (int64_t k = 0; k < Kc; ++k) {
+      for (int i = 0; i < n; ++i) pidh[(size_t)i * Kp + k] = in.pid[(size_t)(m0 + k) * n + i];
+      std::copy_n(g.theta0 + (size_t)(m0 + k) * np, np, th.begin() + (size_t)k * np);
+      fill_q(g, &th[(size_t)k * np], Qh + k, (size_t)Kp);
+    }
+    for (int64_t s = 0; s < S_eval; ++s)
+      for (int k0 = 0; k0 < Kp; k0 += 64) {
+        phm::SmTile tl = {};
+        tl.ev = (int32_t)(s * Kp + k0); tl.k = k0; tl.n_valid = 64;
+        tiles[(size_t)(s * Kp + k0) / 64] = tl;
+        for (int l = 0; l < 64; ++l) {
+          const int64_t k = k0 + l;
+          const int64_t site = k < Kc ? (in.paired ? in.site_of_model[m0 + k] : s) : 0;
+          lane_id[(size_t)(s * Kp + k)] = k < Kc ? (uint32_t)(site * C + (m0 + k)) : phm::SM_LANE_IDLE;
+        }
+      }
+    if (in.paired) {                                     // [tip][Kp]: lane k reads the tips of its own site
+      std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);
+      for (int64_t k = 0; k < Kc; ++k) {
+        const int32_t* y = in.tips_of(in.site_of_model[m0 + k]);
+        for (int t = 0; t < T; ++t) tips_h[(size_t)t * Kp + k] = (uint8_t)y[t];
+      }
+      HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Kp, hipMemcpyHostToDevice));
+    } else {                                             // [site][tip]
+      for (int64_t s = 0; s < S_eval; ++s) {
+        const int32_t* y = in.tips_of(s);
+        for (int t = 0; t < T; ++t) tips_h[(size_t)s * T + t] = (uint8_t)y[t];
+      }
+      HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * S_eval, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(dpid.p, pidh.data(), sizeof(double) * n * Kp, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dtile.p, tiles.data(), sizeof(phm::SmTile) * nt, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dlane.p, lane_id.data(), sizeof(uint32_t) * npad, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dbad.p, 0, sizeof(uint32_t) * Kp));
+    HIPCHK(hipMemset(ddw.p, 0, sizeof(unsigned long long) * n * npad));
+    HIPCHK(hipMemset(dcnt.p, 0, sizeof(uint32_t) * (size_t)n * (n - 1) * npad));
+    p.n = n; p.n_tips = T; p.Kp = Kp; p.Kc = (int)Kc; p.paired = in.paired ? 1 : 0;
+    p.Q = dQ.as<double>(); p.pid = dpid.as<double>(); p.t = dt.as<double>(); p.P = dP.as<double>();
+    p.work = ws ? dwork.as<double>() : nullptr; p.bad = dbad.as<uint32_t>(); p.tips = dtips.as<uint8_t>();
+    p.obs = dobs.as<int32_t>(); p.L = dL.as<double>(); p.sL = dsL.as<double>(); p.ll = dll.as<double>();
+    sp.n_tiles = nt;
+    const int branch_blocks = (int)std::min<int64_t>(((int64_t)E * nt + 3) / 4, 2048);
+    const size_t out_n = (size_t)(cols + 1) * npad + 1;
+
+    // the update of chains [k_lo, k_hi) of the chunk from the iteration's download
+    auto update = [&](int iter, int64_t k_lo, int64_t k_hi) {
+      const bool rec = iter % g.thin == 0;
+      const int64_t r = iter / g.thin;
+      const uint32_t rep = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
+      for (int64_t k = k_lo; k < k_hi; ++k) {
+        const int64_t ch = m0 + k;
+        double* thk = &th[(size_t)k * np];
+        double ll = 0.0;
+        for (int64_t s = 0; s < S_eval; ++s) ll += outh[(size_t)cols * npad + (size_t)(s * Kp + k)];
+        if (!g.status[ch] && !std::isfinite(ll)) g.status[ch] = 1;
+        double* th_row = g.theta + ((size_t)r * C + ch) * np;
+        double* st_row = g.stats ? g.stats + ((size_t)r * C + ch) * cols : nullptr;
+        if (g.status[ch]) {                              // an impossible chain: NaN from here on, its lanes idle on the device
+          if (rec) {
+            std::fill_n(th_row, np, nan);
+            g.loglik[(size_t)r * C + ch] = nan;
+            if (st_row) std::fill_n(st_row, cols, nan);
+          }
+          continue;
+        }
+        if (rec) {
+          std::copy_n(thk, np, th_row);
+          g.loglik[(size_t)r * C + ch] = ll;
+          if (st_row)
+            for (int c = 0; c < cols; ++c) {
+              double v = 0.0;
+              for (int64_t s = 0; s < S_eval; ++s) v += outh[(size_t)c * npad + (size_t)(s * Kp + k)];
+              st_row[c] = v;
+            }
+        }
+        const double* pr = g.prior + (g.n_prior > 1 ? (size_t)ch * np * 2 : 0);
+        for (int c = 0; c < np; ++c) {
+          double Nc = 0.0, Wc = 0.0;                     // W_c: sites ascending, within a site the entries in row-major order
+          for (int64_t s = 0; s < S_eval; ++s) {
+            const size_t ln = (size_t)(s * Kp + k);
+            for (int i = 0; i < n; ++i)
+              for (int j = 0; j < n; ++j) {
+                if (g.index[(size_t)i * n + j] != c + 1) continue;
+                Nc += outh[(size_t)(n + i * (n - 1) + (j > i ? j - 1 : j)) * npad + ln];
+                Wc += outh[(size_t)i * npad + ln];
+              }
+          }
+          phm::HostStream rs{g.opt.seed, phm::ENT_RATE | (uint32_t)c, (uint32_t)ch, rep};
+          const double fresh = rs.gamma(pr[2 * c] + Nc, 1 / (pr[2 * c + 1] + Wc));
+          if (fresh > g.theta_max || !(fresh > 0.0)) ++g.rejected[(size_t)ch * np + c];   // the old value stays
+          else thk[c] = fresh;
+        }
+        fill_q(g, thk, Qh + k, (size_t)Kp);
+      }
+    };
+    const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>(16, Kc * np / 4096));
+
+    for (int iter = 0; iter < g.iters; ++iter) {
+      sp.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
+      Clock::time_point t0 = Clock::now();
+      HIPCHK(hipMemcpy(dQ.p, Qh, sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
+      up_ms += since(t0);
+      t0 = Clock::now();
+      HIPCHK(tm.start());
+      p.n_sites = 1;
+      for (int e0 = 0; e0 < E; e0 += ne_max) HIPCHK(phm::launch_ll_expm(p, e0, std::min(ne_max, E - e0), nullptr));
+      HIPCHK(phm::launch_sm_table(sp, nullptr));
+      p.n_sites = (int)S_eval;
+      HIPCHK(phm::launch_ll_tips(p, nullptr));
+      for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
+        HIPCHK(phm::launch_ll_up(p, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
+      HIPCHK(phm::launch_ll_root(p, sp.root_row, nullptr));
+      HIPCHK(phm::launch_sm_sample(sp, g.level_off, branch_blocks, phm::MAPS_OFF, nullptr));
+      HIPCHK(tm.stop());
+      HIPCHK(hipMemcpy(hout.p, dout.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
+      HIPCHK(tm.elapsed(ms));
+      kernel_ms += ms;
+      run_ms += since(t0);
+      t0 = Clock::now();
+      const uint32_t derrh = (uint32_t)outh[out_n - 1];
+      if (derrh & phm::DERR_CAPACITY) return fail(PHM_ERR_CAPACITY, GB_FN + "a chain's jump-count series outgrew the table theta_max allows");
+      const int32_t ds = device_status(derrh);
+      if (ds) return ds;
+      if (n_threads <= 1) {
+        update(iter, 0, Kc);
+      } else {
+        std::vector<std::thread> pool;
+        for (int t = 1; t < n_threads; ++t) pool.emplace_back(update, iter, Kc * t / n_threads, Kc * (t + 1) / n_threads);
+        update(iter, 0, Kc / n_threads);
+        for (std::thread& t : pool) t.join();
+      }
+      host_ms += since(t0);
+    }
+    int levels = 0;
+    for (size_t l = 0; l + 1 < g.level_off.size(); ++l) levels += g.level_off[l + 1] > g.level_off[l] ? 1 : 0;
+    launches = (E + ne_max - 1) / ne_max + 3 + (int)in.up_off.size() - 1 + 3 + levels;   // P, table, tips, up levels, root | root, node levels, branch, finish
+  }
+  if (q_timing)
+    std::fprintf(stderr, "phm_gibbs_rates: device %d, chains %lld, per iteration: upload of Q %.4f ms, launches + device + download %.4f ms "
+                 "(device %.4f ms), host update %.4f ms on %d thread(s); %d launches per iteration\n", (int)device, (long long)count,
+                 up_ms / g.iters, run_ms / g.iters, kernel_ms / g.iters, host_ms / g.iters,
+                 (int)std::max<int64_t>(1, std::min<int64_t>(16, std::min<int64_t>(Kc_max, count) * np / 4096)), launches);
+  g_phm_last_kernel_ms = kernel_ms;
+  return PHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Chains are independent and every random number is addressed by global indices: with phm_options.n_devices > 1 device d runs a
+// contiguous range of the chains (phm_plan_shards, run_shards), and every output is the one-device output bit for bit.
+int32_t phm_gibbs_rates(const phm_tree* x, int32_t n_states, const int32_t* index, int32_t n_params, int32_t n_chains,
+                        const double* theta0, const double* prior, int32_t n_prior, double theta_max, const double* pid,
+                        int32_t n_pid, const int32_t* observe, const int32_t* site_of_chain, int32_t iters, int32_t thin,
+                        const phm_options* opt, double* theta, double* loglik, double* stats, int32_t* rejected,
+                        int32_t* chain_status) {
+  const phm_options o = resolve_options(opt);
+  if (!x || !index || !theta0 || !prior || !pid || !theta || !loglik || !rejected || !chain_status)
+    return fail(PHM_ERR_BAD_INPUT, GB_FN + "NULL argument (only observe, site_of_chain, opt and stats may be NULL)");
+  const int n = n_states;
+  if (n < 2) return fail(PHM_ERR_BAD_INPUT, GB_FN + "n_states must be in 2..8");
+  if (n > phm::LL_LANE_MAX) return fail(PHM_ERR_UNSUPPORTED, GB_FN + "more than 8 states are not supported");
+  if (n_chains < 1) return fail(PHM_ERR_BAD_INPUT, GB_FN + "n_chains must be >= 1");
+  if (n_params < 1 || n_params > n * (n - 1)) return fail(PHM_ERR_BAD_INPUT, GB_FN + "n_params must be in 1..n(n-1)");
+  if (iters < 1) return fail(PHM_ERR_BAD_INPUT, GB_FN + "iters must be >= 1");
+  if (thin < 1) return fail(PHM_ERR_BAD_INPUT, GB_FN + "thin must be >= 1");
+  if (n_prior != 1 && n_prior != n_chains) return fail(PHM_ERR_BAD_INPUT, GB_FN + "n_prior must be 1 (shared) or n_chains");
+  if (!(theta_max > 0.0) || !std::isfinite(theta_max)) return fail(PHM_ERR_BAD_INPUT, GB_FN + "theta_max must be positive and finite");
+  GbInput g;
+  g.p = n_params; g.iters = iters; g.thin = thin; g.n_prior = n_prior; g.theta_max = theta_max;
+  g.rows = (iters + thin - 1) / thin;
+  g.index.assign((size_t)n * n, 0);
+  std::vector<int> owned(n_params, 0);
+  int row_max = 0;
+  for (int i = 0; i < n; ++i) {
+    int in_row = 0;
+    for (int j = 0; j < n; ++j) {
+      const int32_t c = i == j ? 0 : index[i + (size_t)j * n];                // column-major in, the diagonal is ignored
+      if (c > n_params) return fail(PHM_ERR_BAD_INPUT, GB_FN + "index: entry (" + std::to_string(i + 1) + ", " + std::to_string(j + 1) + ") names parameter " + std::to_string(c) + " of " + std::to_string(n_params));
+      if (c > 0) { g.index[(size_t)i * n + j] = c; ++owned[c - 1]; ++in_row; }
+    }
+    row_max = std::max(row_max, in_row);
+  }
+  for (int c = 0; c < n_params; ++c)
+    if (!owned[c]) return fail(PHM_ERR_BAD_INPUT, GB_FN + "index: parameter " + std::to_string(c + 1) + " owns no entry (parameters are numbered 1..p without gaps)");
+  for (int64_t k = 0; k < (int64_t)n_prior; ++k)
+    for (int c = 0; c < n_params; ++c) {
+      const double a = prior[((size_t)k * n_params + c) * 2], b = prior[((size_t)k * n_params + c) * 2 + 1];
+      if (!(a > 0.0) || !(b > 0.0) || !std::isfinite(a) || !std::isfinite(b))
+        return fail(PHM_ERR_BAD_INPUT, GB_FN + "prior: shape and rate of parameter " + std::to_string(c + 1) + " (prior row " + std::to_string(k) + ") must be positive and finite");
+    }
+  for (int64_t k = 0; k < n_chains; ++k)
+    for (int c = 0; c < n_params; ++c) {
+      const double v = theta0[(size_t)k * n_params + c];
+      if (!(v > 0.0) || !(v <= theta_max))
+        return fail(PHM_ERR_BAD_INPUT, GB_FN + "theta0 of chain " + std::to_string(k) + ", parameter " + std::to_string(c + 1) + " must be in (0, theta_max]");
+    }
+  const int S = std::max(1, (int)o.n_replicas);
+  if (site_of_chain)
+    for (int64_t k = 0; k < n_chains; ++k)
+      if (site_of_chain[k] < 0 || site_of_chain[k] >= S)
+        return fail(PHM_ERR_BAD_INPUT, GB_FN + "site_of_chain[" + std::to_string(k) + "]: the site of chain " + std::to_string(k) + " must be in 0..S-1");
+  if ((int64_t)S * n_chains > (int64_t)INT32_MAX) return fail(PHM_ERR_BAD_INPUT, GB_FN + "sites * chains must fit in 31 bits (evaluation ids)");
+  if (!site_of_chain && S > 65535) return fail(PHM_ERR_UNSUPPORTED, GB_FN + "more than 65535 sites per chain (joint mode)");
+
+  // ll_validate on Q(theta0): the tree, the root priors, the tips, observe and the options
+  const size_t nn = (size_t)n * n;
+  std::vector<double> Q0((size_t)n_chains * nn), qr(nn);
+  g.ll.n = n;
+  for (int64_t k = 0; k < n_chains; ++k) {
+    fill_q(g, theta0 + (size_t)k * n_params, qr.data(), 1);
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) Q0[(size_t)k * nn + i + (size_t)j * n] = qr[(size_t)i * n + j];
+  }
+  int32_t st = ll_validate(GB_FN, x, n, n_chains, Q0.data(), pid, n_pid, observe, site_of_chain, o, g.ll);
+  if (st) return st;
+  const LlInput& in = g.ll;
+  double tree_len = 0.0;
+  for (int b = 0; b < in.E; ++b) { g.t_max = std::max(g.t_max, in.edge_length[b]); tree_len += in.edge_length[b]; }
+  // theta_max bounds every chain's uniformization rate for the whole run: the table is allocated once, to the depth it allows
+  const double x_max = ((double)row_max * theta_max) * g.t_max;
+  if (x_max > phm::SM_MAX_JUMP_MEAN)
+    return fail(PHM_ERR_UNSUPPORTED, GB_FN + "theta_max: (largest number of rates in a row = " + std::to_string(row_max) +
+                                         ") * theta_max * (longest branch) is above 32768; lower theta_max");
+  g.depth = phm::sm_stop_index(x_max);
+  (void)std::frexp(std::max(tree_len, 1.0), &g.fx_exp);
+  g.cols = n + n * (n - 1);
+  phm::depth_levels(in.sched, g.order, g.level_off);
+  g.theta0 = theta0; g.prior = prior; g.opt = o;
+  g.theta = theta; g.loglik = loglik; g.stats = stats; g.rejected = rejected; g.status = chain_status;
+  std::fill_n(rejected, (size_t)n_chains * n_params, 0);
+  std::fill_n(chain_status, (size_t)n_chains, 0);
+
+  std::vector<phm_shard> shards;
+  st = phm_plan_shards(o, in.K, shards);
+  if (st) return st;
+  return run_shards(shards, [&](const phm_shard& sh, size_t) { return gb_device(g, sh.device, sh.first, sh.count); });
+}
+
+}  // extern "C"

@@ -17,39 +17,8 @@ namespace phm {
 
 namespace {
 
-void philox_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
-  for (int r = 0; r < 7; ++r) {      // Philox4x32-7, as every stream of the engine (phm_device.h)
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-struct UpdateStream {
-  uint64_t seed;
-  uint32_t iter, id, next = 0;
-  double uniform() {
-    uint32_t o[4];
-    const uint32_t d = next++;
-    philox_host(d >> 2, 0xFFFFFF00u | id, iter, 0xFFFFFFFFu, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), o);
-    return ((double)o[d & 3u] + 0.5) * 2.3283064365386962890625e-10;      // draw d = word d & 3 of block d >> 2, (x + 0.5) 2^-32
-  }
-  double gamma(double shape, double scale) {
-    double boost = 1.0;
-    if (shape < 1.0) { const double u = uniform(); boost = std::pow(u, 1.0 / shape); shape += 1.0; }
-    const double d = shape - 1.0 / 3.0, c = 1.0 / std::sqrt(9.0 * d);
-    for (;;) {
-      const double u1 = uniform(), u2 = uniform();
-      const double z = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2);
-      double v = 1.0 + c * z;
-      if (v <= 0.0) continue;
-      v = v * v * v;
-      const double u = uniform();
-      if (std::log(u) < 0.5 * z * z + d - d * v + d * std::log(v)) return d * v * boost * scale;
-    }
-  }
+struct UpdateStream : HostStream {
+  UpdateStream(uint64_t seed, uint32_t iter, uint32_t id) : HostStream{seed, 0xFFFFFF00u | id, iter, 0xFFFFFFFFu} {}
 };
 
 // View of one statistics row (device column order: n dwell sums, n*n counts row-major) and of the column-major Q

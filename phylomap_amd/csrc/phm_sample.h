@@ -17,7 +17,11 @@ constexpr int SM_BLOCK = 256;
 constexpr double SM_MAX_JUMP_MEAN = 32768.0;   // max(-q_ii) t_b: bounds the loops, the table and a row's uint16 segment count
 constexpr int SM_M_CAP = 1 << 17;              // hard end of the stopping rule's loop (M(32768) is about 34 000)
 
+constexpr uint32_t SM_LANE_IDLE = 0xFFFFFFFFu;  // packed form: lane_id of a lane without a chain (evaluation ids keep to 31 bits)
+
 // A tile: 64 consecutive draws of ONE evaluation (lane = draw d0 + lane; lanes >= n_valid idle).
+// Packed form (SmParams.packed, section 20): 64 consecutive chains of one site, ONE draw each: lane's evaluation is ev + lane, its
+// model k + lane, its evaluation id lane_id[tile * 64 + lane]; d0 = 0 and n_valid, row0 are not read.
 struct SmTile {
   int32_t ev;            // evaluation in section 17's buffers of this launch: site_local * Kp + k
   int32_t k;             // model in the chunk (lane of the per-model buffers)
@@ -49,7 +53,10 @@ struct SmParams {
   int32_t n_node, n_edge, root_row;            // root_row: n_tips + internal index of the root
   int32_t n_tiles;
   int32_t depth;                               // rows of beta: m = 0 .. depth
-  const int32_t* depth_of;                     // [Kp] every model's own depth M(mu_k max_b t_b) <= depth
+  int32_t* depth_of;                           // [Kp] every model's own depth M(mu_k max_b t_b) <= depth (packed: written by the table kernel)
+  int32_t packed;                              // 1: lane = chain (phm_gibbs_rates); a lane whose ll is not finite, or whose id is SM_LANE_IDLE, idles
+  double t_max;                                // packed: max_b t_b, from which the table kernel takes depth_of (DERR_CAPACITY above depth)
+  const uint32_t* lane_id;                     // packed: [n_tiles * 64] GLOBAL evaluation ids
   int64_t map_pad;                             // MAPS_COUNT: row length of maps.seg_cnt (histories of the shard, padded)
   uint32_t seed_lo, seed_hi, replica;          // replica: phm_options.replica_offset, added to the draw index
   double fx_scale, fx_inv;                     // fixed-point scale of the dwell accumulators (powers of two)
@@ -62,7 +69,7 @@ struct SmParams {
   uint8_t* nstate;                             // [tile][n_tips + n_node][64] 0-based states by ape row
   unsigned long long* dwfx;                    // [n][n_tiles * 64] dwell sums, fixed point
   uint32_t* cnt;                               // [n (n-1)][n_tiles * 64]
-  double* out;                                 // [cols][n_tiles * 64]
+  double* out;                                 // [cols][n_tiles * 64]; packed: one more column (the lanes' ll) and one more value, the error word
   int32_t* nodes;                              // NULL or [n_tiles * 64][n_tips + n_node] 1-based states
   uint32_t* err;
   MapsDev maps;
@@ -70,7 +77,8 @@ struct SmParams {
 
 // mu, B and beta of the models of the chunk (a lane owns a model), each to its own depth
 hipError_t launch_sm_table(const SmParams& p, hipStream_t stream);
-// root, node levels, branches and the finish of the tiles of p; level_off: boundaries of the depth levels in p.order (host)
+// root, node levels, branches and the finish of the tiles of p (packed: maps_mode MAPS_OFF only; the finish also clears the
+// accumulators for the next iteration); level_off: boundaries of the depth levels in p.order (host)
 hipError_t launch_sm_sample(const SmParams& p, const std::vector<int32_t>& level_off, int branch_blocks, int maps_mode,
                             hipStream_t stream);
 

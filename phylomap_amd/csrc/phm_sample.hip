@@ -17,6 +17,11 @@
 //   states       x_i drawn with weights B[x_{i-1}, c] beta_{N-i}[c]; equal neighbours merge.
 // Draw d of a branch stream: 0 the jump count, 1 .. N + 1 the exponentials, N + 1 + i the state x_i.
 // Segments, counts and dwell sums are exp_tiles_branch_kernel's (64-bit fixed point; maps modes of phm_maps.h).
+//
+// Packed form (PACKED = true, DESIGN.md section 20, behind phm_gibbs_rates): one draw per evaluation, so lane = chain.  A tile is 64
+// consecutive chains of one site; the model, the evaluation, its id, mu, the table depth and the beta column are per lane
+// (sm_lane); the buffers are model-fastest, so lanes that agree on (a, e) still load coalesced rows.  Same draws, same
+// arithmetic: lane l of a packed tile computes what lane 0 of the unpacked tile of its evaluation computes.
 #include "phm_sample.h"
 
 #include <algorithm>
@@ -42,7 +47,14 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_table_kernel(SmParams p) {
       p.B[(size_t)(i * n + j) * Kp + k] = mu > 0.0 ? d + q.Q[(size_t)(i * n + j) * Kp + k] / mu : d;
       p.beta[(size_t)(i * n + j) * Kp + k] = d;
     }
-  const int depth = min(p.depth_of[k], p.depth);
+  int depth;
+  if (p.packed) {                                                   // the chain's own depth, from the rates it has now
+    depth = sm_stop_index(mu * p.t_max);
+    if (depth > p.depth) { atomicOr(p.err, DERR_CAPACITY); depth = p.depth; }
+    p.depth_of[k] = depth;
+  } else {
+    depth = min(p.depth_of[k], p.depth);
+  }
   for (int m = 0; m < depth; ++m) {                                 // beta_{m+1} = B beta_m, unfused left-to-right sums
     const double* __restrict__ prev = p.beta + (size_t)m * nn * Kp + k;
     double* __restrict__ next = p.beta + (size_t)(m + 1) * nn * Kp + k;
@@ -87,6 +99,32 @@ __device__ __forceinline__ int sm_draw_n(const double* a, size_t sa, const doubl
   }
 }
 
+// what a lane works on: wave-uniform in the tile form, its own chain in the packed form
+struct SmLane {
+  int k, ev;
+  uint32_t eval_id, rep;
+  bool valid;
+};
+template <bool PACKED>
+__device__ __forceinline__ SmLane sm_lane(const SmParams& p, const SmTile& tl, int tile, int lane) {
+  SmLane l;
+  if constexpr (PACKED) {
+    l.k = tl.k + lane;
+    l.ev = tl.ev + lane;
+    l.eval_id = p.lane_id[(size_t)tile * 64 + lane];
+    l.rep = p.replica;
+    l.valid = l.eval_id != SM_LANE_IDLE && isfinite(p.ll.ll[l.ev]);
+  } else {
+    l.k = tl.k;
+    l.ev = tl.ev;
+    l.eval_id = tl.eval_id;
+    l.rep = (uint32_t)(tl.d0 + lane) + p.replica;
+    l.valid = lane < tl.n_valid;
+  }
+  return l;
+}
+
+template <bool PACKED>
 __global__ __launch_bounds__(SM_BLOCK) void sm_root_kernel(SmParams p) {
   const LlParams& q = p.ll;
   const int lane = threadIdx.x & 63;
@@ -95,14 +133,19 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_root_kernel(SmParams p) {
   const SmTile tl = p.tiles[tile];
   const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp;
   const int NT = q.n_tips + p.n_node;
+  const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
   uint32_t err = 0;
-  const double u = stream_u(p.seed_lo, p.seed_hi, (uint32_t)(tl.d0 + lane) + p.replica, tl.eval_id, ENT_NODE | (uint32_t)p.root_row, 0);
-  const int s = sm_draw_n<0>(q.pid + tl.k, Kp, q.L + (size_t)p.root_row * q.n * Ev + tl.ev, Ev, q.n, u, err);
+  int s = 0;
+  if (!PACKED || l.valid) {
+    const double u = stream_u(p.seed_lo, p.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)p.root_row, 0);
+    s = sm_draw_n<0>(q.pid + l.k, Kp, q.L + (size_t)p.root_row * q.n * Ev + l.ev, Ev, q.n, u, err);
+  }
   p.nstate[((size_t)tile * NT + p.root_row) * 64 + lane] = (uint8_t)s;
-  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+  if (err && l.valid) atomicOr(p.err, err);
 }
 
 // one depth level: a wave per (tile, edge of the level) draws the child's state, tips included
+template <bool PACKED>
 __global__ __launch_bounds__(SM_BLOCK) void sm_node_kernel(SmParams p, int begin, int end) {
   const LlParams& q = p.ll;
   const int lane = threadIdx.x & 63;
@@ -118,15 +161,19 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_node_kernel(SmParams p, int begin
   const int crow = ds.child >= 0 ? q.n_tips + ds.child : ~ds.child;
   uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
   const int a = nst[(q.n_tips + ds.parent) * 64 + lane];
+  const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
   uint32_t err = 0;
-  const double u = stream_u(p.seed_lo, p.seed_hi, (uint32_t)(tl.d0 + lane) + p.replica, tl.eval_id, ENT_NODE | (uint32_t)crow, 0);
-  const int e = sm_draw_n<0>(q.P + ((size_t)ds.edge * n * n + (size_t)a * n) * Kp + tl.k, Kp, q.L + (size_t)crow * n * Ev + tl.ev, Ev, n, u, err);
+  int e = 0;
+  if (!PACKED || l.valid) {
+    const double u = stream_u(p.seed_lo, p.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)crow, 0);
+    e = sm_draw_n<0>(q.P + ((size_t)ds.edge * n * n + (size_t)a * n) * Kp + l.k, Kp, q.L + (size_t)crow * n * Ev + l.ev, Ev, n, u, err);
+  }
   nst[crow * 64 + lane] = (uint8_t)e;
-  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+  if (err && l.valid) atomicOr(p.err, err);
 }
 
 // persistent waves over (tile, group of `group` consecutive branches in pre-order)
-template <int NS, int MODE>
+template <int NS, int MODE, bool PACKED = false>
 __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int group) {
   __shared__ __align__(16) double s_ltab[2 * PHM_LOGTAB_N];        // (1/c_j, log c_j) of the exponential variates (neglog_u32)
   for (int i = threadIdx.x; i < 2 * PHM_LOGTAB_N; i += SM_BLOCK) s_ltab[i] = logtab_entry(i);
@@ -148,13 +195,14 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
     const int q0 = (int)(item / p.n_tiles) * group, q1 = min(q0 + group, p.n_edge);
     const SmTile tl = p.tiles[tile];
     const size_t it = (size_t)tile * 64 + lane;
-    const bool valid = lane < tl.n_valid;
+    const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
+    const bool valid = l.valid;
     const uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
-    const double mu = p.mu[tl.k];
-    const int depth = min(p.depth_of[tl.k], p.depth);
-    const double* __restrict__ Bk = p.B + tl.k;
-    const double* __restrict__ bt = p.beta + tl.k;
-    const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+    const double mu = p.mu[l.k];
+    const int depth = min(p.depth_of[l.k], p.depth);
+    const double* __restrict__ Bk = p.B + l.k;
+    const double* __restrict__ bt = p.beta + l.k;
+    const uint32_t rep = l.rep;
     unsigned long long acc_dw[NA];
     uint32_t acc_ct[NC];
 #pragma unroll
@@ -194,7 +242,7 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
         }
         if constexpr (MODE != MAPS_OFF) ++cur;
       };
-      const double x = mu * tb;
+      const double x = (!PACKED || valid) ? mu * tb : 0.0;         // packed: a lane without a live chain walks no series
       int N = 0;
       if (x > 0.0) {
         const double* __restrict__ ba = bt + (size_t)(a * n + e) * Kp;       // beta_m[a] at ba[m nn Kp]
@@ -213,7 +261,7 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
         }
         if (!(Sa > 0.0) || isinf(Sa)) err |= DERR_ZERO_PROB;
         Stream sr;
-        sr.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
+        sr.open(ENT_BUNIF | (uint32_t)b, l.eval_id, rep, p.seed_lo, p.seed_hi);
         const double thr = sr.draw(0) * Sa;
         // second pass: the first m whose partial sum reaches the threshold
         double cum = ba[0];
@@ -233,7 +281,7 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
           double G = 0.0;
           for (int i = 1; i <= N + 1; ++i) G += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
           Stream su;
-          su.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
+          su.open(ENT_BUNIF | (uint32_t)b, l.eval_id, rep, p.seed_lo, p.seed_hi);
           int prev = a, sprev = a;
           double tprev = 0.0, c = 0.0;
           for (int i = 1; i <= N; ++i) {
@@ -284,6 +332,14 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(SmParams p) {
     const int c = (int)(gid / npad);
     const int64_t it = gid % npad;
     p.out[gid] = c < n ? (double)(long long)p.dwfx[(size_t)c * npad + it] * p.fx_inv : (double)p.cnt[(size_t)(c - n) * npad + it];
+    if (p.packed) {                                                  // the next iteration accumulates from zero
+      if (c < n) p.dwfx[(size_t)c * npad + it] = 0ull;
+      else p.cnt[(size_t)(c - n) * npad + it] = 0u;
+    }
+  }
+  if (p.packed) {                                                    // one download per iteration: the lanes' ll and the error word ride along
+    if (gid < npad) p.out[(int64_t)cols * npad + gid] = p.ll.ll[p.tiles[gid >> 6].ev + (int)(gid & 63)];
+    if (gid == 0) p.out[(int64_t)(cols + 1) * npad] = (double)*p.err;
   }
   if (p.nodes) {
     for (int64_t cell = gid; cell < npad * NT; cell += (int64_t)gridDim.x * blockDim.x) {
@@ -294,13 +350,13 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(SmParams p) {
   }
 }
 
-template <int MODE>
+template <int MODE, bool PACKED = false>
 void launch_branch(const SmParams& p, int blocks, int group, hipStream_t stream) {
   switch (p.ll.n) {
-    case 2: hipLaunchKernelGGL((sm_branch_kernel<2, MODE>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    case 3: hipLaunchKernelGGL((sm_branch_kernel<3, MODE>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    case 4: hipLaunchKernelGGL((sm_branch_kernel<4, MODE>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    default: hipLaunchKernelGGL((sm_branch_kernel<0, MODE>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
+    case 2: hipLaunchKernelGGL((sm_branch_kernel<2, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
+    case 3: hipLaunchKernelGGL((sm_branch_kernel<3, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
+    case 4: hipLaunchKernelGGL((sm_branch_kernel<4, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
+    default: hipLaunchKernelGGL((sm_branch_kernel<0, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
   }
 }
 
@@ -315,17 +371,22 @@ hipError_t launch_sm_table(const SmParams& p, hipStream_t stream) {
 hipError_t launch_sm_sample(const SmParams& p, const std::vector<int32_t>& level_off, int branch_blocks, int maps_mode,
                             hipStream_t stream) {
   if (p.ll.n < 2 || p.ll.n > LL_LANE_MAX || p.n_tiles <= 0 || branch_blocks <= 0) return hipErrorInvalidValue;
+  if (p.packed && (maps_mode != MAPS_OFF || !p.lane_id || p.nodes)) return hipErrorInvalidValue;
   constexpr int W = SM_BLOCK / 64;
-  hipLaunchKernelGGL(sm_root_kernel, dim3((p.n_tiles + W - 1) / W), dim3(SM_BLOCK), 0, stream, p);
+  const dim3 root_grid((p.n_tiles + W - 1) / W);
+  if (p.packed) hipLaunchKernelGGL(sm_root_kernel<true>, root_grid, dim3(SM_BLOCK), 0, stream, p);
+  else hipLaunchKernelGGL(sm_root_kernel<false>, root_grid, dim3(SM_BLOCK), 0, stream, p);
   for (size_t l = 0; l + 1 < level_off.size(); ++l) {
     const int64_t cnt = level_off[l + 1] - level_off[l];
-    if (cnt > 0)
-      hipLaunchKernelGGL(sm_node_kernel, dim3((unsigned)((cnt * p.n_tiles + W - 1) / W)), dim3(SM_BLOCK), 0, stream, p, level_off[l],
-                         level_off[l + 1]);
+    if (cnt <= 0) continue;
+    const dim3 grid((unsigned)((cnt * p.n_tiles + W - 1) / W));
+    if (p.packed) hipLaunchKernelGGL(sm_node_kernel<true>, grid, dim3(SM_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
+    else hipLaunchKernelGGL(sm_node_kernel<false>, grid, dim3(SM_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
   }
   // branches per wave-item: as many as still leave every SIMD a few waves
   const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.n_edge * p.n_tiles / 8192));
-  if (maps_mode == MAPS_COUNT) launch_branch<MAPS_COUNT>(p, branch_blocks, group, stream);
+  if (p.packed) launch_branch<MAPS_OFF, true>(p, branch_blocks, group, stream);
+  else if (maps_mode == MAPS_COUNT) launch_branch<MAPS_COUNT>(p, branch_blocks, group, stream);
   else if (maps_mode == MAPS_WRITE) launch_branch<MAPS_WRITE>(p, branch_blocks, group, stream);
   else launch_branch<MAPS_OFF>(p, branch_blocks, group, stream);
   const int n = p.ll.n;
