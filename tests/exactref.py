@@ -121,6 +121,26 @@ def passes(edge, edge_length, Q, pid, states, observe=None, P=None):
     return dict(L=L, sL=sL, O=O, sO=sO, F=F, sF=sF, P=P, loglik=loglik, lam=lam, root=root, order=order)
 
 
+def transition_unif(Q, t):
+    """P(t) = sum_m pois(m; mu t) B^m, B = I + Q / mu, mu = max_i(-q_ii): every term is non-negative, so nothing cancels, and no
+    Pade enters.  Truncated where the omitted Poisson mass is <= 2^-60 (``poisson_weights``).  ``passes(..., P=...)`` takes a
+    stack of these in place of scipy's expm."""
+    Q = np.asarray(Q, dtype=np.float64)
+    n = Q.shape[0]
+    mu = float(np.max(-np.diag(Q)))
+    if mu <= 0.0 or float(t) <= 0.0:
+        return np.eye(n)
+    B = np.eye(n) + Q / mu
+    p, M = poisson_weights(mu * float(t))
+    P = np.zeros((n, n))
+    Bm = np.eye(n)
+    for m in range(M + 2):
+        if p[m] > 0.0:
+            P += p[m] * Bm
+        Bm = Bm @ B
+    return P
+
+
 def integral_unif(Q, t, F, Lc):
     """I[s, i, j] by uniformization (module docstring), F, Lc [S, n]."""
     Q = np.asarray(Q, dtype=np.float64)

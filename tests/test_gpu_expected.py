@@ -45,11 +45,17 @@ def _close(got, want, rtol, atol):
     assert np.all(err <= rtol * np.abs(want) + atol), (err.max(), np.max(err / np.maximum(np.abs(want), 1e-300)))
 
 
-def _check(z, Q, pid, tips, observe=None, route="unif", rtol=1e-12):
+def _check(z, Q, pid, tips, observe=None, route="unif", rtol=1e-12, what=None):
     st, ll, br, post = api.expected_sumstat(z, Q, pid, sites=tips, observe=observe, per_branch=True, nodes=True)
     ws, wl, wb, wp = exactref.expected(z["edge"], z["edge.length"], Q, pid, tips, observe=observe, route=route,
                                        per_branch=True, nodes=True)
     floor = 1e-14 * float(np.sum(z["edge.length"])) if route == "unif" else rtol * float(np.sum(z["edge.length"]))
+    if what is not None:                                   # the figures first: a failing bar is then seen with its size
+        with np.errstate(divide="ignore", invalid="ignore"):
+            over = [np.nanmax(np.where(g == w, 0.0, np.abs(g - w) / (rtol * np.abs(w) + a)))
+                    for g, w, a in ((st, ws, floor), (br, wb, floor), (ll, wl, 0.0))]
+        print(f"{what}: error / allowance: totals {over[0]:.3g}, per branch {over[1]:.3g}, loglik {over[2]:.3g}, "
+              f"node posteriors {np.max(np.abs(post - wp)) / (1e-13 if route == 'unif' else rtol):.3g}")
     _close(st, ws, rtol, floor)
     _close(br, wb, rtol, floor)
     _close(ll, wl, rtol, 0.0)

@@ -23,7 +23,8 @@ KEYS = ("theta", "loglik", "stats", "rejected", "status")
 
 
 def model_of(n):
-    return {2: ratemodel.ard(2), 3: ratemodel.sym(3), 4: ratemodel.index_model(HIDDEN_INDEX), 8: ratemodel.er(8)}[n]
+    return {2: ratemodel.ard(2), 3: ratemodel.sym(3), 4: ratemodel.index_model(HIDDEN_INDEX), 8: ratemodel.er(8),
+            5: ratemodel.sym(5), 6: ratemodel.er(6), 7: ratemodel.ard(7)}[n]
 
 
 @functools.lru_cache(maxsize=None)

@@ -790,7 +790,7 @@ def test_expm_routes(n):
     np.testing.assert_allclose(P1, P2, atol=1e-10)
 
 
-@pytest.mark.parametrize("n", [20, 61, 64])
+@pytest.mark.parametrize("n", [17, 20, 32, 33, 48, 61, 64])
 def test_expm_eigen_on_matrix_cores(n):
     """K1 as an MFMA f64 batched GEMM: agrees with the exact kernel to rounding, with scipy to 1e-10, and is
     bit-for-bit a k-ordered fma chain (oracle model orc_matexp_fma)."""
@@ -810,7 +810,7 @@ def test_expm_eigen_on_matrix_cores(n):
         assert np.array_equal(P_mfma[b], model), np.abs(P_mfma[b] - model).max()
 
 
-@pytest.mark.parametrize("n", [20, 61, 64])
+@pytest.mark.parametrize("n", [17, 20, 32, 33, 48, 61, 64])
 def test_expm_pade_on_matrix_cores(n):
     from scipy.linalg import expm
     Q = synth.config_Q(5) if n == 20 else synth.dense_Q(n, 0.005, 0.015, seed=n)
