@@ -484,14 +484,16 @@ void fill_narrow_params(phm_engine* e, phm::NarrowParams<NS>& p, const phm_optio
 }
 
 // Level schedules shared by the branch-parallel mappings: positions of up[] grouped by HEIGHT and of down[] grouped by DEPTH
-// (phm_sched.h); uploads the two order arrays, leaves the level boundaries in the engine.
+// (phm_sched.h), and of up[] grouped by the DEPTH of the node (the node draws of phm_tiles.hip: an item per internal node); uploads
+// the order arrays, leaves the level boundaries in the engine.
 int32_t build_level_orders(phm_engine* e) {
   const phm::Schedule& s = e->sched;
   const int E = s.n_edge;
-  std::vector<int32_t> up_order, down_order;
+  std::vector<int32_t> up_order, down_order, node_order;
   phm::height_levels(s.up, up_order, e->nw_up_off);
   phm::depth_levels(s, down_order, e->nw_down_off);
-  HIPCHK(upload(e->d_nw_up_order, up_order)); HIPCHK(upload(e->d_nw_down_order, down_order));
+  phm::node_depth_levels(s, node_order, e->nw_node_off);
+  HIPCHK(upload(e->d_nw_up_order, up_order)); HIPCHK(upload(e->d_nw_down_order, down_order)); HIPCHK(upload(e->d_nw_node_order, node_order));
   if (!e->wide()) {
     // phm_narrow.hip: the sampling steps themselves (no indirection).  Edges that lead to an INTERNAL node first, grouped by depth
     // level -- the walk propagates states only along those --, then the tip edges; boundaries of the first part in nw_walk_off
@@ -639,8 +641,8 @@ void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& 
   p.n_groups = (p.n_edge + p.group - 1) / p.group;
   p.n_chunks = (p.n_groups + phm::TILES_CHUNK - 1) / phm::TILES_CHUNK;
   p.rows = e->nw_total_cap;
-  p.up = e->d_up.as<phm::UpStep>(); p.down = e->d_down.as<phm::DownStep>();
-  p.up_order = e->d_nw_up_order.as<int32_t>(); p.down_order = e->d_nw_down_order.as<int32_t>();
+  p.up = e->d_up.as<phm::UpStep>();
+  p.up_order = e->d_nw_up_order.as<int32_t>(); p.node_order = e->d_nw_node_order.as<int32_t>();
   p.branch_order = e->d_nw_border.as<int32_t>(); p.slot = e->d_tl_slot.as<int32_t>();
   p.cl_nodes = e->d_nw_cl_nodes.as<phm::ClusterNode>();      // NULL unless tiles_setup chose the subtree clusters
   p.cl_lvl_ptr = e->d_nw_cl_lvl_ptr.as<int32_t>(); p.cl_lvl_off = e->d_nw_cl_lvl_off.as<int32_t>();
@@ -1253,7 +1255,7 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
       const bool rec = e->maps.mode != phm::MAPS_OFF && it < (int)e->maps.j_of_iter.size() && e->maps.j_of_iter[it] >= 0;
       if (rec) { ml.mode = e->maps.mode; ml.j = e->maps.j_of_iter[it]; ml.J = e->maps.J; ml.dev = e->maps.dev; ++launches; }
       const phm::McmcMapsLaunch* mlp = rec ? &ml : nullptr;
-      small_n(e, [&](auto& p) { le = phm::launch_tiles_sweep(p.tl, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev, mlp); });
+      small_n(e, [&](auto& p) { le = phm::launch_tiles_sweep(p.tl, e->nw_up_off, e->nw_node_off, e->nw_tier_off, it, stream, pev, mlp); });
       if (e->wide()) le = phm::launch_wtiles_sweep(e->pwt, e->wt_band, e->wt_sparse, e->nw_up_off, e->nw_down_off, e->nw_tier_off, it, stream, pev, mlp);
       const bool clusters = !e->nw_tier_off.empty();
       const int tiers = (int)e->nw_tier_off.size() - 1;
@@ -1261,7 +1263,7 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
         launches += (e->pwt.band_up > 0 && !e->wt_sparse.kernel ? tiers : (int)e->nw_up_off.size() - 1) + tiers + 4;
       else
         launches += clusters ? 2 * tiers + 3      // a launch per tier and pass, branch kernel, two reductions
-                             : (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;
+                             : (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;      // (the node levels of phm_tiles.hip number the edge levels)
     }
     HIPCHK(le);
   } else {

@@ -135,6 +135,16 @@ void depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<in
   group_by_level(level, order, off);
 }
 
+void node_depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<int32_t>& off) {
+  std::vector<int32_t> depth(s.up.size(), 0), level(s.up.size());
+  for (size_t k = s.up.size(); k-- > 0;) {           // s.up backwards: parents before children
+    const UpStep& u = s.up[k];
+    level[k] = depth[u.parent];
+    for (int c = 0; c < 2; ++c) if (u.child[c] >= 0) depth[u.child[c]] = depth[u.parent] + 1;
+  }
+  group_by_level(level, order, off);
+}
+
 // heights, parents and positions in s.up of the internal nodes
 static void node_links(const Schedule& s, std::vector<int32_t>& height, std::vector<int32_t>& parent, std::vector<int32_t>& step_of) {
   height = node_heights(s.up);

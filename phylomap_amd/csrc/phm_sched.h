@@ -74,6 +74,9 @@ std::vector<int32_t> node_heights(const std::vector<UpStep>& up);
 void height_levels(const std::vector<UpStep>& up, std::vector<int32_t>& order, std::vector<int32_t>& off);
 // positions in s.down grouped by the depth of their parent node (root: 0); internal_only: the edges to an internal node alone
 void depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<int32_t>& off, bool internal_only = false);
+// positions in s.up (an internal node with both its children and edges) grouped by the depth of the node (root: 0): the two child
+// edges of a node sit at the same level of depth_levels, so the levels number the same and no level is empty
+void node_depth_levels(const Schedule& s, std::vector<int32_t>& order, std::vector<int32_t>& off);
 
 // Checks that the caller's nen / nodelist / root (R/sumstatMCMC.R:1-18) describe this tree:
 // nen a permutation with sibling edges adjacent and children before parents, nodelist parents before

@@ -8,7 +8,7 @@
 // and the random numbers are addressed by (replica, iteration, node | branch), so the results do not depend on the order.
 //   up     : one launch per HEIGHT level, a wave per (tile, internal node)          makePLrcpp* :503-529
 //   root   : a wave per tile                                                       :618-627
-//   down   : one launch per DEPTH level, a wave per (tile, edge)                   :640-657, :460-475
+//   down   : one launch per DEPTH level, a wave per (tile, internal node): both child edges   :640-657, :460-475
 //   branch : a wave per (tile, branch)                                             :264-413, :44-73, :745-757
 //   stats  : fixed-order reduction of the per-branch dwell sums (two stages), integer counters
 // Few tiles (10^2 .. 10^3 replicas: the sites of an alignment): a launch per tree level is 60+ launches of a handful of waves each
@@ -52,10 +52,11 @@ struct TileParams {
   uint32_t seed_lo, seed_hi;
   int64_t rows;                              // rows of one tile in one dwell buffer (sum of the slot sizes)
   double B2[NS * NS], Bc[NS * NS], scale[NS], pid[NS];
-  const UpStep* up;
-  const DownStep* down;
+  const UpStep* up;                          // up[] and node_order[] are written by the HOST before the first launch and by no kernel:
   const int32_t* up_order;                   // positions into up[], grouped by height level
-  const int32_t* down_order;                 // positions into down[], grouped by depth level
+  const int32_t* node_order;                 // positions into up[], grouped by the depth of the node (node_depth_levels)
+                                             //   tiles_down_kernel reads both through the constant address space (sched_word, phm_tiles.hip),
+                                             //   which would return stale data if a kernel ever rebuilt them on the device
   const ClusterNode* cl_nodes;               // subtree clusters (phm_sched.h ClusterPlan), or NULL: one launch per tree level
   const int32_t* cl_lvl_ptr;                 // [n_clusters + 1] into cl_lvl_off
   const int32_t* cl_lvl_off;                 // per cluster: boundaries of its height levels (positions in cl_nodes)
@@ -92,12 +93,12 @@ struct McmcMapsLaunch;      // phm_mcmc_maps.h
 
 // phase_ev: optional 5 events recorded before the pruning levels and after the pruning levels, the node draws, the branch kernel
 // and the reductions (measurement: bench.py's per-kernel roofline)
-// tier_off: cluster tiers (ClusterPlan::tier_off) when p.cl_nodes is set
+// up_off / node_off: level boundaries into up_order / node_order; tier_off: cluster tiers (ClusterPlan::tier_off) when p.cl_nodes is set
 // maps: a recorded sweep of the stochastic maps: the replay kernel runs after the node draws, before the branch
 // kernel (it counts with the branch phase)
 template <int NS>
 hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t>& up_off,
-                              const std::vector<int32_t>& down_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
+                              const std::vector<int32_t>& node_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
                               hipEvent_t* phase_ev = nullptr, const McmcMapsLaunch* maps = nullptr);
 
 }  // namespace phm

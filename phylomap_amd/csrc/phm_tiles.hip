@@ -3,6 +3,8 @@
 // taken from its own slot instead of the tile's sequential stream and the chain powers read from the long tables.
 #include "phm_tiles.h"
 
+#include <type_traits>
+
 #include "phm_mcmc_maps.h"
 
 namespace phm {
@@ -51,16 +53,66 @@ __device__ __forceinline__ void up_node(const TileParams<NS>& p, int tile, int p
   for (int c = 0; c < NS; ++c) PLt[(parent * NS + c) * 64 + lane] = x[c];
 }
 
+// up_node for the one-launch-per-level kernel below, where tile and schedule record are wave-uniform: the same expressions in the same
+// order, every row addressed as a scalar base plus the lane's 32-bit byte offset (at(), phm_device.h), and what does not depend on a
+// segment count -- both counts themselves, the children's vectors or tip states -- requested before the first count is waited for
+// (up_node goes child by child: count, wait, vector, wait -- four round trips in a row where the data allow two).
+template <int NS>
+__device__ __forceinline__ void up_item(const TileParams<NS>& p, int tile, const UpStep& st, uint32_t lane, uint32_t& err) {
+  double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * NS * 64;
+  const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
+  int k[2], tipst[2] = {0, 0};
+  double v[2][NS];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) k[s] = (int)at(mct + (size_t)st.edge[s] * 64, lane * 2u) - 1;
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    if (st.child[s] >= 0) {
+#pragma unroll
+      for (int c = 0; c < NS; ++c) v[s][c] = at(PLt + (size_t)st.child[s] * NS * 64, ((uint32_t)c * 64u + lane) * 8u);
+    }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)                        // (the tip bytes last: their widening waits for them)
+    if (st.child[s] < 0) {
+      const int tip = ~st.child[s];
+      tipst[s] = p.tips_per_replica ? at(p.tips + ((size_t)tile * p.n_tips + tip) * 64, lane) : p.tips[tip];
+    }
+#pragma unroll
+  for (int s = 1; s >= 0; --s) {                     // child[1] is the "first" factor (:508), child[0] the "second" (:509)
+    if (st.child[s] < 0) {
+      int kk = k[s];
+      if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
+      const double* src = (p.ks && p.tip_masks) ? p.maskL + ((size_t)kk * 2 + (tipst[s] & 1)) * NS : p.colL + ((size_t)kk * NS + tipst[s]) * NS;
+#pragma unroll
+      for (int c = 0; c < NS; ++c) v[s][c] = src[c];
+    } else {
+      for (int i = 0; i < k[s]; ++i) matvec_u<NS>(p.Bc, v[s]);
+    }
+  }
+  double x[NS];
+#pragma unroll
+  for (int c = 0; c < NS; ++c) x[c] = v[1][c] * v[0][c];                        // :510
+  if (p.normalise) {                                                           // :525
+    double sum = x[0];
+#pragma unroll
+    for (int c = 1; c < NS; ++c) sum += x[c];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) x[c] = x[c] / sum;
+  }
+#pragma unroll
+  for (int c = 0; c < NS; ++c) at(PLt + (size_t)st.parent * NS * 64, ((uint32_t)c * 64u + lane) * 8u) = x[c];
+}
+
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_up_kernel(TileParams<NS> p, int begin, int end) {
-  const int lane = threadIdx.x & 63;
-  const int item = blockIdx.x * (TILES_BLOCK / 64) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  const int item = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: tile, schedule record and tile bases in scalar registers
   const int n_lvl = end - begin;
   if (item >= n_lvl * p.n_tiles) return;
   const int tile = item / n_lvl;
   const UpStep st = p.up[p.up_order[begin + item % n_lvl]];
   uint32_t err = 0;
-  up_node<NS>(p, tile, st.parent, st.child[0], st.child[1], st.edge[0], st.edge[1], lane, err);
+  up_item<NS>(p, tile, st, lane, err);
   if (err) atomicOr(p.err, err);
 }
 
@@ -135,7 +187,7 @@ __device__ __forceinline__ void draw_root(const TileParams<NS>& p, int tile, int
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_root_kernel(TileParams<NS> p, int it) {
   const int lane = threadIdx.x & 63;
-  const int tile = blockIdx.x * (TILES_BLOCK / 64) + (threadIdx.x >> 6);
+  const int tile = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (tile >= p.n_tiles) return;
   uint32_t err = 0;
   draw_root<NS>(p, tile, it, lane, err);
@@ -180,88 +232,159 @@ __device__ __forceinline__ void down_edge(const TileParams<NS>& p, int tile, int
   p.estate[((size_t)tile * p.n_edge + b) * 64 + lane] = (uint8_t)(ps | (cs << 4));   // updatenodestates :460-475
 }
 
-// what a node draw reads from memory that does not depend on anything it computes: requested one item ahead by tiles_down_kernel
+// The node draws of one launch per depth level: an item per (tile, INTERNAL NODE) draws both children.  Half the edges of a tree end in
+// a tip, and with the tips' states given such an edge draws nothing: it only stores its end states -- as an item of its own it cost a
+// wave that loaded a segment count for nothing and the parent's state a second time, in a kernel whose time follows its item count.
+// For each child side the expressions are those of down_edge (the cluster kernels keep that one: the tests compare the two).
+// What a side reads from memory that does not depend on anything it computes:
 template <int NS>
-struct DownLoads {
-  int32_t tile, b, parent, child;
-  int32_t m, ps, tipst;
+struct SideLoads {
+  int32_t m, tipst;
   double pl[NS];
 };
 
 template <int NS>
-__device__ __forceinline__ DownLoads<NS> down_request(const TileParams<NS>& p, int item, int n_lvl, int begin, int lane) {
-  DownLoads<NS> d;
-  const DownStep ds = p.down[p.down_order[begin + item % n_lvl]];
-  d.tile = item / n_lvl; d.b = ds.edge; d.parent = ds.parent; d.child = ds.child;
-  d.m = p.mcount[((size_t)d.tile * p.n_edge + d.b) * 64 + lane];
-  d.ps = p.nstate[((size_t)d.tile * p.n_node + d.parent) * 64 + lane];
-  d.tipst = 0;
-  if (d.child >= 0) {
-    const double* __restrict__ PLc = p.PL + ((size_t)d.tile * p.n_node + d.child) * NS * 64 + lane;
-#pragma unroll
-    for (int c = 0; c < NS; ++c) d.pl[c] = PLc[c * 64];
-  } else {
-    const int tip = ~d.child;
-#pragma unroll
-    for (int c = 0; c < NS; ++c) d.pl[c] = 0.0;
-    d.tipst = p.tips_per_replica ? p.tips[((size_t)d.tile * p.n_tips + tip) * 64 + lane] : p.tips[tip];
-  }
-  return d;
+struct NodeLoads {
+  int32_t tile;
+  UpStep st;
+  int32_t ps;
+  SideLoads<NS> side[2];
+};
+
+// A wave-uniform read of a schedule table (written by the host before the first launch, by no kernel): through the constant address
+// space.  Behind the kernel's own stores -- the second item of a persistent wave -- the compiler no longer takes global memory for
+// unchanged and would fetch the record with vector loads and read it back lane by lane.
+__device__ __forceinline__ int32_t sched_word(const int32_t* q, int i) {
+  return ((const __attribute__((address_space(4))) int32_t*)q)[i];
 }
 
-// the draw itself on what down_request brought: the same expression as down_edge
-template <int NS>
-__device__ __forceinline__ void down_finish(const TileParams<NS>& p, const DownLoads<NS>& d, int it, int lane, uint32_t& err) {
-  const uint32_t rep = (uint32_t)(p.replica_offset + d.tile * 64 + lane);
-  int cs;
-  if (d.child >= 0 || (p.ks && p.tip_masks)) {
-    int kk = d.m - 1;
-    if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
-    const double* src = p.rowL + ((size_t)kk * NS + d.ps) * NS;
-    double w[NS];
-    uint32_t node_id;
-    if (d.child >= 0) {
-#pragma unroll
-      for (int c = 0; c < NS; ++c) w[c] = src[c] * d.pl[c];
-      node_id = (uint32_t)(d.child + p.n_tips);
-    } else {
-      const int par = d.tipst & 1;
-#pragma unroll
-      for (int c = 0; c < NS; ++c) w[c] = src[c] * (((c & 1) == par) ? 1.0 : 0.0);
-      node_id = (uint32_t)(~d.child);
+// What a child side is, known per item and the same for the whole wave: a tip whose state is given (nothing is drawn: the edge's end
+// states are stored), an internal node, or -- hidden rates -- a tip drawn against its parity mask.  The code of an item is compiled once
+// per pair of kinds (with_side_kinds), so every form is a straight line: all its requests first, both weight rows together, then the
+// draws.  With the kinds tested at run time inside one body the compiler kept the sides apart and waited for each load where it stood.
+enum : int { SIDE_TIP = 0, SIDE_NODE = 1, SIDE_TIP_DRAWN = 2 };
+
+template <class F>
+__device__ __forceinline__ void with_side_kinds(bool draw_tips, int child0, int child1, F&& f) {
+  using Tip = std::integral_constant<int, SIDE_TIP>;
+  using Node = std::integral_constant<int, SIDE_NODE>;
+  using Drawn = std::integral_constant<int, SIDE_TIP_DRAWN>;
+  const int code = (child0 >= 0 ? 1 : 0) | (child1 >= 0 ? 2 : 0);      // wave-uniform
+  if (!draw_tips) {
+    switch (code) {
+      case 0: f(Tip{}, Tip{}); break;
+      case 1: f(Node{}, Tip{}); break;
+      case 2: f(Tip{}, Node{}); break;
+      default: f(Node{}, Node{}); break;
     }
-    const double u = stream_u(p.seed_lo, p.seed_hi, rep, (uint32_t)it, ENT_NODE | node_id, 0);
-    cs = sample_cat<NS>(w, u, err);                                            // :655
-    if (d.child >= 0) p.nstate[((size_t)d.tile * p.n_node + d.child) * 64 + lane] = (uint8_t)cs;
   } else {
-    cs = d.tipst;                                                             // :612
+    switch (code) {
+      case 0: f(Drawn{}, Drawn{}); break;
+      case 1: f(Node{}, Drawn{}); break;
+      case 2: f(Drawn{}, Node{}); break;
+      default: f(Node{}, Node{}); break;
+    }
   }
-  p.estate[((size_t)d.tile * p.n_edge + d.b) * 64 + lane] = (uint8_t)(d.ps | (cs << 4));   // updatenodestates :460-475
+}
+
+// tile and item position are wave-uniform: the schedule record comes by scalar loads, every per-tile row is a scalar base plus the
+// lane's 32-bit byte offset (at(), phm_device.h)
+template <int NS>
+__device__ __forceinline__ void node_record(const TileParams<NS>& p, NodeLoads<NS>& d, int item, int n_lvl, int begin) {
+  d.tile = item / n_lvl;
+  const int32_t* rec = reinterpret_cast<const int32_t*>(p.up + sched_word(p.node_order, begin + item % n_lvl));
+  static_assert(sizeof(UpStep) == 5 * sizeof(int32_t), "UpStep: parent, two children, two edges");
+  d.st.parent = sched_word(rec, 0);
+  d.st.child[0] = sched_word(rec, 1); d.st.child[1] = sched_word(rec, 2);
+  d.st.edge[0] = sched_word(rec, 3); d.st.edge[1] = sched_word(rec, 4);
+}
+
+// every request of an item before anything is done with a result: parent state, segment counts, partial likelihoods, tip states
+template <int NS, int K0, int K1>
+__device__ __forceinline__ void node_request(const TileParams<NS>& p, NodeLoads<NS>& d, uint32_t lane) {
+  constexpr int kind[2] = {K0, K1};
+  d.ps = at(p.nstate + ((size_t)d.tile * p.n_node + d.st.parent) * 64, lane);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (kind[k] != SIDE_TIP) d.side[k].m = at(p.mcount + ((size_t)d.tile * p.n_edge + d.st.edge[k]) * 64, lane * 2u);
+    else d.side[k].m = 1;
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const double* PLc = p.PL + ((size_t)d.tile * p.n_node + d.st.child[k]) * NS * 64;
+#pragma unroll
+    for (int c = 0; c < NS; ++c) d.side[k].pl[c] = kind[k] == SIDE_NODE ? at(PLc, ((uint32_t)c * 64u + lane) * 8u) : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (kind[k] != SIDE_NODE) {
+      const int tip = ~d.st.child[k];
+      d.side[k].tipst = p.tips_per_replica ? at(p.tips + ((size_t)d.tile * p.n_tips + tip) * 64, lane) : p.tips[tip];
+    } else {
+      d.side[k].tipst = 0;
+    }
+  }
+}
+
+// the draws themselves on what node_request brought: per side the same expressions as down_edge.  The weight rows of both sides are
+// read before either side stores (a byte store may alias anything: the second side's loads would wait behind the first side's stores).
+template <int NS, int K0, int K1>
+__device__ __forceinline__ void node_finish(const TileParams<NS>& p, const NodeLoads<NS>& d, int it, uint32_t lane, uint32_t& err) {
+  constexpr int kind[2] = {K0, K1};
+  const uint32_t rep = (uint32_t)(p.replica_offset + d.tile * 64) + lane;
+  double w[2][NS];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const SideLoads<NS>& sd = d.side[k];
+    if (kind[k] != SIDE_TIP) {
+      int kk = sd.m - 1;
+      if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
+      const double* src = p.rowL + ((size_t)kk * NS + d.ps) * NS;
+      if (kind[k] == SIDE_NODE) {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) w[k][c] = src[c] * sd.pl[c];
+      } else {
+        const int par = sd.tipst & 1;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) w[k][c] = src[c] * (((c & 1) == par) ? 1.0 : 0.0);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int child = d.st.child[k];
+    int cs;
+    if (kind[k] != SIDE_TIP) {
+      const uint32_t node_id = kind[k] == SIDE_NODE ? (uint32_t)(child + p.n_tips) : (uint32_t)(~child);
+      const double u = stream_u(p.seed_lo, p.seed_hi, rep, (uint32_t)it, ENT_NODE | node_id, 0);
+      cs = sample_cat<NS>(w[k], u, err);                                       // :655
+      if (kind[k] == SIDE_NODE) at(p.nstate + ((size_t)d.tile * p.n_node + child) * 64, lane) = (uint8_t)cs;
+    } else {
+      cs = d.side[k].tipst;                                                   // :612
+    }
+    at(p.estate + ((size_t)d.tile * p.n_edge + d.st.edge[k]) * 64, lane) = (uint8_t)(d.ps | (cs << 4));   // updatenodestates :460-475
+  }
 }
 
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_down_kernel(TileParams<NS> p, int it, int begin, int end) {
-  const int lane = threadIdx.x & 63;
+  const uint32_t lane = threadIdx.x & 63;
   const int n_lvl = end - begin;
   const int n_items = n_lvl * p.n_tiles;
   const int stride = gridDim.x * (TILES_BLOCK / 64);
+  const bool draw_tips = p.ks && p.tip_masks;
   uint32_t err = 0;
   // Persistent waves (kernel arguments and wave set-up once per wave: 2.28 -> 2.01 ms per sweep on C3; the pruning kernel above loses by
-  // the same change: 3.16 -> 3.7), and -- round 4 -- the NEXT item's segment count, parent state and partial likelihoods are requested
-  // before the current item is drawn: an item is three dependent memory round trips and a dozen operations, the kernel waited 0.84 of
-  // its time (profiles/r04_pmc_C3_summary.json).  A level's items only read states drawn by the previous launch, so running ahead is safe.
-  int item = blockIdx.x * (TILES_BLOCK / 64) + (threadIdx.x >> 6);
-  if (item < n_items) {
-    DownLoads<NS> cur = down_request<NS>(p, item, n_lvl, begin, lane);
-    for (;;) {
-      const int next = item + stride;
-      const bool more = next < n_items;                // wave-uniform
-      DownLoads<NS> nxt = cur;
-      if (more) nxt = down_request<NS>(p, next, n_lvl, begin, lane);
-      down_finish<NS>(p, cur, it, lane, err);
-      if (!more) break;
-      cur = nxt; item = next;
-    }
+  // the same change: 3.16 -> 3.7).  Round 4 requested the next item's data before drawing the current one; with two children per item
+  // and each form a straight line the requests of an item already overlap, and running ahead as well costs 101 registers (four waves
+  // per SIMD) for nothing: C3 node draws 1.55 ms without it, 1.61 with it (1.91 per edge; docs/MEASUREMENTS.md, round 5).
+  for (int item = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); item < n_items; item += stride) {      // wave-uniform, like all that follows from it
+    NodeLoads<NS> d;
+    node_record<NS>(p, d, item, n_lvl, begin);
+    with_side_kinds(draw_tips, d.st.child[0], d.st.child[1], [&](auto k0, auto k1) {
+      node_request<NS, decltype(k0)::value, decltype(k1)::value>(p, d, lane);
+      node_finish<NS, decltype(k0)::value, decltype(k1)::value>(p, d, it, lane, err);
+    });
   }
   if (err) atomicOr(p.err, err);
 }
@@ -569,7 +692,7 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_chunk_kernel(TileParams<NS> p) {
   const int lane = threadIdx.x & 63;
-  const int item = blockIdx.x * (TILES_BLOCK / 64) + (threadIdx.x >> 6);
+  const int item = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (item >= p.n_chunks * p.n_tiles) return;
   const int tile = item / p.n_chunks, chunk = item % p.n_chunks;
   const int b0 = chunk * TILES_CHUNK, b1 = min(b0 + TILES_CHUNK, p.n_groups);
@@ -705,7 +828,7 @@ hipError_t launch_tiles_init(int n_edge, int n_tiles, int64_t rows, const int32_
 
 template <int NS>
 hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t>& up_off,
-                              const std::vector<int32_t>& down_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
+                              const std::vector<int32_t>& node_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,
                               hipEvent_t* phase_ev, const McmcMapsLaunch* maps) {
   constexpr int WPB = TILES_BLOCK / 64;
   auto blocks = [&](int64_t items) { return dim3((unsigned)((items + WPB - 1) / WPB)); };
@@ -732,9 +855,9 @@ hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t
     }
     mark(1);
     hipLaunchKernelGGL(tiles_root_kernel<NS>, blocks(p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
-    for (size_t l = 0; l + 1 < down_off.size(); ++l) {
-      const int n = down_off[l + 1] - down_off[l];
-      if (n > 0) hipLaunchKernelGGL(tiles_down_kernel<NS>, pblocks((int64_t)n * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it, down_off[l], down_off[l + 1]);
+    for (size_t l = 0; l + 1 < node_off.size(); ++l) {
+      const int n = node_off[l + 1] - node_off[l];
+      if (n > 0) hipLaunchKernelGGL(tiles_down_kernel<NS>, pblocks((int64_t)n * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it, node_off[l], node_off[l + 1]);
     }
   }
   mark(2);
