@@ -466,6 +466,30 @@ int32_t phm_sample_histories_models(const phm_tree* x, int32_t n_states, int32_t
                                     const phm_options* opt, double* stats, double* loglik, int32_t* nodes,
                                     int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
 
+/* ---- ancestral states of many rate matrices in one call: marginal and joint ----
+ * Per evaluation (model k, site s): the marginal posterior of the state of every reported node, and the JOINT reconstruction --
+ * the one assignment of ALL nodes that maximises p(states of all nodes, tips_s | Q_k, pid_k) (Pupko et al. 2000: a max-product up
+ * pass with back pointers, then a traceback; ties go to the smallest state, on the device's own P).  Every argument up to
+ * site_of_model is phm_loglik_models', checked the same way before any device call.  2..8 states (9..64: PHM_ERR_UNSUPPORTED;
+ * phm_expected_stats' node_post serves one wide model at a time).  An evaluation's index e is its index into loglik.
+ *   node_sel: n_sel 1-based ape node ids in 1 .. n_tips + n_node, tips and duplicates allowed: the J = n_sel nodes to report, in
+ *     that order.  NULL with n_sel = 0: every node in id order (J = n_tips + n_node).  A bad entry is PHM_ERR_BAD_INPUT naming
+ *     its 0-based index; so are n_sel < 0 and n_sel > 0 with node_sel NULL.
+ *   loglik: phm_loglik_models' values bit for bit.
+ *   node_post: NULL, or [e][j][state], the state fastest: P(state of node j | tips_s, Q_k, pid_k), phm_expected_stats' node_post
+ *     per model.
+ *   joint_states: NULL, or [e][j]: the 1-based TRUE state of node j in the joint reconstruction, tips included (a missing tip
+ *     and the hidden state behind an observe map come out reconstructed).
+ *   joint_logp: NULL, or [e]: the log of that maximum (at most loglik); it needs joint_states.
+ * node_post and joint_states both NULL is PHM_ERR_BAD_INPUT; the part not asked for is not computed and the other part is the
+ * same bit for bit.  An evaluation whose log-likelihood is -inf gets NaN in node_post, 0 in joint_states and -inf in joint_logp;
+ * it does not fail the call.  n_devices / devices[] shard the models and phm_debug_options.expect_chunk caps the chunks of
+ * models, sites and level steps; neither changes an output bit.  phm_last_kernel_ms: device time of the call. */
+int32_t phm_ancestral_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid,
+                             int32_t n_pid, const int32_t* observe, const int32_t* site_of_model,
+                             const int32_t* node_sel, int32_t n_sel, const phm_options* opt,
+                             double* loglik, double* node_post, int32_t* joint_states, double* joint_logp);
+
 /* ---- batched posterior sampling of the rates of an index model by exact data augmentation ----
  * n_chains chains in lock-step, one per lane.  The model: q_ij = theta_c for index[i, j] = c in 1..n_params, 0 for index 0 (index:
  * n x n column-major, diagonal ignored, every parameter owning at least one entry); the diagonal is minus the row's entries summed

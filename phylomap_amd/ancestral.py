@@ -1,0 +1,58 @@
+"""Helpers around ``api.ancestral_states_models``: model weights, model-averaged node posteriors and the
+node id of a clade's ancestor.  numpy only, no device."""
+from __future__ import annotations
+
+import numpy as np
+
+
+def akaike_weights(loglik, n_params):
+    """Akaike weights of K models: w_k proportional to exp(-(AIC_k - min AIC) / 2), AIC_k = 2 n_params_k - 2 loglik_k.
+    ``n_params``: K values, or one shared by every model.  A model with ``loglik`` = -inf gets weight 0 (all -inf: ValueError)."""
+    ll = np.asarray(loglik, dtype=np.float64).reshape(-1)
+    aic = 2.0 * np.broadcast_to(np.asarray(n_params, dtype=np.float64), ll.shape) - 2.0 * ll
+    if not np.any(np.isfinite(aic)):
+        raise ValueError("every model has loglik = -inf")
+    w = np.where(np.isfinite(aic), np.exp(-0.5 * (aic - np.min(aic[np.isfinite(aic)]))), 0.0)
+    return w / np.sum(w)
+
+
+def model_average(node_post, weights=None, axis=0):
+    """Weighted mean of ``node_post`` over its model axis.  ``weights``: one non-negative value per model, normalised here
+    (``akaike_weights``); None: equal weights, as for a posterior sample of Q.  A model of weight 0 is left out, so it may hold
+    NaN (an impossible evaluation)."""
+    post = np.moveaxis(np.asarray(node_post, dtype=np.float64), axis, 0)
+    K = post.shape[0]
+    w = np.full(K, 1.0) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != K:
+        raise ValueError("weights must have one entry per model")
+    if np.any(w < 0.0) or not np.sum(w) > 0.0:
+        raise ValueError("weights must be non-negative with a positive sum")
+    w = w / np.sum(w)
+    out = np.zeros(post.shape[1:])
+    for k in range(K):
+        if w[k] > 0.0:
+            out += w[k] * post[k]
+    return out
+
+
+def mrca(z, tips):
+    """Ape node id of the most recent common ancestor of the 1-based tip ids ``tips`` in the tree ``z`` (``z['edge']``,
+    ``z['Nnode']``); a single tip is its own ancestor.  The id can go into ``api.ancestral_states_models(nodes=...)``."""
+    edge = np.asarray(z["edge"], dtype=np.int64)
+    T = edge.shape[0] - int(z["Nnode"]) + 1
+    tips = [int(t) for t in np.atleast_1d(tips)]
+    if not tips or any(t < 1 or t > T for t in tips):
+        raise ValueError(f"tips must be ids in 1..{T}")
+    parent = {int(c): int(p) for p, c in edge}
+
+    def path(v):                                        # v, its parent, ..., the root
+        out = [v]
+        while out[-1] in parent:
+            out.append(parent[out[-1]])
+        return out
+
+    common = path(tips[0])
+    for t in tips[1:]:
+        on = set(path(t))
+        common = [v for v in common if v in on]
+    return common[0]

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -495,6 +496,59 @@ def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=
         _lib.check(L.phm_sample_histories_models(*args, None, 0, None, None))
         return res
     return res + (_two_phase_maps(L.phm_sample_histories_models, args, int(np.prod(hshape)), a.E),)
+
+
+AncestralStates = namedtuple("AncestralStates", ["loglik", "node_post", "joint_states", "joint_logp", "nodes"])
+
+
+def ancestral_states_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, nodes=None, marginal=True, joint=True,
+                            **opt):
+    """Ancestral states under K rate matrices in one call -> phm_ancestral_models: the marginal posterior
+    of every reported node's state and the JOINT reconstruction, the one assignment of all nodes that maximises
+    p(states, tips_s | Q_k, pid_k) (Pupko et al. 2000), with the models across the lanes (2..8 states).  ``Qs``, ``pid``, ``z``,
+    ``sites``, ``observe`` and ``site_of_model`` are ``loglik_models``'.  ``nodes``: 1-based ape node ids to report, tips and
+    duplicates allowed (``ancestral.mrca`` names a clade's ancestor); None: every node in id order.  Returns the named tuple
+    ``(loglik, node_post, joint_states, joint_logp, nodes)``: [K, S] (``loglik_models``' values bit for bit), [K, S, J, n],
+    [K, S, J] 1-based TRUE states (a missing tip and the hidden state behind ``observe`` come out reconstructed) and [K, S]; with
+    ``site_of_model`` the S axis is absent.  ``marginal=False`` / ``joint=False`` leave that part out (``None``; the other part is
+    the same bit for bit).  ``nodes`` echoes the ids reported.  An impossible evaluation (``-inf``) has NaN posteriors, zero
+    states and ``joint_logp`` = ``-inf``.  Options: device, devices."""
+    if not marginal and not joint:
+        raise ValueError("marginal and joint are both False: nothing to compute")
+    L = _lib.load()
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError("pid must have n entries, shared or one row per model")
+    som = None
+    if site_of_model is not None:
+        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
+        if som.size != K:
+            raise ValueError("site_of_model must have one entry per model")
+    sel = None
+    if nodes is not None:
+        sel = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
+        if sel.size == 0:
+            raise ValueError("nodes must name at least one node (None: every node)")
+    J = a.NT if sel is None else sel.size
+    shape = (K,) if som is not None else (K, a.S)
+    ll = np.zeros(shape)
+    post = np.zeros(shape + (J, n)) if marginal else None
+    states = np.zeros(shape + (J,), dtype=np.int32) if joint else None
+    jl = np.zeros(shape) if joint else None
+    _lib.check(L.phm_ancestral_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
+                                      _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), _lib._p(sel, C.c_int32),
+                                      0 if sel is None else sel.size, C.byref(a.opt), _lib._p(ll, C.c_double),
+                                      _lib._p(post, C.c_double), _lib._p(states, C.c_int32), _lib._p(jl, C.c_double)))
+    ids = np.arange(1, a.NT + 1, dtype=np.int32) if sel is None else sel.copy()
+    return AncestralStates(ll, post, states, jl, ids)
 
 
 def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, seed=0, gtol=1e-5, max_iter=200, bounds=None,
