@@ -383,6 +383,8 @@ def test_generated_sparse_pruning_kernel_compiles_for_gfx950():
         line = [ln for ln in src.splitlines() if f" y[{i}] = a; }}" in ln][0]
         cols = [int(c) for c in re.findall(r"x\[(\d+)\]", line)]
         assert cols == sorted(np.nonzero(B[i])[0].tolist())
+        coef = [int(c) for c in re.findall(r"C\[(\d+)\]", line)]
+        assert coef == list(range(7 * i, 7 * i + 7))                        # CSR order: row_ptr[i] .. row_ptr[i+1]-1 (7 non-zeros per row)
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
