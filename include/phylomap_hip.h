@@ -490,6 +490,30 @@ int32_t phm_ancestral_models(const phm_tree* x, int32_t n_states, int32_t n_mode
                              const int32_t* node_sel, int32_t n_sel, const phm_options* opt,
                              double* loglik, double* node_post, int32_t* joint_states, double* joint_logp);
 
+/* ---- forward simulation under many rate matrices in one call ----
+ * K = n_models models (Q_k, pid_k), R = replicates histories each: one replicate dataset per posterior draw of the rates, R
+ * bootstrap replicates under each of K fits, one dataset per prior draw.  H = K * R histories, history h = k * R + r, and history
+ * h is -- in every state, count, tip, segment and segment dwell -- what phm_simulate_histories returns for GLOBAL replica
+ * replica_offset + h under (Q_k, pid_k) with the same seed: only the Philox replica word carries h.  The per-history dwell sums
+ * alone may differ from it in the last bits (they are accumulated in 64-bit fixed point, within 1e-12 * tree length of the
+ * floating-point sums, and are the same bits whatever the chunks and devices are).
+ *   Q: n x n x K, each matrix column-major, model slowest (phm_loglik_models' layout); pid: n x n_pid, n_pid = 1 (shared) or K,
+ *     used as given (not normalised), as phm_simulate_histories uses it.
+ *   tips: H x n_tips, history-major, 1-based reported states (through observe).  nodes: NULL, or H x (n_tips + n_node),
+ *     history-major, 1-based true states by ape node id.  stats: H x (n + n*n + 1) column-major, phm_simulate_histories' columns.
+ *   map_off NULL: no maps.  Otherwise the two-phase contract of phm_simulate_histories_maps with R = H, row h * n_edge + b.
+ * Checked before any device call: the tree and edge lengths, every Q_k like phm_simulate_histories' Q and every pid column like
+ * its pid (a bad model or pid column is named by its 0-based index), observe, the map arguments; PHM_ERR_BAD_INPUT for
+ * replicates < 1, n_pid neither 1 nor K, reduce != 0 and replica_offset + H beyond the 32-bit replica word.  2 <= n <= 64.
+ * phm_options.n_replicas is not read.  A branch that needs more than 9 999 jumps is PHM_ERR_CAPACITY naming the lowest-index
+ * model that overflowed and an edge row of it; the loop is bounded, nothing faults.  n_devices / devices[] shard the models,
+ * histories are chunked by free HBM and phm_debug_options.expect_chunk caps the histories per chunk (rounded up to 64) and the
+ * edges per wave item; none of them changes an output bit.  phm_last_kernel_ms: device time of the call. */
+int32_t phm_simulate_histories_models(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid,
+                                      int32_t n_pid, const int32_t* observe, int32_t replicates, const phm_options* opt,
+                                      int32_t* tips, int32_t* nodes, double* stats,
+                                      int64_t* map_off, int64_t map_cap, double* map_dwell, int32_t* map_state);
+
 /* ---- batched posterior sampling of the rates of an index model by exact data augmentation ----
  * n_chains chains in lock-step, one per lane.  The model: q_ij = theta_c for index[i, j] = c in 1..n_params, 0 for index 0 (index:
  * n x n column-major, diagonal ignored, every parameter owning at least one entry); the diagonal is minus the row's entries summed

@@ -302,6 +302,53 @@ def simulate_state_tree(z, Q, pid, observe=None, **opt):
     return synth.with_tip_states(z, tips[0])
 
 
+def simulate_histories_models(z, Qs, pid, R, observe=None, nodes=False, maps=False, **opt):
+    """``R`` forward simulations under EACH of K rate matrices in one call ->
+    phm_simulate_histories_models: one replicate dataset per posterior draw of the rates (``posterior.predictive``), R bootstrap
+    replicates under each of K fits, one dataset per prior draw.  ``Qs``: [K, n, n] (or one [n, n]); ``pid``: n values shared by
+    the models or [K, n], used as given.  History h = k R + r is ``simulate_histories(z, Qs[k], pid[k], 1,
+    replica_offset=replica_offset + h)``'s, bit for bit in tips, nodes, counts, root state and maps; the dwell sums agree with it
+    to 1e-12 of the tree length (64-bit fixed-point accumulators: the same bits whatever the chunks and devices are).
+    Returns ``(tips, stats)``: tips [K, R, n_tips] 1-based (seen through ``observe``), stats [K, R, n + n*n + 1] in
+    ``simulate_histories``' columns; ``nodes=True`` appends [K, R, n_tips + Nnode] 1-based true states, ``maps=True`` the H = K R
+    histories as a ``maps.Maps`` (a sizing call, then a filling call).  Options: seed, replica_offset, device, devices."""
+    L = _lib.load()
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError("pid must have n entries, shared or one row per model")
+    edge = np.asarray(z["edge"], dtype=np.int32)
+    E = edge.shape[0]
+    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
+    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
+    Nn = int(z["Nnode"])
+    T = E - Nn + 1
+    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
+    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
+    if obs is not None and obs.size != n:
+        raise ValueError("observe must have one entry per state")
+    R = int(R)
+    Rr = max(R, 1)                                                    # R < 1 is refused by the library; the arrays stay valid
+    o = _lib.make_options(**opt)
+    cols = n + n * n + 1
+    tips = np.zeros((K, Rr, T), dtype=np.int32)
+    nst = np.zeros((K, Rr, T + Nn), dtype=np.int32) if nodes else None
+    stats = np.zeros((cols, K, Rr))                                   # column slowest, history fastest within it
+    args = (C.byref(tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(obs, C.c_int32), R,
+            C.byref(o), _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32), _lib._p(stats, C.c_double))
+    res = (tips, np.moveaxis(stats, 0, -1)) + ((nst,) if nodes else ())
+    if not maps:
+        _lib.check(L.phm_simulate_histories_models(*args, None, 0, None, None))
+        return res
+    return res + (_two_phase_maps(L.phm_simulate_histories_models, args, K * Rr, E),)
+
+
 def _expect_args(z, Q, pid, sites, observe, opt):
     """What phm_expected_stats and phm_expected_through_time share: the tree with its tip states (``z['states']`` or ``sites``),
     Q, pid, observe and the options.  ``keep`` holds the arrays the tree points into."""

@@ -91,3 +91,42 @@ def dic(result, burn, z, pid, sites=None, observe=None, **opt):
     out = dict(DIC=np.array([v[0] for v in vals]), D=np.array([v[1] for v in vals]), pD=np.array([v[2] for v in vals]),
                theta_mean=mean)
     return out if result.get("per_site", False) else {k: v[0] for k, v in out.items()}
+
+
+def predictive_rows(result, burn=0, draws=None):
+    """The theta rows ``predictive`` simulates under: the rows of ``result["theta"]`` after the first ``burn``, over all chains
+    (and sites), flattened row-major to [N, p]; ``draws`` = M thins them evenly to rows ``(j N) // M``, j = 0 .. M - 1."""
+    th = np.asarray(result["theta"], dtype=np.float64)
+    th = th[int(burn):].reshape(-1, th.shape[-1])
+    N = th.shape[0]
+    if N < 1:
+        raise ValueError("no draws left")
+    if draws is not None:
+        M = int(draws)
+        if M < 1 or M > N:
+            raise ValueError(f"draws must be in 1..{N}")
+        th = th[(np.arange(M, dtype=np.int64) * N) // M]
+    if not np.all(np.isfinite(th)):
+        raise ValueError("the selected rows hold a chain that failed (NaN rates)")
+    return th
+
+
+def predictive(result, z, pid, burn=0, draws=None, observe=None, **opt):
+    """Posterior-predictive replicates of an ``api.posterior_rates`` result: one dataset simulated forward under every kept draw
+    of the rates, all in one ``api.simulate_histories_models`` call (R = 1, the models across the lanes).  The rows are
+    ``predictive_rows(result, burn, draws)``.  Returns a dict: theta [M, p], tips [M, n_tips] (1-based, through ``observe``) and
+    stats [M, n + n*n + 1] in ``api.simulate_histories``' columns.  Row m is ``api.simulate_histories(z, Q(theta[m]), pid, 1,
+    replica_offset=replica_offset + m)``'s.  Options: seed, replica_offset, device, devices."""
+    from . import api
+    th = predictive_rows(result, burn, draws)
+    tips, stats = api.simulate_histories_models(z, rate_matrices(result["model"], th), pid, 1, observe=observe, **opt)[:2]
+    return dict(theta=th, tips=tips[:, 0], stats=stats[:, 0])
+
+
+def ppp(t_obs, t_rep):
+    """Posterior-predictive p-value of a test quantity: mean(t_rep > t_obs) + mean(t_rep == t_obs) / 2 over the replicates
+    (ties count half, so a discrete quantity is not biased towards either tail)."""
+    t_rep = np.asarray(t_rep, dtype=np.float64).reshape(-1)
+    if t_rep.size < 1:
+        raise ValueError("no replicates")
+    return float(np.mean(t_rep > t_obs) + 0.5 * np.mean(t_rep == t_obs))
