@@ -69,8 +69,9 @@ def run(n, Cn, joint, per_chain_prior, thin=1, theta_max=20.0, expect_chunk=0, d
                 theta_max=theta_max, thin=thin, C=Cn)
 
 
-def check_rows(r, update=True):
-    """every recorded row of run r against the public calls and the twin's update; returns whether every theta agreed bitwise"""
+def check_rows(r, update=True, chains=None):
+    """every recorded row of run r against the public calls and the twin's update (``chains``: the chains whose update the twin
+    repeats, None: all); returns whether every theta agreed bitwise"""
     m, z, n, Cn = r["m"], r["z"], r["m"].n, r["C"]
     cols = n + n * (n - 1)
     tree_len = float(np.sum(z["edge.length"]))
@@ -96,7 +97,7 @@ def check_rows(r, update=True):
             tot = tot + llm[:, s]
         assert np.array_equal(tot, r["loglik"][row]) and np.array_equal(ll.reshape(Cn, -1), llm)
         if update and r["thin"] == 1 and row + 1 < rows:
-            for k in range(Cn):
+            for k in (range(Cn) if chains is None else chains):
                 want, _ = gibbsref.update(m.index, th[k], st[k], r["prior"][k], r["theta_max"], r["seed"], k, i)
                 got = r["theta"][row + 1, k]
                 worst_theta = max(worst_theta, float(np.max(np.abs(got - want) / want)))
@@ -122,6 +123,14 @@ def test_lock_step_equivalence(n, Cn, joint, thin, per_chain_prior):
         for k in ("theta", "loglik", "stats"):
             assert np.array_equal(r[k], full[k][::thin])
         assert np.array_equal(r["rejected"], full["rejected"])
+
+
+@pytest.mark.parametrize("joint", [False, True])
+@pytest.mark.parametrize("Cn", [63, 130])
+@pytest.mark.parametrize("n", [5, 6, 7])
+def test_lock_step_equivalence_run_time_n(n, Cn, joint):
+    """5, 6 and 7 states: the run-time-n forms (sm_branch_kernel<0, ...>, sm_draw<0>) between the templated ones and n = 8"""
+    check_rows(run(n, Cn, joint, True, 1))
 
 
 @pytest.mark.parametrize("n,joint", [(4, True), (8, False)])

@@ -70,6 +70,9 @@ CASES = [
     (2, 65, 1, 1, False, None, 0.1, True, False),
     (4, 65, 2, 1, True, sc.PARITY, 0.1, False, True),
     (3, 1, 2, 130, False, None, 0.0, False, False),
+    (5, 3, 2, 64, True, None, 0.1, True, False),           # 5, 6, 7 states: the run-time-n forms below n = 8
+    (6, 3, 2, 64, False, None, 0.0, False, False),
+    (7, 3, 2, 64, True, None, 0.1, False, False),
 ]
 
 

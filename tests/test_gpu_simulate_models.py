@@ -44,8 +44,9 @@ def _row_check(m, lens):
     assert np.all(np.abs(sums - lens[None, :]) <= 1e-12 * lens[None, :])
 
 
-def _check(z, Qs, pids, R, seed, off=0, observe=None, device_twin=True, **opt):
-    """the batched call against simref.simulate and api.simulate_histories, model by model"""
+def _check(z, Qs, pids, R, seed, off=0, observe=None, device_twin=True, twin_rows=None, **opt):
+    """the batched call against simref.simulate and api.simulate_histories, model by model; ``twin_rows``: the (first replica,
+    count) ranges of every model that the Python twin visits (None: all R) -- the device twin always visits them all"""
     Qs = np.asarray(Qs)
     K, n = Qs.shape[0], Qs.shape[1]
     edge, lens = z["edge"], np.asarray(z["edge.length"])
@@ -60,11 +61,13 @@ def _check(z, Qs, pids, R, seed, off=0, observe=None, device_twin=True, **opt):
     worst = 0.0
     for k in range(K):
         pid = pids2[k if pids2.shape[0] > 1 else 0]
-        wt, ws, wn = simref.simulate(edge, lens, Qs[k], pid, R, seed, replica_offset=off + k * R, observe=observe)
-        assert np.array_equal(tips[k], wt), k
-        assert np.array_equal(nodes[k], wn), k
-        assert np.array_equal(stats[k][:, n:], ws[:, n:]), k            # counts and the root column
-        worst = max(worst, float(np.max(np.abs(stats[k][:, :n] - ws[:, :n]))))
+        for r0, cnt in ([(0, R)] if twin_rows is None else twin_rows):
+            wt, ws, wn = simref.simulate(edge, lens, Qs[k], pid, cnt, seed, replica_offset=off + k * R + r0, observe=observe)
+            rows = slice(r0, r0 + cnt)
+            assert np.array_equal(tips[k][rows], wt), k
+            assert np.array_equal(nodes[k][rows], wn), k
+            assert np.array_equal(stats[k][rows, n:], ws[:, n:]), k     # counts and the root column
+            worst = max(worst, float(np.max(np.abs(stats[k][rows, :n] - ws[:, :n]))))
         if device_twin:
             dt, ds, dn, dm = api.simulate_histories(z, Qs[k], pid, R, observe=observe, nodes=True, maps=True, seed=seed,
                                                     replica_offset=off + k * R)
