@@ -182,7 +182,12 @@ typedef struct phm_debug_options {
   int32_t expect_chunk;        /* > 0: phm_expected_stats and phm_expected_through_time run at most this many sites (rounded up to
                                   64) per pass and this many branches, points or sub-branches per launch (default 0: sites by free
                                   HBM, the rest by a 256 MB scratch); the results do not depend on it */
-  int32_t reserved[3];
+  int32_t sweep_parts;         /* (tile, branch) mapping, n <= 4, one launch per tree level: contiguous groups of tiles whose sweeps
+                                  phm_engine_run issues on streams of their own (part 0 on the caller's), so that the narrow tree levels
+                                  and reductions of one part run beside the branch kernel of another: 0 = automatic, 1 .. 4 = forced
+                                  (never more parts than tiles).  Same bits.  With more than one part the phase times of
+                                  phm_engine_phase_ms are summed over parts that share the chip and exceed last_run_ms */
+  int32_t reserved[2];
 } phm_debug_options;
 
 typedef struct phm_info {

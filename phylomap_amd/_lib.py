@@ -64,7 +64,8 @@ class DebugOptions(C.Structure):
     """phm_debug_options: measurement / test aids, per thread (phm_set_debug_options)."""
     _fields_ = [("pruning_form", C.c_int32), ("phase_timing", C.c_int32), ("fail_recovery", C.c_int32),
                 ("branch_group", C.c_int32), ("level_groups", C.c_int32), ("q_timing", C.c_int32),
-                ("pade_pivot_min", C.c_double), ("expect_chunk", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("pade_pivot_min", C.c_double), ("expect_chunk", C.c_int32), ("sweep_parts", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class Info(C.Structure):
@@ -267,7 +268,7 @@ MAPPING = {"auto": 0, "replicas": 1, "branches": 2, "tiles": 3}
 
 def set_debug_options(**kw):
     """Install this thread's phm_debug_options (measurement / test aids; no arguments = defaults): pruning_form, phase_timing,
-    fail_recovery, branch_group, level_groups, q_timing, pade_pivot_min, expect_chunk."""
+    fail_recovery, branch_group, level_groups, q_timing, pade_pivot_min, expect_chunk, sweep_parts."""
     d = DebugOptions()
     for k, v in kw.items():
         setattr(d, k, float(v) if k == "pade_pivot_min" else int(v))
@@ -275,7 +276,7 @@ def set_debug_options(**kw):
 
 
 _DEBUG_KEYS = ("pruning_form", "phase_timing", "fail_recovery", "branch_group", "level_groups", "q_timing", "pade_pivot_min",
-               "expect_chunk")
+               "expect_chunk", "sweep_parts")
 
 
 def make_options(seed=0, n_replicas=1, replica_offset=0, reduce=False, tips_per_replica=False, device=-1,

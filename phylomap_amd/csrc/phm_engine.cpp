@@ -631,13 +631,16 @@ inline int tiles_cnt_copies(int tiles) {
   return c;
 }
 
+// branches per wave of the (tile, branch) kernel for n <= 4: one while waves are scarce, up to 16 once there are 65 536 of them anyway
+int32_t tiles_branch_group(int tiles, int n_edge) { return (int32_t)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)tiles * n_edge / 65536)); }
+
 // Engine state of the wave-per-(tile, branch) mapping (phm_tiles.hip).
 template <int NS>
 void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& o) {
   fill_common(e, o, p);
   p.klong = e->nw_klong;
-  // branches per wave of the branch kernel: one while waves are scarce, up to 16 once there are 65 536 of them anyway
-  p.group = (int32_t)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)e->tiles * p.n_edge / 65536));
+  p.tile0 = 0; p.tiles_part = e->tiles;              // phm_engine_run narrows its copies to the parts of a sweep
+  p.group = tiles_branch_group(e->tiles, p.n_edge);
   p.n_groups = (p.n_edge + p.group - 1) / p.group;
   p.n_chunks = (p.n_groups + phm::TILES_CHUNK - 1) / phm::TILES_CHUNK;
   p.rows = e->nw_total_cap;
@@ -653,7 +656,7 @@ void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& 
   p.mstate = e->d_wt_mstate.p ? e->d_wt_mstate.as<uint8_t>() : nullptr;      // long paths (tiles_setup)
   p.pdw = e->d_tl_pdw.as<double>(); p.pchunk = e->d_tl_pchunk.as<double>(); p.cnt = e->d_tl_cnt.as<uint32_t>();
   p.cnt_copies = tiles_cnt_copies(e->tiles);
-  p.pseg = e->d_tl_pseg.as<uint32_t>(); p.segprev = e->d_tl_segprev.as<uint32_t>();
+  p.pseg = e->d_tl_pseg.as<uint32_t>(); p.segprev = e->d_tl_segprev.as<uint32_t>(); p.gseg = e->d_tl_gseg.p ? e->d_tl_gseg.as<uint32_t>() : nullptr;
 }
 
 // The slots of the (tile, item) mappings: rows of 64 lanes, addressed with 32-bit offsets (phm_tiles.hip, phm_wtiles.hip)
@@ -692,7 +695,9 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   const size_t ms_bytes = long_paths ? (size_t)tiles * rows * 64 : 0;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + stats_bytes(e) + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
+  const int group = tiles_branch_group(tiles, E);      // as fill_tile_params sets it; one branch per wave: no segment rows (phm_tiles.h)
+  const size_t gseg_bytes = group > 1 ? sizeof(uint32_t) * (size_t)tiles * ((E + group - 1) / group) * 64 : 0;
+  const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + gseg_bytes + pl_bytes + stats_bytes(e) + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
   if (int32_t st = check_hbm(need, free_b)) return st;
   HIPCHK(upload(e->d_up, s.up)); HIPCHK(upload(e->d_down, s.down));
   if (int32_t st = build_level_orders(e)) return st;
@@ -707,11 +712,12 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   HIPCHK(e->d_PL.alloc(pl_bytes));
   HIPCHK(e->d_nstate.alloc((size_t)tiles * Nn * 64));
   HIPCHK(e->d_tl_pdw.alloc(pdw_bytes));
+  if (gseg_bytes) HIPCHK(e->d_tl_gseg.alloc(gseg_bytes));
   HIPCHK(e->d_tl_pchunk.alloc(sizeof(double) * (size_t)tiles * n_chunks * n * 64));
   HIPCHK(e->d_tl_cnt.alloc(sizeof(uint32_t) * (size_t)tiles * tiles_cnt_copies(tiles) * n * n * 64));
   HIPCHK(e->d_tl_pseg.alloc(sizeof(uint32_t) * (size_t)tiles * n_chunks * 64)); HIPCHK(e->d_tl_segprev.alloc(sizeof(uint32_t) * tiles));
   if (int32_t st = alloc_stats(e)) return st;
-  e->bytes = (int64_t)(2 * dw_bytes + ms_bytes + pdw_bytes + pl_bytes + e->d_stats.bytes + e->d_red.bytes + e->d_mcount.bytes + e->d_tl_pchunk.bytes +
+  e->bytes = (int64_t)(2 * dw_bytes + ms_bytes + pdw_bytes + gseg_bytes + pl_bytes + e->d_stats.bytes + e->d_red.bytes + e->d_mcount.bytes + e->d_tl_pchunk.bytes +
                        sizeof(double) * 3 * tab);
   HIPCHK(hipMemset(e->d_nstate.p, 0, e->d_nstate.bytes));
   HIPCHK(hipMemset(e->d_tl_cnt.p, 0, e->d_tl_cnt.bytes));
@@ -1220,6 +1226,35 @@ int32_t phm_engine_create_impl(const phm_tree* trees, int32_t n_trees, const phm
   return PHM_OK;
 }
 
+// Parts of a (tile, branch) sweep for n <= 4.  A sweep of one engine is one dependent chain of ~65 launches: the
+// tree passes and reductions wait on memory for half of their wave cycles, the branch kernel is bound by VALU issue, and neither
+// can use what the other leaves.  Tiles do not read each other's state from the first pruning level to the statistics row, so
+// contiguous groups of tiles run their sweeps on streams of their own.  The parts start together and nothing holds them apart; the
+// kernel trace shows that after a sweep or two one part's tree passes and reductions run beside the other part's branch kernel all
+// the same (a deliberate offset was measured and removed: docs/EXPERIMENTS.md).  Only the launch-per-level form takes
+// parts (every kernel of launch_tiles_sweep's level path derives its tile from TileParams::tile0 / tiles_part); the cluster kernels
+// of few tiles or deep trees, the maps replay and phm_wtiles.hip keep the one launch sequence.
+// Automatic: a part must still fill the chip several times over in the branch kernel -- TILES_PART_MIN_ROUNDS rounds of the
+// 8 waves x 1 024 SIMDs that are resident at a time -- or the tails of its launches cost more than the overlap returns.
+constexpr int64_t TILES_RESIDENT_WAVES = 8 * 1024;
+constexpr int64_t TILES_PART_MIN_ROUNDS = 4;      // 4.9 rounds a part (C3 at 16 and at 64 tiles) still gain 4 % and 3 %: docs/MEASUREMENTS.md, sweep parts
+constexpr int TILES_AUTO_PARTS = 2;                  // docs/MEASUREMENTS.md, sweep parts (four parts: the same time within the run-to-run spread)
+
+static int tiles_sweep_parts(const phm_engine* e, int n_iters) {
+  if (e->mapping != PHM_MAP_TILES || e->wide() || !e->nw_tier_off.empty() || n_iters <= 0) return 1;
+  if (e->maps.mode != phm::MAPS_OFF)                 // a recorded iteration replays its maps over all tiles in one launch
+    for (int it = e->iters_done; it < e->iters_done + n_iters; ++it)
+      if (it < (int)e->maps.j_of_iter.size() && e->maps.j_of_iter[it] >= 0) return 1;
+  int parts = e->dbg.sweep_parts;
+  if (parts <= 0) {
+    const int E = e->sched.n_edge;
+    const int g = tiles_branch_group(e->tiles, E);
+    const int64_t waves = (int64_t)e->tiles * ((E + g - 1) / g);      // of one branch-kernel launch over all tiles
+    parts = (int)std::min<int64_t>(TILES_AUTO_PARTS, waves / (TILES_PART_MIN_ROUNDS * TILES_RESIDENT_WAVES));
+  }
+  return std::max(1, std::min({parts, (int)phm_engine::MAX_PARTS, e->tiles}));
+}
+
 extern "C" {
 
 int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
@@ -1243,12 +1278,50 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
       small_n(e, [&](auto& p) { le = phm::launch_narrow_stats(p.br, e->iters_done + n_iters - 1, stream); });
     HIPCHK(le);
   } else if (e->mapping == PHM_MAP_TILES) {
+    const int parts = tiles_sweep_parts(e, n_iters);
+    const int level_launches = (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;      // one launch per level and pass, root, branch kernel, two reductions
+                                                                                             // (the node levels of phm_tiles.hip number the edge levels)
     e->phase_iters = 0;
+    e->phase_parts = parts;
     if (e->phase_timing) {
-      while ((int)e->phase_ev.size() < 5 * n_iters) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); e->phase_ev.push_back(ev); }
+      while ((int)e->phase_ev.size() < 5 * n_iters * parts) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); e->phase_ev.push_back(ev); }
       e->phase_iters = n_iters;
     }
-    for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
+    if (parts > 1) {
+      // fork: every side stream behind ev0 (all the caller's earlier work); sweeps to the parts round-robin, sweep by sweep, all
+      // parts starting together (holding part p + 1 back behind part p's branch kernel was measured and lost, docs/EXPERIMENTS.md);
+      // join: the caller's stream behind the last launch of every side stream, before ev1
+      hipStream_t ps[phm_engine::MAX_PARTS] = {stream, nullptr, nullptr, nullptr};
+      for (int q = 1; q < parts; ++q) {
+        if (!e->part_join[q - 1]) HIPCHK(hipEventCreateWithFlags(&e->part_join[q - 1], hipEventDisableTiming));
+        if (!e->part_stream[q - 1]) HIPCHK(hipStreamCreateWithFlags(&e->part_stream[q - 1], hipStreamNonBlocking));
+        ps[q] = e->part_stream[q - 1];
+      }
+      int forked = 0;
+      hipError_t fe = hipSuccess;
+      for (int q = 1; q < parts && fe == hipSuccess; ++q) { fe = hipStreamWaitEvent(ps[q], e->ev0, 0); if (fe == hipSuccess) forked = q; }
+      le = fe;
+      const int base = e->tiles / parts, extra = e->tiles % parts;      // sizes differ by at most one tile
+      for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
+        const int it = e->iters_done + i;
+        for (int q = 0, t0 = 0; q < parts && le == hipSuccess; ++q) {
+          const int nt = base + (q < extra ? 1 : 0);
+          hipEvent_t* pev = e->phase_timing ? &e->phase_ev[5 * ((size_t)q * n_iters + i)] : nullptr;
+          small_n(e, [&](auto& p) {
+            auto part = p.tl;
+            part.tile0 = t0; part.tiles_part = nt;
+            le = phm::launch_tiles_sweep(part, e->nw_up_off, e->nw_node_off, e->nw_tier_off, it, ps[q], pev, nullptr);
+          });
+          launches += level_launches;
+          t0 += nt;
+        }
+      }
+      for (int q = 1; q <= forked; ++q) {            // joined whatever happened above: no side stream outlives the run unobserved
+        hipError_t je = hipEventRecord(e->part_join[q - 1], ps[q]);
+        if (je == hipSuccess) je = hipStreamWaitEvent(stream, e->part_join[q - 1], 0);
+        if (le == hipSuccess) le = je;
+      }
+    } else for (int i = 0; i < n_iters && le == hipSuccess; ++i) {
       const int it = e->iters_done + i;
       hipEvent_t* pev = e->phase_timing ? &e->phase_ev[5 * (size_t)i] : nullptr;
       phm::McmcMapsLaunch ml;                // a recorded iteration of the stochastic maps: the replay kernel before the branch kernel
@@ -1262,8 +1335,7 @@ int32_t phm_engine_run(phm_engine* e, int32_t n_iters, void* hip_stream) {
       if (clusters && e->wide())             // 5 .. 32 states on a deep tree: the node draws by tier, the pruning pass too when it runs on the band kernel
         launches += (e->pwt.band_up > 0 && !e->wt_sparse.kernel ? tiers : (int)e->nw_up_off.size() - 1) + tiers + 4;
       else
-        launches += clusters ? 2 * tiers + 3      // a launch per tier and pass, branch kernel, two reductions
-                             : (int)(e->nw_up_off.size() + e->nw_down_off.size()) + 2;      // (the node levels of phm_tiles.hip number the edge levels)
+        launches += clusters ? 2 * tiers + 3 : level_launches;      // clusters: a launch per tier and pass, branch kernel, two reductions
     }
     HIPCHK(le);
   } else {
@@ -1344,8 +1416,8 @@ int32_t phm_engine_sync(phm_engine* e) {
     e->last_ms = ms;
     e->timing_pending = false;
     for (double& v : e->phase_ms) v = 0.0;
-    for (int i = 0; i < e->phase_iters; ++i)
-      for (int ph = 0; ph < 4; ++ph) {
+    for (int i = 0; i < e->phase_iters * e->phase_parts; ++i)      // summed over sweeps and parts: parts share the chip, so the four phases
+      for (int ph = 0; ph < 4; ++ph) {                             // of a run with several parts add up to more than last_ms
         float pm = 0.f;
         HIPCHK(hipEventElapsedTime(&pm, e->phase_ev[5 * (size_t)i + ph], e->phase_ev[5 * (size_t)i + ph + 1]));
         e->phase_ms[ph] += pm;

@@ -370,7 +370,19 @@ struct phm_engine {
   phm::WideBranchParams pwb;                  // n > 4, PHM_MAP_BRANCHES: one wave per (replica, branch) (phm_wbranch.hip)
   // wave per (tile, branch) mapping for 10^2 .. 10^5 replicas (phm_tiles.hip); shares the level schedules and long tables
   std::vector<int32_t> tl_slot;                    // first row of every branch slot
-  DevBuf d_tl_slot, d_tl_pdw, d_tl_pchunk, d_tl_cnt, d_tl_estate, d_tl_pseg, d_tl_segprev;
+  DevBuf d_tl_slot, d_tl_pdw, d_tl_pchunk, d_tl_cnt, d_tl_estate, d_tl_pseg, d_tl_segprev, d_tl_gseg;
+  // Sweep parts (phm_engine_run): contiguous groups of tiles, part 0 on the caller's stream, part p > 0 on
+  // part_stream[p - 1].  Forked from ev0 and joined before ev1 inside every run: nothing outside phm_engine_run sees these streams.
+  static constexpr int MAX_PARTS = 4;
+  hipStream_t part_stream[MAX_PARTS - 1] = {nullptr, nullptr, nullptr};
+  hipEvent_t part_join[MAX_PARTS - 1] = {nullptr, nullptr, nullptr};      // the last launch of a side stream in a run
+  int phase_parts = 1;                             // parts of the last run (phase_ev: [part][iteration][5])
+  void release_parts() {
+    for (int i = 0; i < MAX_PARTS - 1; ++i) {
+      if (part_stream[i]) { (void)hipStreamDestroy(part_stream[i]); part_stream[i] = nullptr; }
+      if (part_join[i]) { (void)hipEventDestroy(part_join[i]); part_join[i] = nullptr; }
+    }
+  }
   // 5..64 states, PHM_MAP_TILES: one lane per replica, wave per (tile, item), pruning on the matrix cores (phm_wtiles.hip)
   phm::WtParams pwt;
   DevBuf d_wt_dwfx, d_wt_segacc, d_wt_B2, d_wt_totL, d_wt_pair_slot, d_wt_slot_col, d_wt_B2band, d_wt_mstate, d_wt_dwfx_tile, d_wt_cnt_tile;
@@ -380,7 +392,7 @@ struct phm_engine {
   int sparse_req = 0;                              // phm_options.sparse_chains
   phm_debug_options dbg = {};                      // the creating thread's phm_set_debug_options at creation
   bool phase_timing = false;                       // phm_debug_options.phase_timing: HIP events between the phases of a (tile, item) sweep
-  std::vector<hipEvent_t> phase_ev;                // 5 per iteration of the last run
+  std::vector<hipEvent_t> phase_ev;                // 5 per part and iteration of the last run
   int phase_iters = 0;
   double phase_ms[4] = {0.0, 0.0, 0.0, 0.0};       // pruning levels, node draws, branch kernel, reductions (sums over the last run)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -408,11 +420,13 @@ struct phm_engine {
                      &d_nw_up_order, &d_nw_down_order, &d_nw_node_order, &d_nw_border, &d_nw_off, &d_nw_colL, &d_nw_rowL, &d_nw_maskL, &d_nw_mcount,
                      &d_nw_dwA, &d_nw_dwB, &d_nw_mstate, &d_nw_mlen, &d_nw_estate, &d_nw_part, &d_nw_rowbuf, &d_nw_down_lv, &d_nw_dmap, &d_nw_dmap_edge, &d_nw_walk_off, &d_nw_edge_parent, &d_nw_cl_nodes, &d_nw_cl_item_off, &d_nw_cl_lvl_ptr, &d_nw_cl_lvl_off, &d_ell_col, &d_ell_val,
                      &d_ell2_col, &d_ell2_val, &d_wb_cnt, &d_tl_slot, &d_tl_pdw, &d_tl_pchunk, &d_tl_cnt, &d_tl_estate, &d_tl_pseg,
-                     &d_tl_segprev, &d_wt_dwfx, &d_wt_segacc, &d_wt_B2, &d_wt_totL, &d_wt_pair_slot, &d_wt_slot_col, &d_wt_B2band, &d_wt_mstate, &d_wt_dwfx_tile, &d_wt_cnt_tile, &d_wt_coef};
+                     &d_tl_segprev, &d_tl_gseg, &d_wt_dwfx, &d_wt_segacc, &d_wt_B2, &d_wt_totL, &d_wt_pair_slot, &d_wt_slot_col, &d_wt_B2band, &d_wt_mstate, &d_wt_dwfx_tile, &d_wt_cnt_tile, &d_wt_coef};
     for (DevBuf* b : all) b->reset();
+    release_parts();
   }
   ~phm_engine() {
     delete fwd;
+    release_parts();
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     for (hipEvent_t ev : phase_ev) (void)hipEventDestroy(ev);

@@ -49,6 +49,8 @@ struct TileParams {
   int32_t klong;                             // rows of the long chain tables
   int32_t group, n_groups;                   // branches walked by one wave of the branch kernel; ceil(n_edge / group)
   int32_t n_chunks;                          // ceil(n_groups / TILES_CHUNK)
+  int32_t tile0, tiles_part;                 // the tiles of this launch_tiles_sweep: [tile0, tile0 + tiles_part) (one part: 0, n_tiles; the engine runs
+                                             //   the parts of a sweep on streams of their own); every array below stays indexed by the global tile
   uint32_t seed_lo, seed_hi;
   int64_t rows;                              // rows of one tile in one dwell buffer (sum of the slot sizes)
   double B2[NS * NS], Bc[NS * NS], scale[NS], pid[NS];
@@ -74,6 +76,8 @@ struct TileParams {
   double* PL;                                // [tile][n_node][NS][64]
   uint8_t* nstate;                           // [tile][n_node][64]
   double* pdw;                               // [tile][n_edge][NS][64] dwell sums of every group of branches (n_groups rows used)
+  uint32_t* gseg;                            // group > 1: [tile][n_groups][64] segments the branches of every group hold after the sweep (written
+                                             //   beside pdw); NULL with one branch per wave, where tiles_chunk_kernel walks mcount itself
   double* pchunk;                            // [tile][n_chunks][NS][64] first-stage sums
   uint32_t* cnt;                             // [tile][cnt_copies][NS*NS][64] transition counters of the sweep (integer atomics)
   int32_t cnt_copies;                        // power of two: the waves of a tile spread their atomics over this many copies (few tiles:
@@ -96,6 +100,8 @@ struct McmcMapsLaunch;      // phm_mcmc_maps.h
 // up_off / node_off: level boundaries into up_order / node_order; tier_off: cluster tiers (ClusterPlan::tier_off) when p.cl_nodes is set
 // maps: a recorded sweep of the stochastic maps: the replay kernel runs after the node draws, before the branch
 // kernel (it counts with the branch phase)
+// The sweep covers the tiles [p.tile0, p.tile0 + p.tiles_part) only; tiles do not read each other's state, so sweeps over disjoint
+// tile ranges may run at the same time on different streams (the cluster kernels and the maps replay take the whole range: tile0 = 0)
 template <int NS>
 hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t>& up_off,
                               const std::vector<int32_t>& node_off, const std::vector<int32_t>& tier_off, int it, hipStream_t stream,

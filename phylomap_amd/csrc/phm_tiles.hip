@@ -108,8 +108,8 @@ __global__ __launch_bounds__(TILES_BLOCK) void tiles_up_kernel(TileParams<NS> p,
   const uint32_t lane = threadIdx.x & 63;
   const int item = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: tile, schedule record and tile bases in scalar registers
   const int n_lvl = end - begin;
-  if (item >= n_lvl * p.n_tiles) return;
-  const int tile = item / n_lvl;
+  if (item >= n_lvl * p.tiles_part) return;
+  const int tile = p.tile0 + item / n_lvl;
   const UpStep st = p.up[p.up_order[begin + item % n_lvl]];
   uint32_t err = 0;
   up_item<NS>(p, tile, st, lane, err);
@@ -187,8 +187,9 @@ __device__ __forceinline__ void draw_root(const TileParams<NS>& p, int tile, int
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_root_kernel(TileParams<NS> p, int it) {
   const int lane = threadIdx.x & 63;
-  const int tile = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (tile >= p.n_tiles) return;
+  const int t = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (t >= p.tiles_part) return;
+  const int tile = p.tile0 + t;
   uint32_t err = 0;
   draw_root<NS>(p, tile, it, lane, err);
   if (err) atomicOr(p.err, err);
@@ -291,7 +292,7 @@ __device__ __forceinline__ void with_side_kinds(bool draw_tips, int child0, int 
 // lane's 32-bit byte offset (at(), phm_device.h)
 template <int NS>
 __device__ __forceinline__ void node_record(const TileParams<NS>& p, NodeLoads<NS>& d, int item, int n_lvl, int begin) {
-  d.tile = item / n_lvl;
+  d.tile = p.tile0 + item / n_lvl;
   const int32_t* rec = reinterpret_cast<const int32_t*>(p.up + sched_word(p.node_order, begin + item % n_lvl));
   static_assert(sizeof(UpStep) == 5 * sizeof(int32_t), "UpStep: parent, two children, two edges");
   d.st.parent = sched_word(rec, 0);
@@ -370,7 +371,7 @@ template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_down_kernel(TileParams<NS> p, int it, int begin, int end) {
   const uint32_t lane = threadIdx.x & 63;
   const int n_lvl = end - begin;
-  const int n_items = n_lvl * p.n_tiles;
+  const int n_items = n_lvl * p.tiles_part;
   const int stride = gridDim.x * (TILES_BLOCK / 64);
   const bool draw_tips = p.ks && p.tip_masks;
   uint32_t err = 0;
@@ -442,12 +443,12 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
   if (threadIdx.x < NS * NS) s_B2[threadIdx.x] = p.B2[threadIdx.x];
   if (threadIdx.x < NS) s_scale[threadIdx.x] = p.scale[threadIdx.x];
   __syncthreads();
-  if (item >= p.n_groups * p.n_tiles) return;        // whole waves only; no barrier below this line
+  if (item >= p.n_groups * p.tiles_part) return;     // whole waves only; no barrier below this line
   // neighbouring waves take the same branches of different tiles: similar run times inside a workgroup, longest branches
   // first.  A wave walks `group` consecutive entries of the order (1 when replicas are few, up to 16 when there are plenty of
   // waves anyway) and writes ONE partial dwell sum for all of them.
-  const int tile = item % p.n_tiles;
-  const int grp = item / p.n_tiles;
+  const int tile = p.tile0 + item % p.tiles_part;
+  const int grp = item / p.tiles_part;
   double* s_dw = s_dw_all + wave * NS * 64;
   uint16_t* s_cnt = s_cnt_all + wave * NCNT * 64;
   const uint32_t rep = (uint32_t)(p.replica_offset + tile * 64 + lane);
@@ -469,6 +470,7 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
     }
   };
   uint32_t pending = 0;                              // segments whose transitions sit in the 16-bit counters
+  uint32_t held = 0;                                 // segments the group's branches hold after this sweep (tiles_chunk_kernel: the read + written counter)
   const int q1 = min((grp + 1) * p.group, p.n_edge);
   for (int q = grp * p.group; q < q1; ++q) {
   const int b = p.branch_order[q];
@@ -678,8 +680,10 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
   if (mnew > cap) mnew = cap;
   if (mnew > 65535) { err |= DERR_CAPACITY; mnew = 65535; }
   mct[b * 64 + lane] = (uint16_t)mnew;
+  held += (uint32_t)mnew;
   }      // next branch of the group
   flush_counts();
+  if (p.group > 1) p.gseg[((size_t)tile * p.n_groups + grp) * 64 + lane] = held;      // one branch per wave: the row would be mcount's, twice as wide
 
   double* pd = p.pdw + (((size_t)tile * p.n_edge + grp) * NS) * 64 + lane;      // [tile][group][NS][64] (n_edge rows reserved)
 #pragma unroll
@@ -687,29 +691,41 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
   if (err) atomicOr(p.err, err);
 }
 
-// Dwell sums, second stage: a wave per (tile, chunk of TILES_CHUNK group partials), added in group order; the segments now
-// held by an equal share of the edges (for the read + written counter; one global atomic per wave would serialise).
+// Dwell sums, second stage: a wave per (tile, chunk of TILES_CHUNK group partials), added in group order; the segments now held
+// by a share of the branches (for the read + written counter; one global atomic per wave would serialise).  With several branches
+// per wave of the branch kernel the share is the chunk's groups and the numbers come from the rows that kernel left beside its dwell
+// sums (walking mcount again was 2 B per unit of traffic for this number alone); with one branch per wave (few tiles) a row per
+// group would cost 4 B written and 4 B read per unit, so there the chunk walks an equal share of mcount as it always did.
 template <int NS>
 __global__ __launch_bounds__(TILES_BLOCK) void tiles_chunk_kernel(TileParams<NS> p) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * (TILES_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (item >= p.n_chunks * p.n_tiles) return;
-  const int tile = item / p.n_chunks, chunk = item % p.n_chunks;
+  if (item >= p.n_chunks * p.tiles_part) return;
+  const int tile = p.tile0 + item / p.n_chunks, chunk = item % p.n_chunks;
   const int b0 = chunk * TILES_CHUNK, b1 = min(b0 + TILES_CHUNK, p.n_groups);
   double s[NS];
 #pragma unroll
   for (int c = 0; c < NS; ++c) s[c] = 0.0;
   const double* src = p.pdw + ((size_t)tile * p.n_edge * NS) * 64 + lane;
-  for (int b = b0; b < b1; ++b)
+  uint32_t segs = 0;
+  if (p.group > 1) {                                 // wave-uniform
+    const uint32_t* gs = p.gseg + ((size_t)tile * p.n_groups) * 64 + lane;
+    for (int b = b0; b < b1; ++b) {
 #pragma unroll
-    for (int c = 0; c < NS; ++c) s[c] += src[((size_t)b * NS + c) * 64];
+      for (int c = 0; c < NS; ++c) s[c] += src[((size_t)b * NS + c) * 64];
+      segs += gs[(size_t)b * 64];                                                // integer sums: exact in any order
+    }
+  } else {
+    for (int b = b0; b < b1; ++b)
+#pragma unroll
+      for (int c = 0; c < NS; ++c) s[c] += src[((size_t)b * NS + c) * 64];
+    const uint16_t* mc = p.mcount + ((size_t)tile * p.n_edge) * 64 + lane;
+    const int per = (p.n_edge + p.n_chunks - 1) / p.n_chunks;
+    for (int b = chunk * per; b < min((chunk + 1) * per, p.n_edge); ++b) segs += mc[(size_t)b * 64];
+  }
   double* dst = p.pchunk + (((size_t)tile * p.n_chunks + chunk) * NS) * 64 + lane;
 #pragma unroll
   for (int c = 0; c < NS; ++c) dst[c * 64] = s[c];
-  uint32_t segs = 0;
-  const uint16_t* mc = p.mcount + ((size_t)tile * p.n_edge) * 64 + lane;
-  const int per = (p.n_edge + p.n_chunks - 1) / p.n_chunks;
-  for (int b = chunk * per; b < min((chunk + 1) * per, p.n_edge); ++b) segs += mc[(size_t)b * 64];
   p.pseg[((size_t)tile * p.n_chunks + chunk) * 64 + lane] = segs;
 }
 
@@ -730,7 +746,7 @@ __global__ __launch_bounds__(64 * TILES_STATS_WAVES) void tiles_stats_kernel(Til
   __shared__ uint32_t s_sg[SW][64];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int tile = blockIdx.x;
+  const int tile = p.tile0 + blockIdx.x;
   const int rep_local = tile * 64 + lane;
   const bool valid = rep_local < p.n_rep;
   {
@@ -851,13 +867,13 @@ hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t
   } else {
     for (size_t l = 0; l + 1 < up_off.size(); ++l) {
       const int n = up_off[l + 1] - up_off[l];
-      if (n > 0) hipLaunchKernelGGL(tiles_up_kernel<NS>, blocks((int64_t)n * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]);
+      if (n > 0) hipLaunchKernelGGL(tiles_up_kernel<NS>, blocks((int64_t)n * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]);
     }
     mark(1);
-    hipLaunchKernelGGL(tiles_root_kernel<NS>, blocks(p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
+    hipLaunchKernelGGL(tiles_root_kernel<NS>, blocks(p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it);
     for (size_t l = 0; l + 1 < node_off.size(); ++l) {
       const int n = node_off[l + 1] - node_off[l];
-      if (n > 0) hipLaunchKernelGGL(tiles_down_kernel<NS>, pblocks((int64_t)n * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it, node_off[l], node_off[l + 1]);
+      if (n > 0) hipLaunchKernelGGL(tiles_down_kernel<NS>, pblocks((int64_t)n * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it, node_off[l], node_off[l + 1]);
     }
   }
   mark(2);
@@ -866,16 +882,16 @@ hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t
     if (me != hipSuccess) return me;
   }
   if (p.mstate) {
-    if (p.ks) hipLaunchKernelGGL((tiles_branch_kernel<NS, true, true>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
-    else hipLaunchKernelGGL((tiles_branch_kernel<NS, false, true>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
+    if (p.ks) hipLaunchKernelGGL((tiles_branch_kernel<NS, true, true>), blocks((int64_t)p.n_groups * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it);
+    else hipLaunchKernelGGL((tiles_branch_kernel<NS, false, true>), blocks((int64_t)p.n_groups * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it);
   } else {
-    if (p.ks) hipLaunchKernelGGL((tiles_branch_kernel<NS, true, false>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
-    else hipLaunchKernelGGL((tiles_branch_kernel<NS, false, false>), blocks((int64_t)p.n_groups * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p, it);
+    if (p.ks) hipLaunchKernelGGL((tiles_branch_kernel<NS, true, false>), blocks((int64_t)p.n_groups * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it);
+    else hipLaunchKernelGGL((tiles_branch_kernel<NS, false, false>), blocks((int64_t)p.n_groups * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p, it);
   }
   mark(3);
-  hipLaunchKernelGGL(tiles_chunk_kernel<NS>, blocks((int64_t)p.n_chunks * p.n_tiles), dim3(TILES_BLOCK), 0, stream, p);
-  if (p.ks) hipLaunchKernelGGL((tiles_stats_kernel<NS, true>), dim3(p.n_tiles), dim3(64 * TILES_STATS_WAVES), 0, stream, p, it);
-  else hipLaunchKernelGGL((tiles_stats_kernel<NS, false>), dim3(p.n_tiles), dim3(64 * TILES_STATS_WAVES), 0, stream, p, it);
+  hipLaunchKernelGGL(tiles_chunk_kernel<NS>, blocks((int64_t)p.n_chunks * p.tiles_part), dim3(TILES_BLOCK), 0, stream, p);
+  if (p.ks) hipLaunchKernelGGL((tiles_stats_kernel<NS, true>), dim3(p.tiles_part), dim3(64 * TILES_STATS_WAVES), 0, stream, p, it);
+  else hipLaunchKernelGGL((tiles_stats_kernel<NS, false>), dim3(p.tiles_part), dim3(64 * TILES_STATS_WAVES), 0, stream, p, it);
   mark(4);
   return hipGetLastError();
 }
