@@ -476,7 +476,7 @@ int32_t phm_sample_histories_models(const phm_tree* x, int32_t n_states, int32_t
  * the one assignment of ALL nodes that maximises p(states of all nodes, tips_s | Q_k, pid_k) (Pupko et al. 2000: a max-product up
  * pass with back pointers, then a traceback; ties go to the smallest state, on the device's own P).  Every argument up to
  * site_of_model is phm_loglik_models', checked the same way before any device call.  2..8 states (9..64: PHM_ERR_UNSUPPORTED;
- * phm_expected_stats' node_post serves one wide model at a time).  An evaluation's index e is its index into loglik.
+ * phm_ancestral_models_wide serves those).  An evaluation's index e is its index into loglik.
  *   node_sel: n_sel 1-based ape node ids in 1 .. n_tips + n_node, tips and duplicates allowed: the J = n_sel nodes to report, in
  *     that order.  NULL with n_sel = 0: every node in id order (J = n_tips + n_node).  A bad entry is PHM_ERR_BAD_INPUT naming
  *     its 0-based index; so are n_sel < 0 and n_sel > 0 with node_sel NULL.
@@ -494,6 +494,21 @@ int32_t phm_ancestral_models(const phm_tree* x, int32_t n_states, int32_t n_mode
                              int32_t n_pid, const int32_t* observe, const int32_t* site_of_model,
                              const int32_t* node_sel, int32_t n_sel, const phm_options* opt,
                              double* loglik, double* node_post, int32_t* joint_states, double* joint_logp);
+
+/* ---- ancestral states of many rate matrices at 9..64 states ----
+ * phm_ancestral_models' arguments, argument for argument, with the same meaning, output layouts, NULL rules and refusals, for
+ * 9 <= n_states <= 64: amino acids, codons, hidden-rate models.  One state per lane, batched over models and sites; P_k(t_b) is
+ * phm_expected_stats' (Pade(6) with its squaring counts).  loglik is phm_loglik_models' value and node_post is
+ * phm_expected_stats' node_post of that model, both bit for bit; joint_states and joint_logp follow section 21's rules on the
+ * device's own P (a back pointer is one byte).  2..8 states: PHM_ERR_UNSUPPORTED naming phm_ancestral_models; outside 2..64:
+ * PHM_ERR_BAD_INPUT.  An evaluation whose log-likelihood is -inf, or whose model's Pade denominator met a zero pivot, gets
+ * loglik = -inf, NaN in node_post, 0 in joint_states and -inf in joint_logp; it does not fail the call.  n_devices / devices[]
+ * shard the models and phm_debug_options.expect_chunk caps the chunks of models, sites and level steps; neither changes an output
+ * bit.  phm_last_kernel_ms: device time of the call. */
+int32_t phm_ancestral_models_wide(const phm_tree* x, int32_t n_states, int32_t n_models, const double* Q, const double* pid,
+                                  int32_t n_pid, const int32_t* observe, const int32_t* site_of_model,
+                                  const int32_t* node_sel, int32_t n_sel, const phm_options* opt,
+                                  double* loglik, double* node_post, int32_t* joint_states, double* joint_logp);
 
 /* ---- forward simulation under many rate matrices in one call ----
  * K = n_models models (Q_k, pid_k), R = replicates histories each: one replicate dataset per posterior draw of the rates, R

@@ -27,7 +27,7 @@ EXPORTS = [
     "phm_last_kernel_ms", "phm_set_debug_options", "phm_sparse_kernel_source", "phm_simulate_histories",
     "phm_expected_stats", "phm_simulate_histories_maps", "phm_maketreelistEXP_maps", "phm_maketreelistMCMC_maps",
     "phm_expected_through_time", "phm_loglik_models", "phm_expected_stats_models", "phm_sample_histories_models",
-    "phm_gibbs_rates", "phm_ancestral_models", "phm_simulate_histories_models",
+    "phm_gibbs_rates", "phm_ancestral_models", "phm_simulate_histories_models", "phm_ancestral_models_wide",
 ]
 
 
@@ -184,6 +184,7 @@ def load():
                                            C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
                                            C.POINTER(Options), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+        L.phm_ancestral_models_wide.argtypes = L.phm_ancestral_models.argtypes
         L.phm_simulate_histories_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                                     C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                                     C.POINTER(Options), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

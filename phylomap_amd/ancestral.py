@@ -1,5 +1,5 @@
-"""Helpers around ``api.ancestral_states_models``: model weights, model-averaged node posteriors and the
-node id of a clade's ancestor.  numpy only, no device."""
+"""Helpers around ``api.ancestral_states_models`` (DESIGN.md sections 21 and 23): model weights, model-averaged node posteriors,
+the node id of a clade's ancestor and node posteriors collapsed onto what is observed.  numpy only, no device."""
 from __future__ import annotations
 
 import numpy as np
@@ -32,6 +32,23 @@ def model_average(node_post, weights=None, axis=0):
     for k in range(K):
         if w[k] > 0.0:
             out += w[k] * post[k]
+    return out
+
+
+def collapse_states(node_post, observe):
+    """Node posteriors of the OBSERVED character: ``node_post`` [..., n] summed over the states that share an observation -- the
+    amino acid behind the codons, the observed character behind hidden-rate classes.  ``observe``: the n 1-based observations of
+    the states, as given to ``api.ancestral_states_models``.  Returns [..., n_obs], n_obs = max(observe); a NaN row (an impossible
+    evaluation) stays NaN.  The joint reconstruction needs no function: ``observe[joint_states - 1]`` where ``joint_states`` > 0."""
+    post = np.asarray(node_post, dtype=np.float64)
+    obs = np.asarray(observe, dtype=np.int64).reshape(-1)
+    if post.ndim < 1 or obs.size != post.shape[-1]:
+        raise ValueError("observe must have one entry per state of node_post")
+    if obs.size == 0 or np.any(obs < 1):
+        raise ValueError("observe must hold 1-based observations")
+    out = np.zeros(post.shape[:-1] + (int(obs.max()),))
+    for i, o in enumerate(obs):                         # state order: the sums do not depend on how the states are grouped
+        out[..., o - 1] += post[..., i]
     return out
 
 

@@ -550,16 +550,19 @@ AncestralStates = namedtuple("AncestralStates", ["loglik", "node_post", "joint_s
 
 def ancestral_states_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, nodes=None, marginal=True, joint=True,
                             **opt):
-    """Ancestral states under K rate matrices in one call -> phm_ancestral_models: the marginal posterior
-    of every reported node's state and the JOINT reconstruction, the one assignment of all nodes that maximises
-    p(states, tips_s | Q_k, pid_k) (Pupko et al. 2000), with the models across the lanes (2..8 states).  ``Qs``, ``pid``, ``z``,
-    ``sites``, ``observe`` and ``site_of_model`` are ``loglik_models``'.  ``nodes``: 1-based ape node ids to report, tips and
-    duplicates allowed (``ancestral.mrca`` names a clade's ancestor); None: every node in id order.  Returns the named tuple
+    """Ancestral states under K rate matrices in one call for 2..64 states (DESIGN.md sections 21 and 23) -> phm_ancestral_models
+    (2..8 states, the models across the lanes) or phm_ancestral_models_wide (9..64 states, one state per lane): the marginal
+    posterior of every reported node's state and the JOINT reconstruction, the one assignment of all nodes that maximises
+    p(states, tips_s | Q_k, pid_k) (Pupko et al. 2000).  ``Qs``, ``pid``, ``z``, ``sites``, ``observe`` and ``site_of_model`` are
+    ``loglik_models``'.  ``nodes``: 1-based ape node ids to report, tips and duplicates allowed (``ancestral.mrca`` names a
+    clade's ancestor); None: every node in id order.  Returns the named tuple
     ``(loglik, node_post, joint_states, joint_logp, nodes)``: [K, S] (``loglik_models``' values bit for bit), [K, S, J, n],
     [K, S, J] 1-based TRUE states (a missing tip and the hidden state behind ``observe`` come out reconstructed) and [K, S]; with
     ``site_of_model`` the S axis is absent.  ``marginal=False`` / ``joint=False`` leave that part out (``None``; the other part is
     the same bit for bit).  ``nodes`` echoes the ids reported.  An impossible evaluation (``-inf``) has NaN posteriors, zero
-    states and ``joint_logp`` = ``-inf``.  Options: device, devices."""
+    states and ``joint_logp`` = ``-inf``.  Behind an ``observe`` map (codons -> amino acids, hidden-rate classes -> the observed
+    character) ``ancestral.collapse_states(node_post, observe)`` sums the posterior per observation and ``observe[x - 1]`` maps
+    ``joint_states``.  Options: device, devices."""
     if not marginal and not joint:
         raise ValueError("marginal and joint are both False: nothing to compute")
     L = _lib.load()
@@ -590,10 +593,11 @@ def ancestral_states_models(z, Qs, pid, sites=None, observe=None, site_of_model=
     post = np.zeros(shape + (J, n)) if marginal else None
     states = np.zeros(shape + (J,), dtype=np.int32) if joint else None
     jl = np.zeros(shape) if joint else None
-    _lib.check(L.phm_ancestral_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
-                                      _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), _lib._p(sel, C.c_int32),
-                                      0 if sel is None else sel.size, C.byref(a.opt), _lib._p(ll, C.c_double),
-                                      _lib._p(post, C.c_double), _lib._p(states, C.c_int32), _lib._p(jl, C.c_double)))
+    fn = L.phm_ancestral_models_wide if n > 8 else L.phm_ancestral_models
+    _lib.check(fn(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
+                  _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), _lib._p(sel, C.c_int32),
+                  0 if sel is None else sel.size, C.byref(a.opt), _lib._p(ll, C.c_double),
+                  _lib._p(post, C.c_double), _lib._p(states, C.c_int32), _lib._p(jl, C.c_double)))
     ids = np.arange(1, a.NT + 1, dtype=np.int32) if sel is None else sel.copy()
     return AncestralStates(ll, post, states, jl, ids)
 

@@ -1,0 +1,409 @@
+// phm_ancestral_wide.hip -- ancestral states for many rate matrices at 9..64 states: section 13's up, root,
+// down and posterior arithmetic (ex_tips_kernel, ex_up_kernel, ex_root_kernel, ex_down_kernel, ex_post_kernel of phm_expect.hip)
+// and section 21's joint reconstruction (phm_ancestral.hip), restated with ONE STATE PER LANE and batched over models and sites.
+//
+// A group of NP lanes (16 / 32 / 64 for 9..16 / 17..32 / 33..64 states) owns one (evaluation, node) item; lane a holds state a and
+// the lanes past n hold zeros.  A workgroup of 256 lanes takes (level step, model, tile of sites): it stages the step's two
+// transition matrices of ITS model in LDS once and its 256 / NP groups walk AW_WALK sites each through them.
+//   * lane a's chain over j = 0 .. n-1 is the serial fma chain of the one-lane kernels: same operands, same order, same bits
+//   * the maximum of a vector is a cross-lane fmax (exact in any order)
+//   * the ordered dot products (root, posterior) are one serial chain on the group's first lane, read from LDS
+//   * the root's argmax is the cross-lane maximum followed by the lowest lane that attains it
+// LDS: a matrix read as v[a] = sum_j P[a][j] c[j] is staged TRANSPOSED, sP[j * (NP + 1) + a], so for fixed j the lanes read
+// consecutive doubles (ds_read_b64: 32 lanes x 8 bytes = the 64 banks once) and the staging stores of consecutive j are NP + 1
+// doubles apart (odd: the 16 lanes of a ds_write_b64 group fall on 16 different bank pairs).  The down pass' O_c = P^T F reads
+// row-major P[k][a] consecutively as stored.  A group's child vector is an LDS broadcast; the rows of two groups of one half-wave
+// are NP + 2 doubles apart per vector, which keeps them on different banks at NP = 16.
+// Every loop is bounded by n, the step count or the site tile; the arithmetic of the joint reconstruction is explicit products.
+#include "phm_ancestral_wide.h"
+
+#include <algorithm>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+namespace phm {
+
+namespace {
+
+constexpr int AW_BLOCK = 256;
+constexpr int AW_WALK = 4;                     // sites a group walks through the staged matrices
+constexpr double AW_LN2 = 0.69314718055994530942;
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the function object of the current device: set once per (function,
+// device) to the most its class can ask for (n = NP: 70 784 bytes at 64 states, above the 64 KiB a launch gets unasked)
+hipError_t aw_allow_lds(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::vector<std::pair<const void*, int>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> guard(mu);
+  for (const auto& d : done) if (d.first == fn && d.second == dev) return hipSuccess;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.emplace_back(fn, dev);
+  return e;
+}
+
+template <int NP> struct AwShape {
+  static constexpr int G = AW_BLOCK / NP;      // groups (items) of a workgroup
+  static constexpr int LD = NP + 1;            // row of a staged matrix
+  static constexpr int VS = NP + 2;            // row of a staged vector
+};
+
+// doubles of LDS: two staged matrices, two vectors per group
+template <int NP> inline size_t aw_lds_doubles(int n) { return (size_t)2 * n * AwShape<NP>::LD + (size_t)2 * AwShape<NP>::G * AwShape<NP>::VS; }
+
+template <int NP> __device__ __forceinline__ double aw_group_max(double v) {
+  double m = fmax(0.0, v);
+#pragma unroll
+  for (int off = NP / 2; off >= 1; off >>= 1) m = fmax(m, __shfl_xor(m, off, NP));
+  return m;
+}
+
+// the value scaled by 2^-e with the maximum in [1/2, 1); e = 0 for an all-zero vector (ex_rescale)
+__device__ __forceinline__ double aw_rescale(double v, double mx, int& e) {
+  e = 0;
+  if (!(mx > 0.0)) return v;
+  (void)frexp(mx, &e);
+  return ldexp(v, -e);
+}
+
+// sP[j * LD + i] = P[i][j]
+template <int NP> __device__ __forceinline__ void aw_stage_t(double* sP, const double* __restrict__ P, int n) {
+  for (int e = threadIdx.x; e < n * n; e += AW_BLOCK) {
+    const int i = e / n, j = e - i * n;
+    sP[j * AwShape<NP>::LD + i] = P[e];
+  }
+}
+
+__global__ __launch_bounds__(AW_BLOCK) void aw_tips_kernel(AwParams p, int t0) {
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const size_t at = (size_t)blockIdx.x * AW_BLOCK + threadIdx.x;
+  if (at >= Ev * p.NP) return;
+  const size_t ev = at / p.NP;
+  const int a = (int)(at - ev * p.NP);
+  const int k = (int)(ev / p.Sc), s = (int)(ev - (size_t)k * p.Sc);
+  const int t = t0 + blockIdx.y;
+  const int y = p.tips[((size_t)k * p.tip_model + (size_t)s * p.tip_site) * p.n_tips + t];
+  p.L[((size_t)t * Ev + ev) * p.NP + a] = (a < p.n && (y == 0 || p.obs[a] == y)) ? 1.0 : 0.0;
+  if (a == 0) p.sL[(size_t)t * Ev + ev] = 0;
+}
+
+// grid: (step, model, site tile)
+template <int NP, bool JOINT>
+__global__ __launch_bounds__(AW_BLOCK) void aw_up_kernel(AwParams p, const UpStep* __restrict__ steps) {
+  constexpr int G = AwShape<NP>::G, LD = AwShape<NP>::LD, VS = AwShape<NP>::VS;
+  extern __shared__ __align__(16) double aw_lds[];
+  const int n = p.n;
+  double* sP0 = aw_lds;
+  double* sP1 = sP0 + n * LD;
+  double* sV = sP1 + n * LD;
+  const UpStep u = steps[blockIdx.x];
+  const int k = blockIdx.y;
+  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
+  const size_t Ev = (size_t)p.Kc * p.Sc, nn = (size_t)n * n;
+  const double* __restrict__ Pm = p.P + (size_t)k * p.n_edge * nn;
+  aw_stage_t<NP>(sP0, Pm + (size_t)u.edge[0] * nn, n);
+  aw_stage_t<NP>(sP1, Pm + (size_t)u.edge[1] * nn, n);
+  const bool tip0 = u.child[0] < 0, tip1 = u.child[1] < 0;
+  // sum-product: a child's row of L; max-product: a tip's row of L (0/1, exponent 0) or an internal child's row of M
+  const double* __restrict__ v0;
+  const double* __restrict__ v1;
+  const int32_t* __restrict__ e0;
+  const int32_t* __restrict__ e1;
+  if (JOINT) {
+    v0 = tip0 ? p.L + (size_t)(~u.child[0]) * Ev * NP : p.M + (size_t)u.child[0] * Ev * NP;
+    v1 = tip1 ? p.L + (size_t)(~u.child[1]) * Ev * NP : p.M + (size_t)u.child[1] * Ev * NP;
+    e0 = tip0 ? p.sL + (size_t)(~u.child[0]) * Ev : p.sM + (size_t)u.child[0] * Ev;
+    e1 = tip1 ? p.sL + (size_t)(~u.child[1]) * Ev : p.sM + (size_t)u.child[1] * Ev;
+  } else {
+    const size_t r0 = tip0 ? (size_t)(~u.child[0]) : (size_t)p.n_tips + u.child[0];
+    const size_t r1 = tip1 ? (size_t)(~u.child[1]) : (size_t)p.n_tips + u.child[1];
+    v0 = p.L + r0 * Ev * NP; v1 = p.L + r1 * Ev * NP;
+    e0 = p.sL + r0 * Ev; e1 = p.sL + r1 * Ev;
+  }
+  double* out = JOINT ? p.M + (size_t)u.parent * Ev * NP : p.L + ((size_t)p.n_tips + u.parent) * Ev * NP;
+  int32_t* eout = JOINT ? p.sM + (size_t)u.parent * Ev : p.sL + ((size_t)p.n_tips + u.parent) * Ev;
+  const double* c0 = sV + (g * 2) * VS;
+  const double* c1 = sV + (g * 2 + 1) * VS;
+  for (int w = 0; w < AW_WALK; ++w) {
+    const int sb = (blockIdx.z * AW_WALK + w) * G;                 // uniform over the workgroup
+    if (sb >= p.Sc) break;
+    const int s = sb + g;
+    const bool on = s < p.Sc;
+    const size_t ev = (size_t)k * p.Sc + (on ? s : 0);
+    __syncthreads();                                               // the matrices are staged; the last item's vectors are read
+    if (on) {
+      sV[(g * 2) * VS + a] = v0[ev * NP + a];
+      sV[(g * 2 + 1) * VS + a] = v1[ev * NP + a];
+    }
+    __syncthreads();
+    if (!on) continue;
+    double v;
+    if (JOINT) {
+      double b0 = 0.0, b1 = 0.0;
+      int at0 = 0, at1 = 0;
+      for (int c = 0; c < n; ++c) {                                // the first maximum wins
+        const double w0 = sP0[c * LD + a] * c0[c];
+        const double w1 = sP1[c * LD + a] * c1[c];
+        if (w0 > b0) { b0 = w0; at0 = c; }
+        if (w1 > b1) { b1 = w1; at1 = c; }
+      }
+      if (a >= n) { b0 = 0.0; b1 = 0.0; at0 = 0; at1 = 0; }
+      v = b0 * b1;
+      p.ptr[((size_t)u.edge[0] * Ev + ev) * NP + a] = (uint8_t)at0;
+      p.ptr[((size_t)u.edge[1] * Ev + ev) * NP + a] = (uint8_t)at1;
+    } else {
+      double s0 = 0.0, s1 = 0.0;
+      for (int j = 0; j < n; ++j) {
+        s0 = fma(sP0[j * LD + a], c0[j], s0);
+        s1 = fma(sP1[j * LD + a], c1[j], s1);
+      }
+      v = a < n ? s0 * s1 : 0.0;
+    }
+    int e;
+    v = aw_rescale(v, aw_group_max<NP>(v), e);
+    out[ev * NP + a] = v;
+    if (a == 0) eout[ev] = e0[ev] + e1[ev] + e;
+  }
+}
+
+// grid: (model, site tile).  l = sum_i pid[i] L_root[i] in state order on the group's first lane.
+template <int NP>
+__global__ __launch_bounds__(AW_BLOCK) void aw_root_kernel(AwParams p) {
+  constexpr int G = AwShape<NP>::G, VS = AwShape<NP>::VS;
+  __shared__ double sV[2 * G * VS];
+  const int n = p.n, k = blockIdx.x;
+  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const int s = blockIdx.y * G + g;
+  const bool on = s < p.Sc;
+  const size_t ev = (size_t)k * p.Sc + (on ? s : 0);
+  const double pi = a < n ? p.pid[(size_t)k * n + a] : 0.0;
+  if (on) {
+    sV[(g * 2) * VS + a] = pi;
+    sV[(g * 2 + 1) * VS + a] = p.L[((size_t)p.root * Ev + ev) * NP + a];
+  }
+  __syncthreads();
+  if (!on) return;
+  if (p.O) {
+    p.O[((size_t)p.root * Ev + ev) * NP + a] = pi;
+    if (a == 0) p.sO[(size_t)p.root * Ev + ev] = 0;
+  }
+  if (a == 0) {
+    double l = 0.0;
+    for (int i = 0; i < n; ++i) l = fma(sV[(g * 2) * VS + i], sV[(g * 2 + 1) * VS + i], l);
+    p.ll[ev] = log(l) + (double)p.sL[(size_t)p.root * Ev + ev] * AW_LN2;
+  }
+}
+
+// grid: (step, model, site tile).  F = O_p (.) (P_sib L_sib), O_c = P_b^T F.
+template <int NP>
+__global__ __launch_bounds__(AW_BLOCK) void aw_down_kernel(AwParams p, const ExDown* __restrict__ steps) {
+  constexpr int G = AwShape<NP>::G, LD = AwShape<NP>::LD, VS = AwShape<NP>::VS;
+  extern __shared__ __align__(16) double aw_lds[];
+  const int n = p.n;
+  double* sPs = aw_lds;                                            // sibling branch, transposed
+  double* sPb = sPs + n * LD;                                      // this branch, row-major [k][i] as stored
+  double* sV = sPb + n * LD;
+  const ExDown d = steps[blockIdx.x];
+  const int k = blockIdx.y;
+  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
+  const size_t Ev = (size_t)p.Kc * p.Sc, nn = (size_t)n * n;
+  const double* __restrict__ Pm = p.P + (size_t)k * p.n_edge * nn;
+  aw_stage_t<NP>(sPs, Pm + (size_t)d.sib_edge * nn, n);
+  {
+    const double* __restrict__ Pb = Pm + (size_t)d.edge * nn;
+    for (int e = threadIdx.x; e < n * n; e += AW_BLOCK) sPb[e] = Pb[e];
+  }
+  double* cs = sV + (g * 2) * VS;
+  double* cf = sV + (g * 2 + 1) * VS;
+  for (int w = 0; w < AW_WALK; ++w) {
+    const int sb = (blockIdx.z * AW_WALK + w) * G;
+    if (sb >= p.Sc) break;
+    const int s = sb + g;
+    const bool on = s < p.Sc;
+    const size_t ev = (size_t)k * p.Sc + (on ? s : 0);
+    __syncthreads();
+    if (on) cs[a] = p.L[((size_t)d.sib_child * Ev + ev) * NP + a];
+    __syncthreads();
+    double f = 0.0;
+    int eF = 0;
+    if (on) {
+      double acc = 0.0;
+      for (int j = 0; j < n; ++j) acc = fma(sPs[j * LD + a], cs[j], acc);
+      f = a < n ? p.O[((size_t)d.parent * Ev + ev) * NP + a] * acc : 0.0;
+      f = aw_rescale(f, aw_group_max<NP>(f), eF);
+      cf[a] = f;
+    }
+    __syncthreads();
+    if (!on) continue;
+    double o = 0.0;
+    for (int kk = 0; kk < n; ++kk) o = fma(sPb[kk * n + a], cf[kk], o);   // lanes past n read inside the staged block and are zeroed
+    if (a >= n) o = 0.0;
+    int eO;
+    o = aw_rescale(o, aw_group_max<NP>(o), eO);
+    p.O[((size_t)d.child * Ev + ev) * NP + a] = o;
+    if (a == 0)
+      p.sO[(size_t)d.child * Ev + ev] = p.sO[(size_t)d.parent * Ev + ev] + p.sL[(size_t)d.sib_child * Ev + ev] + eF + eO;
+  }
+}
+
+// grid: (selected row, model, site tile).  sum = sum_i O[i] L[i] in state order on the group's first lane, one reciprocal.
+template <int NP>
+__global__ __launch_bounds__(AW_BLOCK) void aw_post_kernel(AwParams p, int j0) {
+  constexpr int G = AwShape<NP>::G, VS = AwShape<NP>::VS;
+  __shared__ double sV[2 * G * VS];
+  __shared__ double sS[G];
+  const int n = p.n, k = blockIdx.y;
+  const int j = j0 + blockIdx.x, r = p.sel[j];
+  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const int s = blockIdx.z * G + g;
+  const bool on = s < p.Sc;
+  const size_t ev = (size_t)k * p.Sc + (on ? s : 0);
+  const size_t at = ((size_t)r * Ev + ev) * NP + a;
+  const double o = on ? p.O[at] : 0.0, l = on ? p.L[at] : 0.0;
+  sV[(g * 2) * VS + a] = o;
+  sV[(g * 2 + 1) * VS + a] = l;
+  __syncthreads();
+  if (a == 0) {
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum = fma(sV[(g * 2) * VS + i], sV[(g * 2 + 1) * VS + i], sum);
+    sS[g] = 1.0 / sum;
+  }
+  __syncthreads();
+  if (on && a < n) p.post[(ev * p.J + j) * n + a] = o * l * sS[g];
+}
+
+// grid: (model, site tile)
+template <int NP>
+__global__ __launch_bounds__(AW_BLOCK) void aw_jroot_kernel(AwParams p) {
+  constexpr int G = AwShape<NP>::G;
+  const int n = p.n, k = blockIdx.x;
+  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const int s = blockIdx.y * G + g;
+  if (s >= p.Sc) return;                                           // a whole group leaves: the shuffles stay inside a group
+  const size_t ev = (size_t)k * p.Sc + s;
+  const int ri = p.root - p.n_tips;
+  const double r = a < n ? p.pid[(size_t)k * n + a] * p.M[((size_t)ri * Ev + ev) * NP + a] : 0.0;
+  const double best = aw_group_max<NP>(r);
+  int at = (best > 0.0 && r == best) ? a : NP;
+#pragma unroll
+  for (int off = NP / 2; off >= 1; off >>= 1) at = min(at, __shfl_xor(at, off, NP));
+  if (a == 0) {
+    p.x[(size_t)p.root * Ev + ev] = (uint8_t)(at == NP ? 0 : at);
+    const double v = log(best) + (double)p.sM[(size_t)ri * Ev + ev] * AW_LN2;
+    p.jlogp[ev] = best > 0.0 ? v : -INFINITY;
+  }
+}
+
+// grid: (evaluations / block, step)
+template <int NP>
+__global__ __launch_bounds__(AW_BLOCK) void aw_trace_kernel(AwParams p, const ExDown* __restrict__ steps) {
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const size_t ev = (size_t)blockIdx.x * AW_BLOCK + threadIdx.x;
+  if (ev >= Ev) return;
+  const ExDown d = steps[blockIdx.y];
+  const uint32_t a = p.x[(size_t)d.parent * Ev + ev] & (uint32_t)(NP - 1);
+  p.x[(size_t)d.child * Ev + ev] = p.ptr[((size_t)d.edge * Ev + ev) * NP + a];
+}
+
+inline bool aw_ok(const AwParams& p) {
+  return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.Sc >= 1 &&
+         p.Sc <= AW_GRID_MAX && (size_t)p.Kc * p.Sc <= (size_t)INT32_MAX && p.root >= p.n_tips && p.P && p.pid && p.L && p.sL;
+}
+
+template <int NP> inline int aw_tiles(const AwParams& p) { return (p.Sc + AwShape<NP>::G * AW_WALK - 1) / (AwShape<NP>::G * AW_WALK); }
+template <int NP> inline int aw_rows(const AwParams& p) { return (p.Sc + AwShape<NP>::G - 1) / AwShape<NP>::G; }
+
+template <int NP, bool JOINT>
+hipError_t aw_up(const AwParams& p, const UpStep* steps, int count, hipStream_t stream) {
+  const size_t lds = sizeof(double) * aw_lds_doubles<NP>(p.n);
+  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(aw_up_kernel<NP, JOINT>), (int)(sizeof(double) * aw_lds_doubles<NP>(NP)));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((aw_up_kernel<NP, JOINT>), dim3(count, p.Kc, aw_tiles<NP>(p)), dim3(AW_BLOCK), lds, stream, p, steps);
+  return hipGetLastError();
+}
+
+template <int NP>
+hipError_t aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
+  const size_t lds = sizeof(double) * aw_lds_doubles<NP>(p.n);
+  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(aw_down_kernel<NP>), (int)(sizeof(double) * aw_lds_doubles<NP>(NP)));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((aw_down_kernel<NP>), dim3(count, p.Kc, aw_tiles<NP>(p)), dim3(AW_BLOCK), lds, stream, p, steps);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+#define AW_DISPATCH(call16, call32, call64) (p.NP == 16 ? (call16) : p.NP == 32 ? (call32) : (call64))
+
+hipError_t launch_aw_tips(const AwParams& p, hipStream_t stream) {
+  if (!aw_ok(p) || !p.tips || !p.obs) return hipErrorInvalidValue;
+  const size_t cells = (size_t)p.Kc * p.Sc * p.NP;
+  for (int t0 = 0; t0 < p.n_tips; t0 += AW_GRID_MAX)
+    hipLaunchKernelGGL(aw_tips_kernel, dim3((unsigned)((cells + AW_BLOCK - 1) / AW_BLOCK), std::min(AW_GRID_MAX, p.n_tips - t0)),
+                       dim3(AW_BLOCK), 0, stream, p, t0);
+  return hipGetLastError();
+}
+
+hipError_t launch_aw_up(const AwParams& p, const UpStep* steps, int count, bool joint, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (!aw_ok(p) || !steps || (joint && (!p.M || !p.sM || !p.ptr))) return hipErrorInvalidValue;
+  if (joint) return AW_DISPATCH((aw_up<16, true>(p, steps, count, stream)), (aw_up<32, true>(p, steps, count, stream)),
+                                (aw_up<64, true>(p, steps, count, stream)));
+  return AW_DISPATCH((aw_up<16, false>(p, steps, count, stream)), (aw_up<32, false>(p, steps, count, stream)),
+                     (aw_up<64, false>(p, steps, count, stream)));
+}
+
+hipError_t launch_aw_root(const AwParams& p, hipStream_t stream) {
+  if (!aw_ok(p) || !p.ll || (p.O && !p.sO)) return hipErrorInvalidValue;
+  const dim3 blk(AW_BLOCK);
+  if (p.NP == 16) hipLaunchKernelGGL((aw_root_kernel<16>), dim3(p.Kc, aw_rows<16>(p)), blk, 0, stream, p);
+  else if (p.NP == 32) hipLaunchKernelGGL((aw_root_kernel<32>), dim3(p.Kc, aw_rows<32>(p)), blk, 0, stream, p);
+  else hipLaunchKernelGGL((aw_root_kernel<64>), dim3(p.Kc, aw_rows<64>(p)), blk, 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (!aw_ok(p) || !steps || !p.O || !p.sO) return hipErrorInvalidValue;
+  return AW_DISPATCH((aw_down<16>(p, steps, count, stream)), (aw_down<32>(p, steps, count, stream)), (aw_down<64>(p, steps, count, stream)));
+}
+
+hipError_t launch_aw_post(const AwParams& p, int j0, int count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (!aw_ok(p) || !p.O || !p.sel || !p.post || j0 < 0 || j0 + count > p.J) return hipErrorInvalidValue;
+  const dim3 blk(AW_BLOCK);
+  if (p.NP == 16) hipLaunchKernelGGL((aw_post_kernel<16>), dim3(count, p.Kc, aw_rows<16>(p)), blk, 0, stream, p, j0);
+  else if (p.NP == 32) hipLaunchKernelGGL((aw_post_kernel<32>), dim3(count, p.Kc, aw_rows<32>(p)), blk, 0, stream, p, j0);
+  else hipLaunchKernelGGL((aw_post_kernel<64>), dim3(count, p.Kc, aw_rows<64>(p)), blk, 0, stream, p, j0);
+  return hipGetLastError();
+}
+
+hipError_t launch_aw_jroot(const AwParams& p, hipStream_t stream) {
+  if (!aw_ok(p) || !p.M || !p.sM || !p.x || !p.jlogp) return hipErrorInvalidValue;
+  const dim3 blk(AW_BLOCK);
+  if (p.NP == 16) hipLaunchKernelGGL((aw_jroot_kernel<16>), dim3(p.Kc, aw_rows<16>(p)), blk, 0, stream, p);
+  else if (p.NP == 32) hipLaunchKernelGGL((aw_jroot_kernel<32>), dim3(p.Kc, aw_rows<32>(p)), blk, 0, stream, p);
+  else hipLaunchKernelGGL((aw_jroot_kernel<64>), dim3(p.Kc, aw_rows<64>(p)), blk, 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_aw_trace(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (!aw_ok(p) || !steps || !p.ptr || !p.x || count > AW_GRID_MAX) return hipErrorInvalidValue;
+  const size_t Ev = (size_t)p.Kc * p.Sc;
+  const dim3 grid((unsigned)((Ev + AW_BLOCK - 1) / AW_BLOCK), count), blk(AW_BLOCK);
+  if (p.NP == 16) hipLaunchKernelGGL((aw_trace_kernel<16>), grid, blk, 0, stream, p, steps);
+  else if (p.NP == 32) hipLaunchKernelGGL((aw_trace_kernel<32>), grid, blk, 0, stream, p, steps);
+  else hipLaunchKernelGGL((aw_trace_kernel<64>), grid, blk, 0, stream, p, steps);
+  return hipGetLastError();
+}
+
+#undef AW_DISPATCH
+
+}  // namespace phm
