@@ -1,13 +1,13 @@
 // phm_ancestral_wide_api.cpp -- C-ABI of the ancestral states for many rate matrices at 9..64 states
-// (phm_ancestral_models_wide): phm_ancestral_models' arguments, validation (ll_validate, then the node
-// selection) and outputs.  Per device and per chunk of models P_k(t_b) by one launch_expm_pade per model (section 13's kernel and
+// (phm_ancestral_models_wide): phm_ancestral_models' arguments, validation (an_entry of phm_ancestral_host.h:
+// ll_validate, then the node selection) and outputs.  Per device and per chunk of models P_k(t_b) by one launch_expm_pade per model (section 13's kernel and
 // ex_squarings' counts, each model with its own error word), then per chunk of sites the tips / up / root launches followed by
 // what was asked for: the down pass with the node posteriors, and the max-product up pass, root and traceback.  The output stage
 // is on the HOST.  An evaluation is independent of every other one and P_k of every other model, so neither the chunks nor the
 // shards change an output bit.
 #include "phm_ancestral_wide.h"
 #include "phm_exp.h"
-#include "phm_loglik_host.h"
+#include "phm_ancestral_host.h"
 
 #include <limits>
 
@@ -18,53 +18,8 @@ using namespace phm_ll;
 
 const std::string AW_FN = "phm_ancestral_models_wide: ";
 
-struct AwInput {
-  LlInput ll;
-  int J = 0;                                            // reported nodes
-  std::vector<int32_t> sel;                             // their node rows (node id - 1), in the caller's order
-  std::vector<phm::ExDown> down;                        // grouped by the depth of the parent
-  std::vector<int32_t> down_off;
-};
-
-inline int64_t eval_of(const LlInput& in, int64_t site, int64_t model) { return in.paired ? model : site + (int64_t)in.S * model; }
-
-int32_t aw_prepare(AwInput& an, const int32_t* node_sel, int32_t n_sel) {
-  LlInput& in = an.ll;
-  if (in.n < phm::AW_MIN_STATES)
-    return fail(PHM_ERR_UNSUPPORTED, AW_FN + "9..64 states only: 2..8 states go to phm_ancestral_models");
-  if ((int64_t)in.S * in.K > (int64_t)INT32_MAX) return fail(PHM_ERR_BAD_INPUT, AW_FN + "sites * models must fit in 31 bits");
-  if (n_sel == 0) {
-    an.sel.resize(in.NT);
-    for (int r = 0; r < in.NT; ++r) an.sel[r] = r;
-  } else {
-    an.sel.resize(n_sel);
-    for (int j = 0; j < n_sel; ++j) {
-      if (node_sel[j] < 1 || node_sel[j] > in.NT)
-        return fail(PHM_ERR_BAD_INPUT, AW_FN + "node_sel[" + std::to_string(j) + "] must be in 1.." + std::to_string(in.NT));
-      an.sel[j] = node_sel[j] - 1;
-    }
-  }
-  an.J = (int)an.sel.size();
-  const phm::Schedule& s = in.sched;
-  const int T = in.T;
-  std::vector<int32_t> order, up_of(s.n_node, -1);
-  for (int k = 0; k < s.n_node; ++k) up_of[s.up[k].parent] = k;
-  auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
-  phm::depth_levels(s, order, an.down_off);
-  for (int32_t k : order) {
-    const phm::DownStep& d = s.down[k];
-    const phm::UpStep& u = s.up[up_of[d.parent]];
-    const int side = u.edge[0] == d.edge ? 1 : 0;                  // the sibling branch
-    phm::ExDown x = {};
-    x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
-    x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
-    an.down.push_back(x);
-  }
-  return PHM_OK;
-}
-
 // models [first, first + count) on one device
-int32_t aw_device(const AwInput& an, int32_t device, int64_t first, int64_t count, double* loglik, double* node_post,
+int32_t aw_device(const AnInput& an, int32_t device, int64_t first, int64_t count, double* loglik, double* node_post,
                   int32_t* joint_states, double* joint_logp) {
   int32_t st = select_device(device);
   if (st) return st;
@@ -72,7 +27,7 @@ int32_t aw_device(const AwInput& an, int32_t device, int64_t first, int64_t coun
   const int n = in.n, E = in.E, NT = in.NT, T = in.T, Nn = in.Nn, J = an.J, NP = phm::aw_lanes(in.n);
   const bool marg = node_post != nullptr, joint = joint_states != nullptr;
   const size_t nn = (size_t)n * n;
-  const int64_t S_eval = in.paired ? 1 : in.S;           // sites per model
+  const int64_t S_eval = in.sites_per_model();
   const double nan = std::numeric_limits<double>::quiet_NaN(), ninf = -std::numeric_limits<double>::infinity();
   KernelTimer tm;
   double kernel_ms = 0.0, ms = 0.0;
@@ -170,11 +125,8 @@ int32_t aw_device(const AwInput& an, int32_t device, int64_t first, int64_t coun
           for (int t = 0; t < T; ++t) tips_h[(size_t)k * T + t] = (uint8_t)y[t];
         }
         HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Kc, hipMemcpyHostToDevice));
-      } else {                                           // [site][tip]
-        for (int64_t s = 0; s < Sc; ++s) {
-          const int32_t* y = in.tips_of(s0 + s);
-          for (int t = 0; t < T; ++t) tips_h[(size_t)s * T + t] = (uint8_t)y[t];
-        }
+      } else {
+        ll_stage_tips_sites(in, s0, Sc, tips_h);         // [site][tip]
         HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Sc, hipMemcpyHostToDevice));
       }
       const phm::UpStep* up = dup.as<phm::UpStep>();
@@ -214,7 +166,7 @@ int32_t aw_device(const AwInput& an, int32_t device, int64_t first, int64_t coun
       for (int64_t k = 0; k < Kc; ++k)
         for (int64_t s = 0; s < Sc; ++s) {
           const size_t at = (size_t)k * Sc + s;
-          const int64_t ev = eval_of(in, s0 + s, m0 + k);
+          const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
           const bool possible = !badh[k] && std::isfinite(llh[at]);
           loglik[ev] = possible ? llh[at] : ninf;
           if (marg) {
@@ -244,24 +196,9 @@ int32_t phm_ancestral_models_wide(const phm_tree* x, int32_t n_states, int32_t n
                                   int32_t n_pid, const int32_t* observe, const int32_t* site_of_model, const int32_t* node_sel,
                                   int32_t n_sel, const phm_options* opt, double* loglik, double* node_post, int32_t* joint_states,
                                   double* joint_logp) {
-  const phm_options o = resolve_options(opt);
-  if (!x || !Q || !pid || !loglik)
-    return fail(PHM_ERR_BAD_INPUT, AW_FN + "NULL argument (x, Q, pid and loglik are required)");
-  if (!node_post && !joint_states) return fail(PHM_ERR_BAD_INPUT, AW_FN + "node_post and joint_states are both NULL: nothing to compute");
-  if (joint_logp && !joint_states) return fail(PHM_ERR_BAD_INPUT, AW_FN + "joint_logp needs joint_states");
-  if (n_sel < 0) return fail(PHM_ERR_BAD_INPUT, AW_FN + "n_sel must be >= 0");
-  if (n_sel > 0 && !node_sel) return fail(PHM_ERR_BAD_INPUT, AW_FN + "node_sel is NULL with n_sel > 0");
-  AwInput an;
-  int32_t st = ll_validate(AW_FN, x, n_states, n_models, Q, pid, n_pid, observe, site_of_model, o, an.ll);
-  if (st) return st;
-  st = aw_prepare(an, node_sel, n_sel);
-  if (st) return st;
-  std::vector<phm_shard> shards;
-  st = phm_plan_shards(o, an.ll.K, shards);
-  if (st) return st;
-  return run_shards(shards, [&](const phm_shard& sh, size_t) {
-    return aw_device(an, sh.device, sh.first, sh.count, loglik, node_post, joint_states, joint_logp);
-  });
+  return an_entry(AW_FN, phm::AW_MIN_STATES, phm::EX_MAX_STATES, "9..64 states only: 2..8 states go to phm_ancestral_models", aw_device, x,
+                  n_states, n_models, Q, pid, n_pid, observe, site_of_model, node_sel, n_sel, opt, loglik, node_post, joint_states,
+                  joint_logp);
 }
 
 }  // extern "C"

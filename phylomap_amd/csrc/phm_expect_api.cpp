@@ -1,7 +1,8 @@
 // phm_expect_api.cpp -- C-ABI of the exact conditional expectations (phm_expected_stats): validation and
 // everything that depends on the branch alone (level schedules, Poisson weights, Pade squaring counts) on the host, then per
 // device P(t_b) once, and per chunk of sites the up pass, the down pass and the branch stage (phm_expect.hip).  The host pieces
-// declared in phm_expect_host.h, which phm_expected_through_time shares, are defined here.
+// declared in phm_expect_host.h, which phm_expected_through_time shares, are defined here (ex_down_schedule, which the many-model
+// entry points use too, is inline in that header).
 #include "phm_expect_host.h"
 
 namespace phm_ex {
@@ -88,24 +89,10 @@ int ex_squarings(const double* Q_rm, int n, double t) {
 
 void ex_prepare(ExInput& in) {
   const phm::Schedule& s = in.sched;
-  const int T = in.T;
-  std::vector<int32_t> order, up_of(s.n_node, -1);
+  std::vector<int32_t> order;
   phm::height_levels(s.up, order, in.up_off);
   for (int32_t k : order) in.up.push_back(s.up[k]);
-  for (int k = 0; k < s.n_node; ++k) up_of[s.up[k].parent] = k;
-  auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
-  phm::depth_levels(s, order, in.down_off);
-  in.child_row.assign(in.E, 0);
-  for (int32_t k : order) {
-    const phm::DownStep& d = s.down[k];
-    const phm::UpStep& u = s.up[up_of[d.parent]];
-    const int side = u.edge[0] == d.edge ? 1 : 0;                // the sibling branch
-    phm::ExDown x = {};
-    x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
-    x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
-    in.down.push_back(x);
-    in.child_row[d.edge] = x.child;
-  }
+  ex_down_schedule(s, in.T, in.down, in.down_off, &in.child_row);
   in.w_off.assign(1, 0);
   in.sq.resize(in.E);
   std::vector<double> p;

@@ -1,6 +1,7 @@
 // phm_expect_host.h -- host side shared by the two entry points of the exact conditional expectations: phm_expected_stats
 // (phm_expect_api.cpp) and phm_expected_through_time (phm_expect_time.cpp, section 16).  The checked input,
-// the per-call preparation, P(t_b) once per device and the tips / up / root / down passes of one chunk of sites.
+// the per-call preparation, P(t_b) once per device and the tips / up / root / down passes of one chunk of sites.  The schedule of
+// the down pass (ex_down_schedule) also serves the many-model entry points (phm_loglik_host.h).
 #pragma once
 
 #include "phm_internal.h"
@@ -38,6 +39,28 @@ int32_t ex_validate(const std::string& fn, const phm_tree* x, int32_t n, const d
                     const phm_options& o, ExInput& in);
 // level schedules, child rows, Poisson weights and Pade squaring counts (host, once per call)
 void ex_prepare(ExInput& in);
+
+// The schedule of the down pass of a tree with T tips: every branch with the rows of its ends and of its sibling, grouped by the
+// depth of the parent (down_off: the level boundaries); child_row (when asked for): [edge row] the row of the branch's child.
+// Every entry point with a down pass builds it here, the many-model ones (phm_loglik_host.h) included.
+inline void ex_down_schedule(const phm::Schedule& s, int T, std::vector<phm::ExDown>& down, std::vector<int32_t>& down_off,
+                             std::vector<int32_t>* child_row = nullptr) {
+  std::vector<int32_t> order, up_of(s.n_node, -1);
+  for (int k = 0; k < s.n_node; ++k) up_of[s.up[k].parent] = k;
+  auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
+  phm::depth_levels(s, order, down_off);
+  if (child_row) child_row->assign(s.n_edge, 0);
+  for (int32_t k : order) {
+    const phm::DownStep& d = s.down[k];
+    const phm::UpStep& u = s.up[up_of[d.parent]];
+    const int side = u.edge[0] == d.edge ? 1 : 0;                    // the sibling branch
+    phm::ExDown x = {};
+    x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
+    x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
+    down.push_back(x);
+    if (child_row) (*child_row)[d.edge] = x.child;
+  }
+}
 
 // What one device holds for the whole call: the model, the schedules, the branch weights and P(t_b).
 struct ExDevice {

@@ -58,7 +58,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   const int n = in.n, E = in.E, NT = in.NT, T = in.T, cols = g.cols, np = g.p;
   const size_t nn = (size_t)n * n;
   const int64_t C = in.K;
-  const int64_t S_eval = in.paired ? 1 : in.S;           // sites per chain
+  const int64_t S_eval = in.sites_per_model();           // sites per chain
   const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
   double kernel_ms = 0.0, ms = 0.0;
@@ -67,8 +67,10 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   double up_ms = 0.0, run_ms = 0.0, host_ms = 0.0;
   int launches = 0;
   auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
-  DevBuf dt, dobs, dup, ddown, dorder, derr;
-  HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dobs, in.obs)); HIPCHK(upload(dup, in.up));
+  LlLanes ln(in);
+  DevBuf ddown, dorder, derr;
+  st = ln.upload_tree();
+  if (st) return st;
   HIPCHK(upload(ddown, in.sched.down)); HIPCHK(upload(dorder, g.order));
   HIPCHK(derr.alloc(sizeof(uint32_t)));
   HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
@@ -89,18 +91,12 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   if (chunk > 0) Kc_max = std::min<int64_t>(Kc_max, ((int64_t)chunk + 63) / 64 * 64);
   Kc_max = std::min<int64_t>(Kc_max, (count + 63) / 64 * 64);
   const size_t Kpm = (size_t)Kc_max, Evm = Kpm * (size_t)S_eval;
-  int ne_max = E;
-  if (ws) ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, LL_WORK / (sizeof(double) * 4 * nn * Kpm)}));
-  ne_max = std::min(ne_max, 65535);
-  if (chunk > 0) ne_max = std::min(ne_max, chunk);
+  LlPlan pl;
+  pl.Kc_max = Kc_max; pl.Sc_max = S_eval; pl.ne_max = ll_edges_per_launch(n, E, Kpm, chunk);
 
-  DevBuf dQ, dpid, dP, dwork, dbad, dL, dsL, dll, dtips, dmu, dB, dbeta, ddepth, dtile, dlane, dnst, ddw, dcnt, dout;
-  HIPCHK(dQ.alloc(sizeof(double) * nn * Kpm)); HIPCHK(dpid.alloc(sizeof(double) * n * Kpm));
-  HIPCHK(dP.alloc(sizeof(double) * (size_t)E * nn * Kpm)); HIPCHK(dbad.alloc(sizeof(uint32_t) * Kpm));
-  if (ws) HIPCHK(dwork.alloc(sizeof(double) * 4 * nn * Kpm * (size_t)ne_max));
-  HIPCHK(dL.alloc(sizeof(double) * (size_t)NT * n * Evm)); HIPCHK(dsL.alloc(sizeof(double) * (size_t)NT * Evm));
-  HIPCHK(dll.alloc(sizeof(double) * Evm));
-  HIPCHK(dtips.alloc(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)S_eval));
+  DevBuf dmu, dB, dbeta, ddepth, dtile, dlane, dnst, ddw, dcnt, dout;
+  st = ln.alloc(pl);
+  if (st) return st;
   HIPCHK(dmu.alloc(sizeof(double) * Kpm)); HIPCHK(dB.alloc(sizeof(double) * nn * Kpm));
   HIPCHK(dbeta.alloc(sizeof(double) * ((size_t)g.depth + 1) * nn * Kpm)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Kpm));
   HIPCHK(dtile.alloc(sizeof(phm::SmTile) * (Evm / 64))); HIPCHK(dlane.alloc(sizeof(uint32_t) * Evm));
@@ -112,8 +108,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   HIPCHK(hQ.reserve(sizeof(double) * nn * Kpm)); HIPCHK(hout.reserve(sizeof(double) * out_max));
   double* Qh = hQ.as<double>();
   const double* outh = hout.as<double>();
-  std::vector<double> pidh((size_t)n * Kpm), th((size_t)np * Kpm);
-  std::vector<uint8_t> tips_h(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)S_eval);
+  std::vector<double> th((size_t)np * Kpm);
   std::vector<phm::SmTile> tiles(Evm / 64);
   std::vector<uint32_t> lane_id(Evm);
 
@@ -130,14 +125,14 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
 
   for (int64_t c0 = 0; c0 < count; c0 += Kc_max) {
     const int64_t Kc = std::min<int64_t>(Kc_max, count - c0);
-    const int Kp = (int)((Kc + 63) / 64 * 64);
-    const int64_t m0 = first + c0;                       // global index of this chunk's first chain
+    st = ln.load_priors(first + c0, Kc);                 // Q is this driver's own: filled into Qh, uploaded every iteration
+    if (st) return st;
+    const int Kp = ln.Kp;
+    const int64_t m0 = ln.m0;                            // global index of this chunk's first chain
     const size_t npad = (size_t)S_eval * Kp;             // lanes of the chunk: evaluation s * Kp + k is lane s * Kp + k
     const int nt = (int)(npad / 64);
     std::fill(Qh, Qh + nn * Kp, 0.0);
-    std::fill(pidh.begin(), pidh.end(), 0.0);
     for (int64_t k = 0; k < Kc; ++k) {
-      for (int i = 0; i < n; ++i) pidh[(size_t)i * Kp + k] = in.pid[(size_t)(m0 + k) * n + i];
       std::copy_n(g.theta0 + (size_t)(m0 + k) * np, np, th.begin() + (size_t)k * np);
       fill_q(g, &th[(size_t)k * np], Qh + k, (size_t)Kp);
     }
@@ -152,30 +147,13 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
           lane_id[(size_t)(s * Kp + k)] = k < Kc ? (uint32_t)(site * C + (m0 + k)) : phm::SM_LANE_IDLE;
         }
       }
-    if (in.paired) {                                     // [tip][Kp]: lane k reads the tips of its own site
-      std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);
-      for (int64_t k = 0; k < Kc; ++k) {
-        const int32_t* y = in.tips_of(in.site_of_model[m0 + k]);
-        for (int t = 0; t < T; ++t) tips_h[(size_t)t * Kp + k] = (uint8_t)y[t];
-      }
-      HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Kp, hipMemcpyHostToDevice));
-    } else {                                             // [site][tip]
-      for (int64_t s = 0; s < S_eval; ++s) {
-        const int32_t* y = in.tips_of(s);
-        for (int t = 0; t < T; ++t) tips_h[(size_t)s * T + t] = (uint8_t)y[t];
-      }
-      HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * S_eval, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(dpid.p, pidh.data(), sizeof(double) * n * Kp, hipMemcpyHostToDevice));
+    st = ln.stage_tips(0, S_eval);
+    if (st) return st;
     HIPCHK(hipMemcpy(dtile.p, tiles.data(), sizeof(phm::SmTile) * nt, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dlane.p, lane_id.data(), sizeof(uint32_t) * npad, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dbad.p, 0, sizeof(uint32_t) * Kp));
     HIPCHK(hipMemset(ddw.p, 0, sizeof(unsigned long long) * n * npad));
     HIPCHK(hipMemset(dcnt.p, 0, sizeof(uint32_t) * (size_t)n * (n - 1) * npad));
-    p.n = n; p.n_tips = T; p.Kp = Kp; p.Kc = (int)Kc; p.paired = in.paired ? 1 : 0;
-    p.Q = dQ.as<double>(); p.pid = dpid.as<double>(); p.t = dt.as<double>(); p.P = dP.as<double>();
-    p.work = ws ? dwork.as<double>() : nullptr; p.bad = dbad.as<uint32_t>(); p.tips = dtips.as<uint8_t>();
-    p.obs = dobs.as<int32_t>(); p.L = dL.as<double>(); p.sL = dsL.as<double>(); p.ll = dll.as<double>();
+    p = ln.params();
     sp.n_tiles = nt;
     const int branch_blocks = (int)std::min<int64_t>(((int64_t)E * nt + 3) / 4, 2048);
     const size_t out_n = (size_t)(cols + 1) * npad + 1;
@@ -236,18 +214,17 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
     for (int iter = 0; iter < g.iters; ++iter) {
       sp.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
       Clock::time_point t0 = Clock::now();
-      HIPCHK(hipMemcpy(dQ.p, Qh, sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(ln.dQ.p, Qh, sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
       up_ms += since(t0);
       t0 = Clock::now();
       HIPCHK(tm.start());
       p.n_sites = 1;
-      for (int e0 = 0; e0 < E; e0 += ne_max) HIPCHK(phm::launch_ll_expm(p, e0, std::min(ne_max, E - e0), nullptr));
+      st = ln.expm(p);
+      if (st) return st;
       HIPCHK(phm::launch_sm_table(sp, nullptr));
       p.n_sites = (int)S_eval;
-      HIPCHK(phm::launch_ll_tips(p, nullptr));
-      for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-        HIPCHK(phm::launch_ll_up(p, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
-      HIPCHK(phm::launch_ll_root(p, sp.root_row, nullptr));
+      st = ln.passes(p);
+      if (st) return st;
       HIPCHK(phm::launch_sm_sample(sp, g.level_off, branch_blocks, phm::MAPS_OFF, nullptr));
       HIPCHK(tm.stop());
       HIPCHK(hipMemcpy(hout.p, dout.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
@@ -271,7 +248,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
     }
     int levels = 0;
     for (size_t l = 0; l + 1 < g.level_off.size(); ++l) levels += g.level_off[l + 1] > g.level_off[l] ? 1 : 0;
-    launches = (E + ne_max - 1) / ne_max + 3 + (int)in.up_off.size() - 1 + 3 + levels;   // P, table, tips, up levels, root | root, node levels, branch, finish
+    launches = (E + pl.ne_max - 1) / pl.ne_max + 3 + (int)in.up_off.size() - 1 + 3 + levels;   // P, table, tips, up levels, root | root, node levels, branch, finish
   }
   if (q_timing)
     std::fprintf(stderr, "phm_gibbs_rates: device %d, chains %lld, per iteration: upload of Q %.4f ms, launches + device + download %.4f ms "

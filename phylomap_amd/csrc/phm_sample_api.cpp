@@ -27,8 +27,6 @@ struct SmInput {
   int32_t* nodes = nullptr;
 };
 
-inline int64_t eval_of(const LlInput& in, int64_t site, int64_t model) { return in.paired ? model : site + (int64_t)in.S * model; }
-
 int32_t sm_prepare(SmInput& sm, int32_t draws) {
   LlInput& in = sm.ll;
   const int n = in.n;
@@ -64,15 +62,17 @@ int32_t sm_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
   const LlInput& in = sm.ll;
   const int n = in.n, E = in.E, NT = in.NT, T = in.T, cols = sm.cols, D = sm.D;
   const size_t nn = (size_t)n * n;
-  const int64_t S_eval = in.paired ? 1 : in.S;           // sites per model
+  const int64_t S_eval = in.sites_per_model();
   const int64_t H = sm.H;
   const int tiles_per_eval = (D + 63) / 64;
   const double nan = std::numeric_limits<double>::quiet_NaN();
-  const int64_t h_first = eval_of(in, 0, first) * D, h_count = count * S_eval * D;      // the shard's histories
+  const int64_t h_first = ll_eval_of(in, 0, first) * D, h_count = count * S_eval * D;      // the shard's histories
   KernelTimer tm;
   double kernel_ms = 0.0, ms = 0.0;
-  DevBuf dt, dobs, dup, ddown, dorder, derr;
-  HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dobs, in.obs)); HIPCHK(upload(dup, in.up));
+  LlLanes ln(in);
+  DevBuf ddown, dorder, derr;
+  st = ln.upload_tree();
+  if (st) return st;
   HIPCHK(upload(ddown, in.sched.down)); HIPCHK(upload(dorder, sm.order));
   HIPCHK(derr.alloc(sizeof(uint32_t)));
   HIPCHK(hipMemset(derr.p, 0, sizeof(uint32_t)));
@@ -89,46 +89,22 @@ int32_t sm_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
   int depth_max = 0;
   for (int64_t k = first; k < first + count; ++k) depth_max = std::max(depth_max, sm.depth[k]);
 
-  // Chunks by free HBM: section 17's buffers per model and per evaluation, the table per model, and a fixed share for the tiles.
+  // On top of section 17's footprint: mu, B, the table and its depth per model, and a fixed share for the tiles.
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const bool ws = n > phm::LL_REG_MAX;
   const size_t per_tile = (size_t)NT * 64 + 64 * (sizeof(double) * (cols + n) + sizeof(uint32_t) * n * (n - 1)) +
                           (sm.nodes ? sizeof(int32_t) * 64 * (size_t)NT : 0) + sizeof(phm::SmTile);
   const int chunk = g_phm_debug.expect_chunk;
   const int64_t tiles_total = count * S_eval * tiles_per_eval;
   int64_t Tc_max = std::max<int64_t>(1, std::min<int64_t>({tiles_total, (int64_t)(free_b / 8 / per_tile), (int64_t)1 << 20}));
   if (chunk > 0) Tc_max = std::min<int64_t>(Tc_max, chunk);
-  const size_t fixed = (ws ? LL_WORK : 0) + per_tile * (size_t)Tc_max;
-  const size_t budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
-  const size_t per_model = sizeof(double) * ((size_t)E * nn + 2 * nn + n + 1 + ((size_t)depth_max + 1) * nn) + sizeof(uint32_t) + sizeof(int32_t);
-  const size_t per_eval = sizeof(double) * ((size_t)NT * (n + 1) + 1) + (in.paired ? (size_t)T : 0);
-  int64_t Sc_max = std::min<int64_t>(S_eval, 65535);
-  int64_t Kc_max = (int64_t)(budget / (per_model + per_eval * (size_t)Sc_max)) / 64 * 64;
-  if (Kc_max < 64) {
-    Kc_max = 64;
-    const size_t per64 = budget / 64;
-    Sc_max = std::max<int64_t>(1, std::min<int64_t>(Sc_max, per64 > per_model ? (int64_t)((per64 - per_model) / per_eval) : 1));
-  }
-  if (chunk > 0) {
-    Kc_max = std::min<int64_t>(Kc_max, ((int64_t)chunk + 63) / 64 * 64);
-    Sc_max = std::min<int64_t>(Sc_max, chunk);
-  }
-  Kc_max = std::min<int64_t>(Kc_max, (count + 63) / 64 * 64);
-  const size_t Kpm = (size_t)Kc_max, Evm = Kpm * (size_t)Sc_max;
-  int ne_max = E;
-  if (ws) ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, LL_WORK / (sizeof(double) * 4 * nn * Kpm)}));
-  ne_max = std::min(ne_max, 65535);
-  if (chunk > 0) ne_max = std::min(ne_max, chunk);
+  const LlPlan pl = ll_plan(free_b, in, count, chunk, per_tile * (size_t)Tc_max,
+                            sizeof(double) * (nn + 1 + ((size_t)depth_max + 1) * nn) + sizeof(int32_t), 0);
+  const size_t Kpm = (size_t)pl.Kc_max;
 
-  DevBuf dQ, dpid, dP, dwork, dbad, dL, dsL, dll, dtips, dmu, dB, dbeta, ddepth;
-  DevBuf dtile, dnst, ddw, dcnt, dout, dnodes;
-  HIPCHK(dQ.alloc(sizeof(double) * nn * Kpm)); HIPCHK(dpid.alloc(sizeof(double) * n * Kpm));
-  HIPCHK(dP.alloc(sizeof(double) * (size_t)E * nn * Kpm)); HIPCHK(dbad.alloc(sizeof(uint32_t) * Kpm));
-  if (ws) HIPCHK(dwork.alloc(sizeof(double) * 4 * nn * Kpm * (size_t)ne_max));
-  HIPCHK(dL.alloc(sizeof(double) * (size_t)NT * n * Evm)); HIPCHK(dsL.alloc(sizeof(double) * (size_t)NT * Evm));
-  HIPCHK(dll.alloc(sizeof(double) * Evm));
-  HIPCHK(dtips.alloc(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)Sc_max));
+  DevBuf dmu, dB, dbeta, ddepth, dtile, dnst, ddw, dcnt, dout, dnodes;
+  st = ln.alloc(pl);
+  if (st) return st;
   HIPCHK(dmu.alloc(sizeof(double) * Kpm)); HIPCHK(dB.alloc(sizeof(double) * nn * Kpm));
   HIPCHK(dbeta.alloc(sizeof(double) * ((size_t)depth_max + 1) * nn * Kpm)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Kpm));
   const size_t npad_max = (size_t)Tc_max * 64;
@@ -136,9 +112,8 @@ int32_t sm_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
   HIPCHK(ddw.alloc(sizeof(unsigned long long) * n * npad_max)); HIPCHK(dcnt.alloc(sizeof(uint32_t) * (size_t)n * (n - 1) * npad_max));
   HIPCHK(dout.alloc(sizeof(double) * cols * npad_max));
   if (sm.nodes) HIPCHK(dnodes.alloc(sizeof(int32_t) * (size_t)NT * npad_max));
-  std::vector<double> Qh(nn * Kpm), pidh((size_t)n * Kpm), llh(Evm), outh((size_t)cols * npad_max);
+  std::vector<double> outh((size_t)cols * npad_max);
   std::vector<int32_t> depth_h(Kpm), nodes_h(sm.nodes ? (size_t)NT * npad_max : 0);
-  std::vector<uint8_t> tips_h(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)Sc_max);
   std::vector<phm::SmTile> tiles;
   tiles.reserve((size_t)Tc_max);
 
@@ -188,68 +163,47 @@ int32_t sm_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
     return PHM_OK;
   };
 
-  for (int64_t c0 = 0; c0 < count; c0 += Kc_max) {
-    const int64_t Kc = std::min<int64_t>(Kc_max, count - c0);
-    const int Kp = (int)((Kc + 63) / 64 * 64);
-    const int64_t m0 = first + c0;                       // global index of this chunk's first model
-    std::fill(Qh.begin(), Qh.end(), 0.0);
-    std::fill(pidh.begin(), pidh.end(), 0.0);
+  for (int64_t c0 = 0; c0 < count; c0 += pl.Kc_max) {
+    const int64_t Kc = std::min<int64_t>(pl.Kc_max, count - c0);
+    st = ln.load_models(first + c0, Kc);
+    if (st) return st;
+    const int Kp = ln.Kp;
+    const int64_t m0 = ln.m0;                            // global index of this chunk's first model
     std::fill(depth_h.begin(), depth_h.end(), 0);
     int depth_c = 0;
     for (int64_t k = 0; k < Kc; ++k) {
-      for (size_t e = 0; e < nn; ++e) Qh[e * Kp + k] = in.Qr[(size_t)(m0 + k) * nn + e];
-      for (int i = 0; i < n; ++i) pidh[(size_t)i * Kp + k] = in.pid[(size_t)(m0 + k) * n + i];
       depth_h[k] = sm.depth[m0 + k];
       depth_c = std::max(depth_c, depth_h[k]);
     }
-    HIPCHK(hipMemcpy(dQ.p, Qh.data(), sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpid.p, pidh.data(), sizeof(double) * n * Kp, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(ddepth.p, depth_h.data(), sizeof(int32_t) * Kp, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dbad.p, 0, sizeof(uint32_t) * Kp));
-    p.n = n; p.n_tips = T; p.Kp = Kp; p.Kc = (int)Kc; p.paired = in.paired ? 1 : 0;
-    p.Q = dQ.as<double>(); p.pid = dpid.as<double>(); p.t = dt.as<double>(); p.P = dP.as<double>();
-    p.work = ws ? dwork.as<double>() : nullptr; p.bad = dbad.as<uint32_t>(); p.tips = dtips.as<uint8_t>();
-    p.obs = dobs.as<int32_t>(); p.L = dL.as<double>(); p.sL = dsL.as<double>(); p.ll = dll.as<double>();
-    p.n_sites = 1;
+    p = ln.params();
     sp.depth = depth_c;
     HIPCHK(tm.start());
-    for (int e0 = 0; e0 < E; e0 += ne_max) HIPCHK(phm::launch_ll_expm(p, e0, std::min(ne_max, E - e0), nullptr));
+    st = ln.expm(p);
+    if (st) return st;
     HIPCHK(phm::launch_sm_table(sp, nullptr));
     HIPCHK(tm.stop());
     HIPCHK(tm.elapsed(ms));
     kernel_ms += ms;
 
-    for (int64_t s0 = 0; s0 < S_eval; s0 += Sc_max) {
-      const int64_t Sc = std::min<int64_t>(Sc_max, S_eval - s0);
+    for (int64_t s0 = 0; s0 < S_eval; s0 += pl.Sc_max) {
+      const int64_t Sc = std::min<int64_t>(pl.Sc_max, S_eval - s0);
       p.n_sites = (int)Sc;
-      if (in.paired) {                                   // [tip][Kp]: lane k reads the tips of its own site
-        std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);
-        for (int64_t k = 0; k < Kc; ++k) {
-          const int32_t* y = in.tips_of(in.site_of_model[m0 + k]);
-          for (int t = 0; t < T; ++t) tips_h[(size_t)t * Kp + k] = (uint8_t)y[t];
-        }
-        HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Kp, hipMemcpyHostToDevice));
-      } else {                                           // [site][tip]
-        for (int64_t s = 0; s < Sc; ++s) {
-          const int32_t* y = in.tips_of(s0 + s);
-          for (int t = 0; t < T; ++t) tips_h[(size_t)s * T + t] = (uint8_t)y[t];
-        }
-        HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Sc, hipMemcpyHostToDevice));
-      }
+      st = ln.stage_tips(s0, Sc);
+      if (st) return st;
       HIPCHK(tm.start());
-      HIPCHK(phm::launch_ll_tips(p, nullptr));
-      for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-        HIPCHK(phm::launch_ll_up(p, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
-      HIPCHK(phm::launch_ll_root(p, sp.root_row, nullptr));
+      st = ln.passes(p);
+      if (st) return st;
       HIPCHK(tm.stop());
-      HIPCHK(hipMemcpy(llh.data(), dll.p, sizeof(double) * (size_t)Sc * Kp, hipMemcpyDeviceToHost));
+      st = ln.fetch_ll(Sc);
+      if (st) return st;
       HIPCHK(tm.elapsed(ms));
       kernel_ms += ms;
       for (int64_t s = 0; s < Sc; ++s)
         for (int64_t k = 0; k < Kc; ++k) {
           const int64_t site = in.paired ? in.site_of_model[m0 + k] : s0 + s;
-          const int64_t ev = eval_of(in, s0 + s, m0 + k);
-          const double ll = llh[(size_t)s * Kp + k];
+          const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
+          const double ll = ln.llh[(size_t)s * Kp + k];
           loglik[ev] = ll;
           if (!std::isfinite(ll)) {                      // an impossible evaluation is not drawn: NaN rows, zero nodes, empty map rows
             for (int64_t h = ev * D; h < (ev + 1) * D; ++h) {

@@ -1,6 +1,6 @@
 // phm_scores_api.cpp -- C-ABI of the exact conditional expectations for many rate matrices in one call
 // (phm_expected_stats_models): phm_loglik_models' validation (ll_validate) and its limit on mu t_b, then per
-// device and per chunk of models P_k(t_b) once and, per chunk of sites, section 17's tips / up / root launches followed by the
+// device and per chunk of models P_k(t_b) once and, per chunk of sites, section 17's tips / up / root launches (LlLanes) followed by the
 // down pass, the branch stage and the run totals of phm_scores.hip.  2..8 states run with the models across the lanes.  9..64
 // states are NOT batched: the models go one after the other through phm_expected_stats itself, for correctness only.
 #include "phm_loglik_host.h"
@@ -30,9 +30,6 @@ struct ScInput {
   phm_options opt;
 };
 
-// evaluation index of (site, model)
-inline int64_t eval_of(const LlInput& in, int64_t site, int64_t model) { return in.paired ? model : site + (int64_t)in.S * model; }
-
 int32_t sc_prepare(ScInput& sc) {
   LlInput& in = sc.ll;
   const int n = in.n;
@@ -48,23 +45,7 @@ int32_t sc_prepare(ScInput& sc) {
       if (mu * in.edge_length[b] > EX_MAX_JUMP_MEAN)
         return fail(PHM_ERR_UNSUPPORTED, "model " + std::to_string(k) + ", edge row " + std::to_string(b + 1) + ": max(-q_ii) * t_b above 1e6");
   }
-  const phm::Schedule& s = in.sched;
-  const int T = in.T;
-  std::vector<int32_t> order, up_of(s.n_node, -1);
-  for (int k = 0; k < s.n_node; ++k) up_of[s.up[k].parent] = k;
-  auto row_of = [T](int32_t c) { return c >= 0 ? T + c : ~c; };
-  phm::depth_levels(s, order, sc.down_off);
-  sc.child_row.assign(in.E, 0);
-  for (int32_t k : order) {
-    const phm::DownStep& d = s.down[k];
-    const phm::UpStep& u = s.up[up_of[d.parent]];
-    const int side = u.edge[0] == d.edge ? 1 : 0;                  // the sibling branch
-    phm::ExDown x = {};
-    x.edge = d.edge; x.parent = T + d.parent; x.child = row_of(d.child);
-    x.sib_edge = u.edge[side]; x.sib_child = row_of(u.child[side]);
-    sc.down.push_back(x);
-    sc.child_row[d.edge] = x.child;
-  }
+  ex_down_schedule(in.sched, in.T, sc.down, sc.down_off, &sc.child_row);
   return PHM_OK;
 }
 
@@ -73,117 +54,72 @@ int32_t sc_lanes_device(const ScInput& sc, int32_t device, int64_t first, int64_
   int32_t st = select_device(device);
   if (st) return st;
   const LlInput& in = sc.ll;
-  const int n = in.n, E = in.E, NT = in.NT, T = in.T, cols = sc.cols;
+  const int n = in.n, E = in.E, NT = in.NT, cols = sc.cols;
   const size_t nn = (size_t)n * n;
-  const int64_t S_eval = in.paired ? 1 : in.S;           // sites per model
+  const int64_t S_eval = in.sites_per_model();
   const int n_runs = (E + phm::SC_RUN - 1) / phm::SC_RUN;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
   double kernel_ms = 0.0, ms = 0.0;
-  DevBuf dt, dobs, dup, ddown, dchild;
-  HIPCHK(upload(dt, in.edge_length)); HIPCHK(upload(dobs, in.obs)); HIPCHK(upload(dup, in.up));
+  LlLanes ln(in);
+  DevBuf ddown, dchild;
+  st = ln.upload_tree();
+  if (st) return st;
   HIPCHK(upload(ddown, sc.down)); HIPCHK(upload(dchild, sc.child_row));
 
-  // Chunks by free HBM: per model Q, pid, P, mu and B; per evaluation L, O, F with their exponents, ll, lam and the totals (and a
-  // tip byte per tip when paired).  The run totals of one branch-stage launch take a fixed share.
+  // On top of section 17's footprint: per model mu and B; per evaluation O, F with their exponents, lam and the totals.  The run
+  // totals of one branch-stage launch take a fixed share.
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
   const bool ws = n > phm::LL_REG_MAX;
-  const size_t fixed = SC_SCRATCH + (ws ? LL_WORK : 0);
-  const size_t budget = free_b / 2 > fixed ? free_b / 2 - fixed : 0;
-  const size_t per_model = sizeof(double) * ((size_t)E * nn + 2 * nn + n + 1) + sizeof(uint32_t);
-  const size_t per_eval = sizeof(double) * ((size_t)NT * (2 * n + 2) + (size_t)E * (n + 1) + 2 + cols) + (in.paired ? (size_t)T : 0);
-  int64_t Sc_max = std::min<int64_t>(S_eval, 65535);
-  int64_t Kc_max = (int64_t)(budget / (per_model + per_eval * (size_t)Sc_max)) / 64 * 64;
-  if (Kc_max < 64) {
-    Kc_max = 64;
-    const size_t per64 = budget / 64;
-    Sc_max = std::max<int64_t>(1, std::min<int64_t>(Sc_max, per64 > per_model ? (int64_t)((per64 - per_model) / per_eval) : 1));
-  }
   const int chunk = g_phm_debug.expect_chunk;
-  if (chunk > 0) {
-    Kc_max = std::min<int64_t>(Kc_max, ((int64_t)chunk + 63) / 64 * 64);
-    Sc_max = std::min<int64_t>(Sc_max, chunk);
-  }
-  Kc_max = std::min<int64_t>(Kc_max, (count + 63) / 64 * 64);
-  const size_t Kpm = (size_t)Kc_max, Evm = Kpm * (size_t)Sc_max;
-  int ne_max = E;
-  if (ws) ne_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)E, (size_t)65535, LL_WORK / (sizeof(double) * 4 * nn * Kpm)}));
-  ne_max = std::min(ne_max, 65535);
+  const LlPlan pl = ll_plan(free_b, in, count, chunk, SC_SCRATCH, sizeof(double) * (nn + 1),
+                            sizeof(double) * ((size_t)NT * (n + 1) + (size_t)E * (n + 1) + 1 + cols));
+  const size_t Kpm = (size_t)pl.Kc_max, Evm = Kpm * (size_t)pl.Sc_max;
   int nr_max = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_runs, (size_t)65535, SC_SCRATCH / (sizeof(double) * cols * Evm)}));
-  if (chunk > 0) {
-    ne_max = std::min(ne_max, chunk);
-    nr_max = std::min(nr_max, std::max(1, chunk / phm::SC_RUN));
-  }
+  if (chunk > 0) nr_max = std::min(nr_max, std::max(1, chunk / phm::SC_RUN));
 
-  DevBuf dQ, dpid, dP, dwork, dbad, dmu, dB, dL, dsL, dO, dsO, dF, dsF, dll, dlam, dtips, druns, dtot;
-  HIPCHK(dQ.alloc(sizeof(double) * nn * Kpm)); HIPCHK(dpid.alloc(sizeof(double) * n * Kpm));
-  HIPCHK(dP.alloc(sizeof(double) * (size_t)E * nn * Kpm)); HIPCHK(dbad.alloc(sizeof(uint32_t) * Kpm));
+  DevBuf dmu, dB, dO, dsO, dF, dsF, dlam, druns, dtot;
+  st = ln.alloc(pl);
+  if (st) return st;
   HIPCHK(dmu.alloc(sizeof(double) * Kpm));
-  if (ws) { HIPCHK(dwork.alloc(sizeof(double) * 4 * nn * Kpm * (size_t)ne_max)); HIPCHK(dB.alloc(sizeof(double) * nn * Kpm)); }
-  HIPCHK(dL.alloc(sizeof(double) * (size_t)NT * n * Evm)); HIPCHK(dsL.alloc(sizeof(double) * (size_t)NT * Evm));
+  if (ws) HIPCHK(dB.alloc(sizeof(double) * nn * Kpm));
   HIPCHK(dO.alloc(sizeof(double) * (size_t)NT * n * Evm)); HIPCHK(dsO.alloc(sizeof(double) * (size_t)NT * Evm));
   HIPCHK(dF.alloc(sizeof(double) * (size_t)E * n * Evm)); HIPCHK(dsF.alloc(sizeof(double) * (size_t)E * Evm));
-  HIPCHK(dll.alloc(sizeof(double) * Evm)); HIPCHK(dlam.alloc(sizeof(double) * Evm));
-  HIPCHK(dtips.alloc(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)Sc_max));
+  HIPCHK(dlam.alloc(sizeof(double) * Evm));
   HIPCHK(druns.alloc(sizeof(double) * cols * (size_t)nr_max * Evm)); HIPCHK(dtot.alloc(sizeof(double) * cols * Evm));
-  std::vector<double> Qh(nn * Kpm), pidh((size_t)n * Kpm), llh(Evm), toth((size_t)cols * Evm);
-  std::vector<uint8_t> tips_h(in.paired ? (size_t)T * Kpm : (size_t)T * (size_t)Sc_max);
+  std::vector<double> toth((size_t)cols * Evm);
 
-  for (int64_t c0 = 0; c0 < count; c0 += Kc_max) {
-    const int64_t Kc = std::min<int64_t>(Kc_max, count - c0);
-    const int Kp = (int)((Kc + 63) / 64 * 64);
-    const int64_t m0 = first + c0;                       // global index of this chunk's first model
-    std::fill(Qh.begin(), Qh.end(), 0.0);
-    std::fill(pidh.begin(), pidh.end(), 0.0);
-    for (int64_t k = 0; k < Kc; ++k) {
-      for (size_t e = 0; e < nn; ++e) Qh[e * Kp + k] = in.Qr[(size_t)(m0 + k) * nn + e];
-      for (int i = 0; i < n; ++i) pidh[(size_t)i * Kp + k] = in.pid[(size_t)(m0 + k) * n + i];
-    }
-    HIPCHK(hipMemcpy(dQ.p, Qh.data(), sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dpid.p, pidh.data(), sizeof(double) * n * Kp, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dbad.p, 0, sizeof(uint32_t) * Kp));
+  for (int64_t c0 = 0; c0 < count; c0 += pl.Kc_max) {
+    const int64_t Kc = std::min<int64_t>(pl.Kc_max, count - c0);
+    st = ln.load_models(first + c0, Kc);
+    if (st) return st;
+    const int Kp = ln.Kp;
+    const int64_t m0 = ln.m0;                            // global index of this chunk's first model
     phm::ScParams sp = {};
     phm::LlParams& p = sp.ll;
-    p.n = n; p.n_tips = T; p.Kp = Kp; p.Kc = (int)Kc; p.paired = in.paired ? 1 : 0;
-    p.Q = dQ.as<double>(); p.pid = dpid.as<double>(); p.t = dt.as<double>(); p.P = dP.as<double>();
-    p.work = ws ? dwork.as<double>() : nullptr; p.bad = dbad.as<uint32_t>(); p.tips = dtips.as<uint8_t>();
-    p.obs = dobs.as<int32_t>(); p.L = dL.as<double>(); p.sL = dsL.as<double>(); p.ll = dll.as<double>();
-    p.n_sites = 1;
-    sp.n_edge = E; sp.root = T + in.sched.root; sp.mu = dmu.as<double>(); sp.B = ws ? dB.as<double>() : nullptr;
+    p = ln.params();
+    sp.n_edge = E; sp.root = in.T + in.sched.root; sp.mu = dmu.as<double>(); sp.B = ws ? dB.as<double>() : nullptr;
     sp.child = dchild.as<int32_t>(); sp.O = dO.as<double>(); sp.sO = dsO.as<double>(); sp.F = dF.as<double>();
     sp.sF = dsF.as<double>(); sp.lam = dlam.as<double>(); sp.runs = druns.as<double>(); sp.tot = dtot.as<double>();
     HIPCHK(tm.start());
-    for (int e0 = 0; e0 < E; e0 += ne_max) HIPCHK(phm::launch_ll_expm(p, e0, std::min(ne_max, E - e0), nullptr));
+    st = ln.expm(p);
+    if (st) return st;
     HIPCHK(phm::launch_sc_model(sp, nullptr));
     HIPCHK(tm.stop());
     HIPCHK(tm.elapsed(ms));
     kernel_ms += ms;
 
-    for (int64_t s0 = 0; s0 < S_eval; s0 += Sc_max) {
-      const int64_t Sc = std::min<int64_t>(Sc_max, S_eval - s0);
+    for (int64_t s0 = 0; s0 < S_eval; s0 += pl.Sc_max) {
+      const int64_t Sc = std::min<int64_t>(pl.Sc_max, S_eval - s0);
       p.n_sites = (int)Sc;
       const size_t Ev = (size_t)Sc * Kp;
-      if (in.paired) {                                   // [tip][Kp]: lane k reads the tips of its own site
-        std::fill(tips_h.begin(), tips_h.end(), (uint8_t)0);
-        for (int64_t k = 0; k < Kc; ++k) {
-          const int32_t* y = in.tips_of(in.site_of_model[m0 + k]);
-          for (int t = 0; t < T; ++t) tips_h[(size_t)t * Kp + k] = (uint8_t)y[t];
-        }
-        HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Kp, hipMemcpyHostToDevice));
-      } else {                                           // [site][tip]
-        for (int64_t s = 0; s < Sc; ++s) {
-          const int32_t* y = in.tips_of(s0 + s);
-          for (int t = 0; t < T; ++t) tips_h[(size_t)s * T + t] = (uint8_t)y[t];
-        }
-        HIPCHK(hipMemcpy(dtips.p, tips_h.data(), (size_t)T * Sc, hipMemcpyHostToDevice));
-      }
+      st = ln.stage_tips(s0, Sc);
+      if (st) return st;
       HIPCHK(hipMemset(dtot.p, 0, sizeof(double) * cols * Ev));
       HIPCHK(tm.start());
-      HIPCHK(phm::launch_ll_tips(p, nullptr));
-      for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-        HIPCHK(phm::launch_ll_up(p, dup.as<phm::UpStep>() + in.up_off[l], in.up_off[l + 1] - in.up_off[l], nullptr));
-      HIPCHK(phm::launch_ll_root(p, sp.root, nullptr));
+      st = ln.passes(p);
+      if (st) return st;
       HIPCHK(phm::launch_sc_root(sp, nullptr));
       for (size_t l = 0; l + 1 < sc.down_off.size(); ++l)
         HIPCHK(phm::launch_sc_down(sp, ddown.as<phm::ExDown>() + sc.down_off[l], sc.down_off[l + 1] - sc.down_off[l], nullptr));
@@ -193,14 +129,15 @@ int32_t sc_lanes_device(const ScInput& sc, int32_t device, int64_t first, int64_
         HIPCHK(phm::launch_sc_total(sp, nr, nullptr));
       }
       HIPCHK(tm.stop());
-      HIPCHK(hipMemcpy(llh.data(), dll.p, sizeof(double) * Ev, hipMemcpyDeviceToHost));
+      st = ln.fetch_ll(Sc);
+      if (st) return st;
       HIPCHK(hipMemcpy(toth.data(), dtot.p, sizeof(double) * cols * Ev, hipMemcpyDeviceToHost));
       HIPCHK(tm.elapsed(ms));
       kernel_ms += ms;
       for (int64_t s = 0; s < Sc; ++s)
         for (int64_t k = 0; k < Kc; ++k) {
-          const int64_t ev = eval_of(in, s0 + s, m0 + k);
-          const double ll = llh[(size_t)s * Kp + k];
+          const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
+          const double ll = ln.llh[(size_t)s * Kp + k];
           loglik[ev] = ll;
           const bool possible = std::isfinite(ll);       // an impossible evaluation: -inf and a row of NaN
           for (int col = 0; col < cols; ++col)
@@ -239,7 +176,7 @@ int32_t sc_wide_device(const ScInput& sc, int32_t device, int64_t first, int64_t
     };
     auto put = [&](int64_t lo, int64_t cnt, bool ok) {
       for (int64_t s = 0; s < cnt; ++s) {
-        const int64_t ev = eval_of(in, lo + s, m);
+        const int64_t ev = ll_eval_of(in, lo + s, m);
         loglik[ev] = ok ? ll_h[s] : ninf;
         for (int col = 0; col < cols; ++col) stats[ev + sc.n_eval * col] = ok ? st_h[(size_t)s + (size_t)cnt * col] : nan;
       }
