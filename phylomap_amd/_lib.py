@@ -78,10 +78,71 @@ class Info(C.Structure):
 
 
 def _p(a, t):
+    """pointer to the data of ``a`` (None: NULL).  It holds a reference to ``a`` (numpy's ``data_as``), so an argument tuple
+    of such pointers keeps its arrays alive by itself; every array pointer handed to the library is made here."""
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
 
 _lib = None
+
+
+def _argtypes():
+    """{symbol: argtypes} of include/phylomap_hip.h, from the argument runs that the entry points share"""
+    i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
+    pi, pl, pd, pt, po = (C.POINTER(t) for t in (C.c_int32, C.c_int64, C.c_double, Tree, Options))
+    sweep = [pt, i32, pd, pd, pd, f64, pi, pi, i32, i32]     # tree, n, Q, pid, B, Omega, nen, nodelist, root, N
+    prior = [pd, i32]
+    out = [po, pd]                                           # options, statistics
+    shot = [pt, i32, pd, pd, pi, po]                         # tree, n, Q, pid, observe, options
+    models = [pt, i32, i32, pd, pd, i32, pi, pi]             # tree, n, K, Qs, pid, n_pid, observe, site_of_model
+    maps = [pl, i64, pd, pi]                                 # offsets, capacity, dwell, state
+    exp = [pt, i32, pd, pd, pi, pi, i32, i32, pd, pd, pd] + out
+    expm_eigen = [i32, pd, pd, pd, pd, i32, i32, pd, pd]
+    expm_pade = [i32, pd, pd, i32, i32, pd, pd]
+    ancestral = models + [pi, i32, po, pd, pd, pi, pd]
+    t = {"phm_status_string": [i32],
+         "phm_engine_create": [pt, C.POINTER(Model), po, i32, C.POINTER(vp)],
+         "phm_engine_create_multi": [pt, i32, C.POINTER(Model), po, i32, C.POINTER(vp)],
+         "phm_engine_run": [vp, i32, vp],
+         "phm_engine_sync": [vp],
+         "phm_engine_read_stats": [vp, i32, i32, pd],
+         "phm_engine_dump": [vp, i32, pi, pd, i32, pi, pd],
+         "phm_engine_info": [vp, C.POINTER(Info)],
+         "phm_tree_orders": [i32, i32, pi, pi, pi, pi],
+         "phm_engine_time_pruning": [vp, i32, vp, pd],
+         "phm_engine_reduced_stats_device": [vp, i32, i32, vp, C.POINTER(vp)],
+         "phm_engine_phase_ms": [vp, pd],
+         "phm_engine_destroy": [vp],
+         "phm_maketreelistMCMCmt": [pt, i32, i32, pd, pd, pd, f64, pi, pi, pi, i32] + prior + out,
+         "phm_engine_set_model": [vp, pd],
+         "phm_qupdate_apply": [i32, i32, pd, f64, pd, i32, pd, C.c_uint64, C.c_uint32],
+         "phm_maketreelistEXP": exp,
+         "phm_maketreelistEXP_maps": exp + maps,
+         "phm_expm_eigen": expm_eigen,
+         "phm_expm_eigen_mfma": expm_eigen,
+         "phm_expm_pade": expm_pade,
+         "phm_expm_pade_mfma": expm_pade,
+         "phm_set_debug_options": [C.POINTER(DebugOptions)],
+         "phm_simulate_histories": shot + [pi, pi, pd],
+         "phm_simulate_histories_maps": shot + [pi, pi, pd] + maps,
+         "phm_maketreelistMCMC_maps": [i32] + sweep + [pi, i32] + out + maps,
+         "phm_expected_stats": shot + [pd, pd, pd, pd],
+         "phm_expected_through_time": shot + [i32, pd, pd, pd, i64, pi, pd, pd, pd],
+         "phm_loglik_models": models + [po, pd],
+         "phm_expected_stats_models": models + [po, pd, pd],
+         "phm_sample_histories_models": models + [i32, po, pd, pd, pi] + maps,
+         "phm_gibbs_rates": [pt, i32, pi, i32, i32, pd, pd, i32, f64, pd, i32, pi, pi, i32, i32, po, pd, pd, pd, pi, pi],
+         "phm_ancestral_models": ancestral,
+         "phm_ancestral_models_wide": ancestral,
+         "phm_simulate_histories_models": models[:7] + [i32, po, pi, pi, pd] + maps,
+         "phm_sparse_kernel_source": [i32, pd, C.c_char_p, i32]}
+    t["phm_maketreelistMCMCksmt"] = t["phm_maketreelistMCMCmt"]
+    for name in ("phm_maketreelistMCMC", "phm_maketreelistMCMC_bigtree", "phm_SPARSEmaketreelistMCMC", "phm_maketreelistMCMCks_sweep",
+                 "phm_maketreelistMCMCbf_sweep"):
+        t[name] = sweep + out
+    for name in ("phm_maketreelistMCMCbf", "phm_maketreelistMCMCks", "phm_maketreelistMCMC2sDICt", "phm_maketreelistMCMCksDICt"):
+        t[name] = sweep + prior + out
+    return t
 
 
 def load():
@@ -94,103 +155,10 @@ def load():
         L = C.CDLL(LIB_PATH)
         L.phm_last_error.restype = C.c_char_p
         L.phm_status_string.restype = C.c_char_p
-        L.phm_status_string.argtypes = [C.c_int32]
         L.phm_last_kernel_ms.restype = C.c_double
-        L.phm_engine_create.argtypes = [C.POINTER(Tree), C.POINTER(Model), C.POINTER(Options), C.c_int32,
-                                        C.POINTER(C.c_void_p)]
-        L.phm_engine_create_multi.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(Model), C.POINTER(Options), C.c_int32,
-                                              C.POINTER(C.c_void_p)]
-        L.phm_engine_run.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        L.phm_engine_sync.argtypes = [C.c_void_p]
-        L.phm_engine_read_stats.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
-        L.phm_engine_dump.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,
-                                      C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-        L.phm_engine_info.argtypes = [C.c_void_p, C.POINTER(Info)]
-        L.phm_tree_orders.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.phm_engine_time_pruning.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]
-        L.phm_engine_reduced_stats_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                                      C.POINTER(C.c_void_p)]
-        L.phm_engine_phase_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        L.phm_engine_destroy.argtypes = [C.c_void_p]
         L.phm_engine_destroy.restype = None
-        mc = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-              C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(Options),
-              C.POINTER(C.c_double)]
-        L.phm_maketreelistMCMC.argtypes = mc
-        L.phm_maketreelistMCMC_bigtree.argtypes = mc
-        L.phm_SPARSEmaketreelistMCMC.argtypes = mc
-        L.phm_maketreelistMCMCks_sweep.argtypes = mc
-        L.phm_maketreelistMCMCbf_sweep.argtypes = mc
-        mcq = mc[:10] + [C.POINTER(C.c_double), C.c_int32] + mc[10:]
-        L.phm_maketreelistMCMCbf.argtypes = mcq
-        L.phm_maketreelistMCMCks.argtypes = mcq
-        L.phm_maketreelistMCMC2sDICt.argtypes = mcq
-        L.phm_maketreelistMCMCksDICt.argtypes = mcq
-        mt = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-              C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
-              C.POINTER(C.c_double), C.c_int32, C.POINTER(Options), C.POINTER(C.c_double)]
-        L.phm_maketreelistMCMCmt.argtypes = mt
-        L.phm_maketreelistMCMCksmt.argtypes = mt
-        L.phm_engine_set_model.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-        L.phm_qupdate_apply.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double),
-                                        C.c_int32, C.POINTER(C.c_double), C.c_uint64, C.c_uint32]
-        L.phm_maketreelistEXP.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
-                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                          C.POINTER(Options), C.POINTER(C.c_double)]
-        L.phm_expm_eigen.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_double), C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                     C.POINTER(C.c_double)]
-        L.phm_expm_eigen_mfma.argtypes = L.phm_expm_eigen.argtypes
-        L.phm_expm_pade_mfma.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32,
-                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.phm_expm_pade.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32,
-                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.phm_set_debug_options.argtypes = [C.POINTER(DebugOptions)]
-        L.phm_simulate_histories.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                             C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_int32),
-                                             C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-        L.phm_simulate_histories_maps.argtypes = L.phm_simulate_histories.argtypes + [
-            C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.phm_maketreelistEXP_maps.argtypes = L.phm_maketreelistEXP.argtypes + [
-            C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.phm_maketreelistMCMC_maps.argtypes = [C.c_int32] + mc[:10] + [C.POINTER(C.c_int32), C.c_int32] + mc[10:] + [
-            C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.phm_expected_stats.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                         C.POINTER(C.c_int32), C.POINTER(Options), C.POINTER(C.c_double),
-                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.phm_expected_through_time.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                                C.POINTER(C.c_int32), C.POINTER(Options), C.c_int32, C.POINTER(C.c_double),
-                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32),
-                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.phm_loglik_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(Options),
-                                        C.POINTER(C.c_double)]
-        L.phm_expected_stats_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                                C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                                C.POINTER(Options), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.phm_sample_histories_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                                  C.c_int32, C.POINTER(Options), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_double),
-                                                  C.POINTER(C.c_int32)]
-        L.phm_gibbs_rates.argtypes = [C.POINTER(Tree), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
-                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_double, C.POINTER(C.c_double),
-                                      C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32,
-                                      C.POINTER(Options), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.phm_ancestral_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                           C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32,
-                                           C.POINTER(Options), C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                           C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-        L.phm_ancestral_models_wide.argtypes = L.phm_ancestral_models.argtypes
-        L.phm_simulate_histories_models.argtypes = [C.POINTER(Tree), C.c_int32, C.c_int32, C.POINTER(C.c_double),
-                                                    C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
-                                                    C.POINTER(Options), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                                    C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int64,
-                                                    C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-        L.phm_sparse_kernel_source.argtypes = [C.c_int32, C.POINTER(C.c_double), C.c_char_p, C.c_int32]
+        for name, types in _argtypes().items():
+            getattr(L, name).argtypes = types
         for which, mirror in enumerate((Options, Info, Tree, Model, DebugOptions)):      # the ctypes mirrors must match the C layout
             if L.phm_struct_size(which) != C.sizeof(mirror):
                 raise RuntimeError(f"{LIB_PATH}: {mirror.__name__} is {L.phm_struct_size(which)} bytes in the library, "
@@ -204,18 +172,41 @@ def check(status):
         raise PhmError(status, load().phm_last_error().decode())
 
 
+def _flat_edge(edge):
+    """(E, the E x 2 edge table as column-major int32 in one row): the one place where an edge table is flattened"""
+    edge = np.asarray(edge, dtype=np.int32)
+    return edge.shape[0], np.asfortranarray(edge).reshape(-1, order="F").copy()
+
+
+def _tip_states(states):
+    """tip states in any shape as C-contiguous int32 (R may hand doubles, :910)"""
+    return np.ascontiguousarray(np.asarray(states).round(), dtype=np.int32)
+
+
+class PlainTree:
+    """``phm_tree`` without paths, as the one-shot calls take it: the edge table of the R-list-shaped ``z``, its lengths,
+    ``Nnode`` and, with ``tips``, tip states in any shape.  Holds the struct ``c``, the arrays it points into and T, E, NT."""
+
+    def __init__(self, z, tips=None):
+        self.E, self.edge = _flat_edge(z["edge"])
+        self.edge_length = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
+        Nn = int(z["Nnode"])
+        self.T = self.E - Nn + 1
+        self.NT = self.T + Nn
+        self.states = None if tips is None else _tip_states(tips)
+        self.c = Tree(self.T, Nn, self.E, _p(self.edge, C.c_int32), _p(self.edge_length, C.c_double),
+                      _p(None if tips is None else self.states.reshape(-1), C.c_int32), None, None, None)
+
+
 class FlatTree:
-    """Flattens the R-list-shaped tree object ``z`` into the plain arrays of ``phm_tree`` (and keeps them alive)."""
+    """Flattens the R-list-shaped tree object ``z`` with its paths into the plain arrays of ``phm_tree`` (and keeps them alive)."""
 
     def __init__(self, z, states=None):
-        edge = np.asarray(z["edge"], dtype=np.int32)
-        if edge.ndim != 2 or edge.shape[1] != 2:
+        if np.ndim(z["edge"]) != 2 or np.shape(z["edge"])[1] != 2:
             raise ValueError("z['edge'] must be E x 2")
-        self.E = edge.shape[0]
-        st = z["states"] if states is None else states
-        self.states = np.ascontiguousarray(np.asarray(st).round(), dtype=np.int32)   # R may hand doubles (:910)
+        self.E, self.edge = _flat_edge(z["edge"])
+        self.states = _tip_states(z["states"] if states is None else states)
         self.T = int(np.asarray(z["states"]).shape[-1])
-        self.edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
         el = z.get("edge.length")
         self.edge_length = None if el is None else np.ascontiguousarray(el, dtype=np.float64)
         lens = [len(m) for m in z["maps"]]
@@ -241,15 +232,13 @@ class FlatTreeList:
 
 def tree_orders(z):
     """(nen, nodelist, root) computed natively in O(E): phm_tree_orders, the replacement of R/sumstatMCMC.R:1-18."""
-    edge = np.asarray(z["edge"], dtype=np.int32)
-    E = edge.shape[0]
-    flat = np.asfortranarray(edge).reshape(-1, order="F").copy()
-    T = int(z["Nnode"]) + 1
+    E, flat = _flat_edge(z["edge"])
+    Nn = int(z["Nnode"])
     nen = np.zeros(E, dtype=np.int32)
-    nodelist = np.zeros(max(int(z["Nnode"]) - 1, 1), dtype=np.int32)
+    nodelist = np.zeros(max(Nn - 1, 1), dtype=np.int32)
     root = C.c_int32(0)
-    check(load().phm_tree_orders(T, E, _p(flat, C.c_int32), _p(nen, C.c_int32), _p(nodelist, C.c_int32), C.byref(root)))
-    return nen, nodelist[: int(z["Nnode"]) - 1], int(root.value)
+    check(load().phm_tree_orders(Nn + 1, E, _p(flat, C.c_int32), _p(nen, C.c_int32), _p(nodelist, C.c_int32), C.byref(root)))
+    return nen, nodelist[: Nn - 1], int(root.value)
 
 
 def sparse_kernel_source(M):
@@ -262,6 +251,15 @@ def sparse_kernel_source(M):
     buf = C.create_string_buffer(need)
     L.phm_sparse_kernel_source(Mf.shape[0], _p(Mf, C.c_double), buf, need)
     return buf.value.decode()
+
+
+def stat_cols(n, kind="plain"):
+    """Columns of one row of statistics at ``n`` states.  "plain": n dwell sums and n(n-1) jump counts (man/sumstatMCMC.Rd:18);
+    "ks": man/sumstatMCMCks.Rd:19; "bf" (and the tree lists' two-state form): dwell, n x n counts, Q[0,1], Q[1,0], root state or
+    tree number; "ksdic" / "bfdic": those plus log p(y|Q); "simulate": dwell, n x n counts, root state."""
+    ks = n + n * n + 2 + 3 * (n // 2 - 1) + 1
+    return {"plain": n + n * (n - 1), "ks": ks, "ksdic": ks + 1, "bf": n + n * n + 3, "bfdic": n + n * n + 4,
+            "simulate": n + n * n + 1}[kind]
 
 
 MAPPING = {"auto": 0, "replicas": 1, "branches": 2, "tiles": 3}
@@ -338,11 +336,8 @@ class Engine:
             self.ft = FlatTree(z, states)
             check(L.phm_engine_create(C.byref(self.ft.c), C.byref(self.model), C.byref(self.opt), int(max_iters),
                                       C.byref(self.h)))
-        self.cols = self.n + self.n * (self.n - 1)
-        if int(variant) in (PHM_MCMC_KS, PHM_MCMC_KSMT):
-            self.cols = self.n + self.n * self.n + 2 + 3 * (self.n // 2 - 1) + 1
-        if int(variant) in (PHM_MCMC_BF, PHM_MCMC_MT):
-            self.cols = self.n + self.n * self.n + 3
+        kind = {PHM_MCMC_KS: "ks", PHM_MCMC_KSMT: "ks", PHM_MCMC_BF: "bf", PHM_MCMC_MT: "bf"}.get(int(variant), "plain")
+        self.cols = stat_cols(self.n, kind)
         self.S = max(1, int(self.opt.n_replicas)) * n_trees      # tree-major: replica j * n_replicas + c
         self.reduce = bool(self.opt.reduce)
 

@@ -28,6 +28,28 @@ _MCMC_VARIANT = {"phm_maketreelistMCMC": _lib.PHM_MCMC, "phm_maketreelistMCMC_bi
                  "phm_maketreelistMCMCbf_sweep": _lib.PHM_MCMC_BF}
 
 
+def _one_model(Q, pid):
+    """(n, Q column-major, pid) of one model as the library takes them"""
+    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
+    return Q.shape[0], Q, np.ascontiguousarray(pid, dtype=np.float64)
+
+
+def _model_args(Q, pid, Omega):
+    """(n, the model run of every sweep's head): n, Q column-major, pid, B = I + Q / Omega (R/sumstatMCMC.R:25), Omega"""
+    n, Q, pid = _one_model(Q, pid)
+    B = np.asfortranarray(np.eye(n) + Q / Omega)
+    return n, (n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double), float(Omega))
+
+
+def _sweep_head(z, Q, pid, Omega, N, sites=None):
+    """(tree, n, head) of a one-tree sweep; the head: tree, model run, nen, nodelist, root (R/sumstatMCMC.R:22-24, native O(E))
+    and N.  ``_lib._p``'s pointers keep their arrays alive; the caller holds the tree, which owns the struct's arrays."""
+    n, model = _model_args(Q, pid, Omega)
+    nen, nodelist, root = _lib.tree_orders(z)
+    ft = _lib.FlatTree(z, sites)
+    return ft, n, (C.byref(ft.c),) + model + (_lib._p(nen, C.c_int32), _lib._p(nodelist, C.c_int32), root, int(N))
+
+
 def _mcmc(fn_name, z, Q, pid, Omega, N, sites=None, maps=False, map_iters=None, **opt):
     """``sites``: optional S x n_tips matrix of 1-based tip states -- S sites of an alignment on the same tree, one chain each
     (``n_replicas = S``, ``tips_per_replica``); the initial paths of ``z`` must be compatible with every site (e.g. internal
@@ -38,23 +60,12 @@ def _mcmc(fn_name, z, Q, pid, Omega, N, sites=None, maps=False, map_iters=None, 
     if sites is not None:
         sites = np.ascontiguousarray(np.asarray(sites).round(), dtype=np.int32)
         opt = dict(opt, n_replicas=sites.shape[0], tips_per_replica=True)
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
-    nen, nodelist, root = _lib.tree_orders(z)                                 # R/sumstatMCMC.R:22-24, native O(E)
-    B = np.asfortranarray(np.eye(n) + Q / Omega)                              # :25
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
-    ft = _lib.FlatTree(z, sites)
+    ft, n, head = _sweep_head(z, Q, pid, Omega, N, sites)
     o = _lib.make_options(**opt)
     S = max(1, int(o.n_replicas))
-    cols = n + n * (n - 1)
-    if fn_name == "phm_maketreelistMCMCks_sweep":
-        cols = n + n * n + 2 + 3 * (n // 2 - 1) + 1                         # man/sumstatMCMCks.Rd:19
-    if fn_name == "phm_maketreelistMCMCbf_sweep":
-        cols = n + n * n + 3                                                  # dwell, n x n counts, Q[0,1], Q[1,0], root state
+    cols = _lib.stat_cols(n, {"phm_maketreelistMCMCks_sweep": "ks", "phm_maketreelistMCMCbf_sweep": "bf"}.get(fn_name, "plain"))
     single = bool(o.reduce) or S == 1
     out = np.zeros((N, cols), order="F") if single else np.zeros((S, cols, N))
-    head = (C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double), float(Omega),
-            _lib._p(nen, C.c_int32), _lib._p(nodelist, C.c_int32), root, int(N))
     if not maps:
         _lib.check(getattr(L, fn_name)(*head, C.byref(o), _lib._p(out, C.c_double)))
         return out if single else out.transpose(0, 2, 1)
@@ -101,68 +112,53 @@ def sumstatMCMCbf_sweep(z, Q, pid, Omega, N, maps=False, map_iters=None, **opt):
     return _mcmc("phm_maketreelistMCMCbf_sweep", z, Q, pid, Omega, N, maps=maps, map_iters=map_iters, **opt)
 
 
-def _qupdate(fn_name, z, Q, pid, Omega, N, prior, cols, **opt):
+def _qupdate(fn_name, z, Q, pid, Omega, N, prior, kind, **opt):
     L = _lib.load()
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
-    nen, nodelist, root = _lib.tree_orders(z)
-    B = np.asfortranarray(np.eye(n) + Q / Omega)
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
+    _tree, n, head = _sweep_head(z, Q, pid, Omega, N)
     prior = np.ascontiguousarray(prior, dtype=np.float64)
-    ft = _lib.FlatTree(z)
     o = _lib.make_options(**opt)
-    out = np.zeros((N, cols), order="F")
-    st = getattr(L, fn_name)(C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double),
-                             float(Omega), _lib._p(nen, C.c_int32), _lib._p(nodelist, C.c_int32), root, int(N),
-                             _lib._p(prior, C.c_double), int(prior.size), C.byref(o), _lib._p(out, C.c_double))
-    _lib.check(st)
+    out = np.zeros((N, _lib.stat_cols(n, kind)), order="F")
+    _lib.check(getattr(L, fn_name)(*head, _lib._p(prior, C.c_double), int(prior.size), C.byref(o), _lib._p(out, C.c_double)))
     return out
 
 
 def sumstatMCMCbf(z, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMCbf.R:19-35 -> phm_maketreelistMCMCbf: two-state model, rates re-drawn after every sweep.
     Columns: time 0, time 1, n00, n01, n10, n11, l01, l10, root_state (R/sumstatMCMCbf.R:33).  ``Q`` is not modified."""
-    return _qupdate("phm_maketreelistMCMCbf", z, Q, pid, Omega, N, prior, 9, **opt)
+    return _qupdate("phm_maketreelistMCMCbf", z, Q, pid, Omega, N, prior, "bf", **opt)
 
 
 def sumstatMCMCks(z, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMCks.R:19-33 -> phm_maketreelistMCMCks: hidden-rates model with k regimes (n = 2k+2), all 2+3k rate
     parameters updated after every sweep.  Layout man/sumstatMCMCks.Rd:19.  ``Q`` is not modified."""
-    n = np.asarray(Q).shape[0]
-    return _qupdate("phm_maketreelistMCMCks", z, Q, pid, Omega, N, prior, n + n * n + 2 + 3 * (n // 2 - 1) + 1, **opt)
+    return _qupdate("phm_maketreelistMCMCks", z, Q, pid, Omega, N, prior, "ks", **opt)
 
 
 def sumstatMCMC2sDICt(z, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMC2sDICt.R -> phm_maketreelistMCMC2sDICt: ``sumstatMCMCbf`` plus log p(y|Q) (matrix exponentiation) per
     iteration; columns time 0, time 1, n00, n01, n10, n11, l01, l10, root_state, log(p(y|Q))."""
-    return _qupdate("phm_maketreelistMCMC2sDICt", z, Q, pid, Omega, N, prior, 10, **opt)
+    return _qupdate("phm_maketreelistMCMC2sDICt", z, Q, pid, Omega, N, prior, "bfdic", **opt)
 
 
 def sumstatMCMCksDICt(z, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMCksDICt.R -> phm_maketreelistMCMCksDICt: ``sumstatMCMCks`` plus log p(y|Q) per iteration (last column)."""
-    n = np.asarray(Q).shape[0]
-    return _qupdate("phm_maketreelistMCMCksDICt", z, Q, pid, Omega, N, prior, n + n * n + 2 + 3 * (n // 2 - 1) + 2, **opt)
+    return _qupdate("phm_maketreelistMCMCksDICt", z, Q, pid, Omega, N, prior, "ksdic", **opt)
 
 
-def _qupdate_mt(fn_name, treelist, Q, pid, Omega, N, prior, cols, **opt):
+def _qupdate_mt(fn_name, treelist, Q, pid, Omega, N, prior, kind, **opt):
     L = _lib.load()
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
+    n, model = _model_args(Q, pid, Omega)
     orders = [_lib.tree_orders(z) for z in treelist]                 # R/sumstatMCMCmt.R:37-46, one row per tree
     nen_m = np.asfortranarray(np.stack([o[0] for o in orders]), dtype=np.int32)
     nodelist_m = np.asfortranarray(np.stack([o[1] for o in orders]), dtype=np.int32)
     roots = np.ascontiguousarray([o[2] for o in orders], dtype=np.int32)
-    B = np.asfortranarray(np.eye(n) + Q / Omega)
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
     prior = np.ascontiguousarray(prior, dtype=np.float64)
     ftl = _lib.FlatTreeList(treelist)
     o = _lib.make_options(**opt)
-    out = np.zeros((N, cols), order="F")
-    st = getattr(L, fn_name)(ftl.c, ftl.n, n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(B, C.c_double),
-                             float(Omega), _lib._p(nen_m, C.c_int32), _lib._p(nodelist_m, C.c_int32),
-                             _lib._p(roots, C.c_int32), int(N), _lib._p(prior, C.c_double), int(prior.size), C.byref(o),
-                             _lib._p(out, C.c_double))
-    _lib.check(st)
+    out = np.zeros((N, _lib.stat_cols(n, kind)), order="F")
+    _lib.check(getattr(L, fn_name)(ftl.c, ftl.n, *model, _lib._p(nen_m, C.c_int32), _lib._p(nodelist_m, C.c_int32),
+                                   _lib._p(roots, C.c_int32), int(N), _lib._p(prior, C.c_double), int(prior.size), C.byref(o),
+                                   _lib._p(out, C.c_double)))
     return out
 
 
@@ -170,14 +166,13 @@ def sumstatMCMCmt(treelist, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMCmt.R:29-52 -> phm_maketreelistMCMCmt: two-state model over a list of trees (same tips, different
     topologies / branch lengths); every iteration sweeps every tree, keeps one drawn uniformly and updates the rates from
     it.  Columns: time_0, time_1, n00, n01, n10, n11, l01, l10, tree_number (0-based, as the reference stores it)."""
-    return _qupdate_mt("phm_maketreelistMCMCmt", treelist, Q, pid, Omega, N, prior, 9, **opt)
+    return _qupdate_mt("phm_maketreelistMCMCmt", treelist, Q, pid, Omega, N, prior, "bf", **opt)
 
 
 def sumstatMCMCksmt(treelist, Q, pid, Omega, N, prior, **opt):
     """R/sumstatMCMCksmt.R -> phm_maketreelistMCMCksmt: hidden-rates model (n = 2k+2) over a list of trees; ``prior`` has
     8 entries (l01, l10, kappa, gamma shape/rate pairs).  Columns as ``sumstatMCMCks`` with tree_number last."""
-    n = np.asarray(Q).shape[0]
-    return _qupdate_mt("phm_maketreelistMCMCksmt", treelist, Q, pid, Omega, N, prior, n + n * n + 2 + 3 * (n // 2 - 1) + 1, **opt)
+    return _qupdate_mt("phm_maketreelistMCMCksmt", treelist, Q, pid, Omega, N, prior, "ks", **opt)
 
 
 def eigen_decompose(Q):
@@ -196,14 +191,12 @@ def sumstatEXP(z, Q, pid, N, eig=None, maps=False, **opt):
     ``(out, maps)`` with the N sampled histories as a ``maps.Maps`` (phm_maketreelistEXP_maps: a sizing call, then a filling
     call; the (tile, branch) mapping)."""
     L = _lib.load()
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
+    n, Q, pid = _one_model(Q, pid)
     nen, nodelist, root = _lib.tree_orders(z)
     lefts, rights, d = (np.asfortranarray(np.asarray(a, dtype=np.float64)) for a in (eigen_decompose(Q) if eig is None else eig))
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
     ft = _lib.FlatTree(z)
     o = _lib.make_options(**opt)
-    out = np.zeros((N, n + n * (n - 1)), order="F")
+    out = np.zeros((N, _lib.stat_cols(n)), order="F")
     args = (C.byref(ft.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(nen, C.c_int32),
             _lib._p(nodelist, C.c_int32), root, int(N), _lib._p(lefts, C.c_double), _lib._p(rights, C.c_double),
             _lib._p(d, C.c_double), C.byref(o), _lib._p(out, C.c_double))
@@ -255,6 +248,73 @@ def expm_pade(Q, t, device=-1, mfma=False):
     return out, ms.value
 
 
+def _observe(observe, n):
+    """``observe`` as the library takes it: None, or the n observed states as int32"""
+    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
+    if obs is not None and obs.size != n:
+        raise ValueError("observe must have one entry per state")
+    return obs
+
+
+def _pid_rows(pid, n, K, per="model"):
+    """pid as [1, n] (shared) or [K, n]"""
+    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
+    if pid.shape[1] != n or pid.shape[0] not in (1, K):
+        raise ValueError(f"pid must have n entries, shared or one row per {per}")
+    return pid
+
+
+def _model_batch(Qs, pid, site_of_model=None):
+    """A batch of models as the many-model entry points take it: (K, n, Qf, pid, som) with Qf [K, n, n], each matrix
+    column-major and the model slowest, pid [1, n] or [K, n], som None ("cross") or K int32 site indices ("paired")."""
+    Qs = np.asarray(Qs, dtype=np.float64)
+    if Qs.ndim == 2:
+        Qs = Qs[None]
+    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
+        raise ValueError("Qs must be [K, n, n]")
+    K, n = Qs.shape[0], Qs.shape[1]
+    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))
+    pid = _pid_rows(pid, n, K)
+    som = None
+    if site_of_model is not None:
+        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
+        if som.size != K:
+            raise ValueError("site_of_model must have one entry per model")
+    return K, n, Qf, pid, som
+
+
+def _tips_tree(z, sites, observe, n, opt):
+    """What the calls on observed tips share: the tree with its tip states (``z['states']``, or one row of ``sites`` per site),
+    ``observe`` and the options.  ``pt`` holds the arrays the tree points into."""
+    if sites is None:
+        tips = np.asarray(z["states"]).reshape(1, -1)
+    else:
+        tips = np.atleast_2d(np.asarray(sites))
+        opt = dict(opt, n_replicas=tips.shape[0], tips_per_replica=True)
+    pt = _lib.PlainTree(z, tips)
+    if pt.states.shape[1] != pt.T:
+        raise ValueError(f"tip states must have {pt.T} columns")
+    obs = _observe(observe, n)
+    o = _lib.make_options(**opt)
+    S = max(1, int(o.n_replicas))                  # without sites: n_replicas sites that share z['states']
+    return SimpleNamespace(pt=pt, tree=pt.c, obs=obs, opt=o, E=pt.E, T=pt.T, NT=pt.NT, S=S)
+
+
+def _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt):
+    """(n, a, shape, head) of a many-model call on observed tips: ``_tips_tree``'s ``a`` (hold it: it owns the tree), the
+    outputs' leading shape, (K,) paired or (K, S) cross, and the eight arguments every such entry point begins with."""
+    K, n, Qf, pid, som = _model_batch(Qs, pid, site_of_model)
+    a = _tips_tree(z, sites, observe, n, opt)
+    head = (C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(a.obs, C.c_int32),
+            _lib._p(som, C.c_int32))
+    return n, a, (K,) if som is not None else (K, a.S), head
+
+
+def _start_rate(z, n_tips):
+    """tips / tree length: the rate around which a fit and a posterior sample start"""
+    return n_tips / float(np.sum(np.asarray(z["edge.length"], dtype=np.float64)))
+
+
 def simulate_histories(z, Q, pid, R, observe=None, nodes=False, maps=False, **opt):
     """``R`` independent forward simulations of the chain along the tree of ``z`` (sample2statehistory, R/sourceme.R:346-414)
     -> phm_simulate_histories.  Reads ``z['edge']``, ``z['edge.length']`` and ``z['Nnode']`` only.  ``observe``: n values in
@@ -265,31 +325,21 @@ def simulate_histories(z, Q, pid, R, observe=None, nodes=False, maps=False, **op
     ``maps=True`` appends the R histories as a ``maps.Maps`` (true states; phm_simulate_histories_maps: a sizing call, then a
     filling call): ``(tips, stats[, nodes], maps)``."""
     L = _lib.load()
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asarray(z["edge"], dtype=np.int32)
-    E = edge.shape[0]
-    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    Nn = int(z["Nnode"])
-    T = E - Nn + 1
-    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
-    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
-    if obs is not None and obs.size != n:
-        raise ValueError("observe must have one entry per state")
+    n, Q, pid = _one_model(Q, pid)
+    pt = _lib.PlainTree(z)
+    obs = _observe(observe, n)
     R = int(R)
     o = _lib.make_options(n_replicas=R, **opt)
-    tips = np.zeros((max(R, 1), T), dtype=np.int32)
-    nst = np.zeros((max(R, 1), T + Nn), dtype=np.int32) if nodes else None
-    stats = np.zeros((max(R, 1), n + n * n + 1), order="F")
-    args = (C.byref(tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(obs, C.c_int32), C.byref(o),
+    tips = np.zeros((max(R, 1), pt.T), dtype=np.int32)
+    nst = np.zeros((max(R, 1), pt.NT), dtype=np.int32) if nodes else None
+    stats = np.zeros((max(R, 1), _lib.stat_cols(n, "simulate")), order="F")
+    args = (C.byref(pt.c), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), _lib._p(obs, C.c_int32), C.byref(o),
             _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32), _lib._p(stats, C.c_double))
     res = (tips, stats, nst) if nodes else (tips, stats)
     if not maps:
         _lib.check(L.phm_simulate_histories(*args))
         return res
-    return res + (_two_phase_maps(L.phm_simulate_histories_maps, args, max(R, 1), E),)
+    return res + (_two_phase_maps(L.phm_simulate_histories_maps, args, max(R, 1), pt.E),)
 
 
 def simulate_state_tree(z, Q, pid, observe=None, **opt):
@@ -313,69 +363,22 @@ def simulate_histories_models(z, Qs, pid, R, observe=None, nodes=False, maps=Fal
     ``simulate_histories``' columns; ``nodes=True`` appends [K, R, n_tips + Nnode] 1-based true states, ``maps=True`` the H = K R
     histories as a ``maps.Maps`` (a sizing call, then a filling call).  Options: seed, replica_offset, device, devices."""
     L = _lib.load()
-    Qs = np.asarray(Qs, dtype=np.float64)
-    if Qs.ndim == 2:
-        Qs = Qs[None]
-    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
-        raise ValueError("Qs must be [K, n, n]")
-    K, n = Qs.shape[0], Qs.shape[1]
-    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, K):
-        raise ValueError("pid must have n entries, shared or one row per model")
-    edge = np.asarray(z["edge"], dtype=np.int32)
-    E = edge.shape[0]
-    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    Nn = int(z["Nnode"])
-    T = E - Nn + 1
-    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
-    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
-    if obs is not None and obs.size != n:
-        raise ValueError("observe must have one entry per state")
+    K, n, Qf, pid, _ = _model_batch(Qs, pid)
+    pt = _lib.PlainTree(z)
+    obs = _observe(observe, n)
     R = int(R)
     Rr = max(R, 1)                                                    # R < 1 is refused by the library; the arrays stay valid
     o = _lib.make_options(**opt)
-    cols = n + n * n + 1
-    tips = np.zeros((K, Rr, T), dtype=np.int32)
-    nst = np.zeros((K, Rr, T + Nn), dtype=np.int32) if nodes else None
-    stats = np.zeros((cols, K, Rr))                                   # column slowest, history fastest within it
-    args = (C.byref(tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(obs, C.c_int32), R,
+    tips = np.zeros((K, Rr, pt.T), dtype=np.int32)
+    nst = np.zeros((K, Rr, pt.NT), dtype=np.int32) if nodes else None
+    stats = np.zeros((_lib.stat_cols(n, "simulate"), K, Rr))         # column slowest, history fastest within it
+    args = (C.byref(pt.c), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(obs, C.c_int32), R,
             C.byref(o), _lib._p(tips, C.c_int32), _lib._p(nst, C.c_int32), _lib._p(stats, C.c_double))
     res = (tips, np.moveaxis(stats, 0, -1)) + ((nst,) if nodes else ())
     if not maps:
         _lib.check(L.phm_simulate_histories_models(*args, None, 0, None, None))
         return res
-    return res + (_two_phase_maps(L.phm_simulate_histories_models, args, K * Rr, E),)
-
-
-def _expect_args(z, Q, pid, sites, observe, opt):
-    """What phm_expected_stats and phm_expected_through_time share: the tree with its tip states (``z['states']`` or ``sites``),
-    Q, pid, observe and the options.  ``keep`` holds the arrays the tree points into."""
-    Q = np.asfortranarray(np.asarray(Q, dtype=np.float64))
-    n = Q.shape[0]
-    pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asarray(z["edge"], dtype=np.int32)
-    E = edge.shape[0]
-    flat_edge = np.asfortranarray(edge).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    Nn = int(z["Nnode"])
-    T = E - Nn + 1
-    if sites is None:
-        tips = np.ascontiguousarray(np.asarray(z["states"]).round(), dtype=np.int32).reshape(1, -1)
-    else:
-        tips = np.ascontiguousarray(np.atleast_2d(np.asarray(sites)).round(), dtype=np.int32)
-        opt = dict(opt, n_replicas=tips.shape[0], tips_per_replica=True)
-    if tips.shape[1] != T:
-        raise ValueError(f"tip states must have {T} columns")
-    tree = _lib.Tree(T, Nn, E, _lib._p(flat_edge, C.c_int32), _lib._p(el, C.c_double), _lib._p(tips.reshape(-1), C.c_int32),
-                     None, None, None)
-    obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
-    if obs is not None and obs.size != n:
-        raise ValueError("observe must have one entry per state")
-    o = _lib.make_options(**opt)
-    S = max(1, int(o.n_replicas))                  # without sites: n_replicas sites that share z['states']
-    return SimpleNamespace(keep=(flat_edge, el, tips), tree=tree, Q=Q, pid=pid, obs=obs, opt=o, n=n, E=E, NT=T + Nn, S=S)
+    return res + (_two_phase_maps(L.phm_simulate_histories_models, args, K * Rr, pt.E),)
 
 
 def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, nodes=False, **opt):
@@ -387,14 +390,14 @@ def expected_sumstat(z, Q, pid, sites=None, observe=None, per_branch=False, node
     [S, n + n(n-1)] in man/sumstatMCMC.Rd:18 column order, loglik [S] = log p(tips | Q), branch [S, n_edge, n + n(n-1)] by
     edge row, nodes [S, n_tips + Nnode, n] = P(state of node | tips) by ape node id.  Options: device, devices."""
     L = _lib.load()
-    a = _expect_args(z, Q, pid, sites, observe, opt)
-    n, S = a.n, a.S
-    cols = n + n * (n - 1)
+    n, Q, pid = _one_model(Q, pid)
+    a = _tips_tree(z, sites, observe, n, opt)
+    S, cols = a.S, _lib.stat_cols(n)
     stats = np.zeros((S, cols), order="F")
     ll = np.zeros(S)
     br = np.zeros((S, a.E, cols), order="F") if per_branch else None
     post = np.zeros((S, a.NT, n), order="F") if nodes else None
-    _lib.check(L.phm_expected_stats(C.byref(a.tree), n, _lib._p(a.Q, C.c_double), _lib._p(a.pid, C.c_double),
+    _lib.check(L.phm_expected_stats(C.byref(a.tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
                                     _lib._p(a.obs, C.c_int32), C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
                                     _lib._p(br, C.c_double), _lib._p(post, C.c_double)))
     out = [stats, ll]
@@ -415,13 +418,14 @@ def expected_through_time(z, Q, pid, bounds=None, points=None, sites=None, obser
     ``points`` [S, P, n] = P(state at the point | tips).  ``loglik`` [S] always.  ``z``, ``sites``, ``observe`` and the options
     are ``expected_sumstat``'s.  Returns a dict of those keys."""
     L = _lib.load()
-    a = _expect_args(z, Q, pid, sites, observe, opt)
-    n, S = a.n, a.S
+    n, Q, pid = _one_model(Q, pid)
+    a = _tips_tree(z, sites, observe, n, opt)
+    S = a.S
     out = {}
     bnd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1)
     K = 0 if bnd is None else bnd.size
     occ = out["occupancy"] = np.zeros((S, K, n), order="F") if K >= 1 else None
-    bins = out["bins"] = np.zeros((S, K - 1, n + n * (n - 1)), order="F") if K >= 2 else None
+    bins = out["bins"] = np.zeros((S, K - 1, _lib.stat_cols(n)), order="F") if K >= 2 else None
     pe = pp = post = None
     if points is not None:
         pe = np.ascontiguousarray(points[0], dtype=np.int32).reshape(-1)
@@ -430,7 +434,7 @@ def expected_through_time(z, Q, pid, bounds=None, points=None, sites=None, obser
             raise ValueError("points: as many edge rows as positions")
         post = out["points"] = np.zeros((S, pe.size, n), order="F")
     ll = out["loglik"] = np.zeros(S)
-    _lib.check(L.phm_expected_through_time(C.byref(a.tree), n, _lib._p(a.Q, C.c_double), _lib._p(a.pid, C.c_double),
+    _lib.check(L.phm_expected_through_time(C.byref(a.tree), n, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double),
                                            _lib._p(a.obs, C.c_int32), C.byref(a.opt), K, _lib._p(bnd, C.c_double),
                                            _lib._p(occ, C.c_double), _lib._p(bins, C.c_double), 0 if pe is None else pe.size,
                                            _lib._p(pe, C.c_int32), _lib._p(pp, C.c_double), _lib._p(post, C.c_double),
@@ -445,25 +449,9 @@ def loglik_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **op
     ``expected_sumstat``'s.  ``site_of_model`` None ("cross"): every model on every site, returns [K, S].  ``site_of_model`` = K
     0-based site indices ("paired"): model k on its own site alone, returns [K].  An impossible evaluation is ``-inf``."""
     L = _lib.load()
-    Qs = np.asarray(Qs, dtype=np.float64)
-    if Qs.ndim == 2:
-        Qs = Qs[None]
-    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
-        raise ValueError("Qs must be [K, n, n]")
-    K, n = Qs.shape[0], Qs.shape[1]
-    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
-    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, K):
-        raise ValueError("pid must have n entries, shared or one row per model")
-    som = None
-    if site_of_model is not None:
-        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
-        if som.size != K:
-            raise ValueError("site_of_model must have one entry per model")
-    out = np.zeros(K if som is not None else (K, a.S))
-    _lib.check(L.phm_loglik_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
-                                   _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), C.byref(a.opt), _lib._p(out, C.c_double)))
+    _, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
+    out = np.zeros(shape)
+    _lib.check(L.phm_loglik_models(*head, C.byref(a.opt), _lib._p(out, C.c_double)))
     return out
 
 
@@ -474,29 +462,10 @@ def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=
     [K, S] ("cross"), or [K, n + n(n-1)] and [K] with ``site_of_model`` ("paired").  ``loglik`` is ``loglik_models``' value bit
     for bit; an impossible evaluation is ``-inf`` with a row of NaN."""
     L = _lib.load()
-    Qs = np.asarray(Qs, dtype=np.float64)
-    if Qs.ndim == 2:
-        Qs = Qs[None]
-    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
-        raise ValueError("Qs must be [K, n, n]")
-    K, n = Qs.shape[0], Qs.shape[1]
-    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
-    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, K):
-        raise ValueError("pid must have n entries, shared or one row per model")
-    som = None
-    if site_of_model is not None:
-        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
-        if som.size != K:
-            raise ValueError("site_of_model must have one entry per model")
-    cols = n + n * (n - 1)
-    shape = (K,) if som is not None else (K, a.S)
+    n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
     ll = np.zeros(shape)
-    stats = np.zeros((cols,) + shape)                                # column slowest, evaluation (site fastest) within it
-    _lib.check(L.phm_expected_stats_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
-                                           _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), C.byref(a.opt),
-                                           _lib._p(stats, C.c_double), _lib._p(ll, C.c_double)))
+    stats = np.zeros((_lib.stat_cols(n),) + shape)                 # column slowest, evaluation (site fastest) within it
+    _lib.check(L.phm_expected_stats_models(*head, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double)))
     return np.moveaxis(stats, 0, -1), ll
 
 
@@ -512,32 +481,13 @@ def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=
     call) whose history index is h = (k S + s) draws + d.  An impossible evaluation (``-inf``) has NaN statistics, zero nodes and
     empty map rows.  Options: seed, replica_offset, device, devices."""
     L = _lib.load()
-    Qs = np.asarray(Qs, dtype=np.float64)
-    if Qs.ndim == 2:
-        Qs = Qs[None]
-    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
-        raise ValueError("Qs must be [K, n, n]")
-    K, n = Qs.shape[0], Qs.shape[1]
-    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
-    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, K):
-        raise ValueError("pid must have n entries, shared or one row per model")
-    som = None
-    if site_of_model is not None:
-        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
-        if som.size != K:
-            raise ValueError("site_of_model must have one entry per model")
+    n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
     D = int(draws)
-    cols = n + n * (n - 1)
-    shape = (K,) if som is not None else (K, a.S)
     ll = np.zeros(shape)
     hshape = shape + (max(D, 1),)
-    stats = np.zeros((cols,) + hshape)                               # column slowest, history fastest within it
+    stats = np.zeros((_lib.stat_cols(n),) + hshape)                  # column slowest, history fastest within it
     nst = np.zeros(hshape + (a.NT,), dtype=np.int32) if nodes else None
-    args = (C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0], _lib._p(a.obs, C.c_int32),
-            _lib._p(som, C.c_int32), D, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
-            _lib._p(nst, C.c_int32))
+    args = head + (D, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double), _lib._p(nst, C.c_int32))
     res = (np.moveaxis(stats, 0, -1), ll) + ((nst,) if nodes else ())
     if not maps:
         _lib.check(L.phm_sample_histories_models(*args, None, 0, None, None))
@@ -566,37 +516,19 @@ def ancestral_states_models(z, Qs, pid, sites=None, observe=None, site_of_model=
     if not marginal and not joint:
         raise ValueError("marginal and joint are both False: nothing to compute")
     L = _lib.load()
-    Qs = np.asarray(Qs, dtype=np.float64)
-    if Qs.ndim == 2:
-        Qs = Qs[None]
-    if Qs.ndim != 3 or Qs.shape[1] != Qs.shape[2]:
-        raise ValueError("Qs must be [K, n, n]")
-    K, n = Qs.shape[0], Qs.shape[1]
-    a = _expect_args(z, Qs[0], np.zeros(n), sites, observe, opt)
-    Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))                 # each matrix column-major, model slowest
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, K):
-        raise ValueError("pid must have n entries, shared or one row per model")
-    som = None
-    if site_of_model is not None:
-        som = np.ascontiguousarray(site_of_model, dtype=np.int32).reshape(-1)
-        if som.size != K:
-            raise ValueError("site_of_model must have one entry per model")
+    n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
     sel = None
     if nodes is not None:
         sel = np.ascontiguousarray(nodes, dtype=np.int32).reshape(-1)
         if sel.size == 0:
             raise ValueError("nodes must name at least one node (None: every node)")
     J = a.NT if sel is None else sel.size
-    shape = (K,) if som is not None else (K, a.S)
     ll = np.zeros(shape)
     post = np.zeros(shape + (J, n)) if marginal else None
     states = np.zeros(shape + (J,), dtype=np.int32) if joint else None
     jl = np.zeros(shape) if joint else None
     fn = L.phm_ancestral_models_wide if n > 8 else L.phm_ancestral_models
-    _lib.check(fn(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), pid.shape[0],
-                  _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), _lib._p(sel, C.c_int32),
-                  0 if sel is None else sel.size, C.byref(a.opt), _lib._p(ll, C.c_double),
+    _lib.check(fn(*head, _lib._p(sel, C.c_int32), 0 if sel is None else sel.size, C.byref(a.opt), _lib._p(ll, C.c_double),
                   _lib._p(post, C.c_double), _lib._p(states, C.c_int32), _lib._p(jl, C.c_double)))
     ids = np.arange(1, a.NT + 1, dtype=np.int32) if sel is None else sel.copy()
     return AncestralStates(ll, post, states, jl, ids)
@@ -613,10 +545,8 @@ def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, se
     points.  ``se=True`` adds ``fit.standard_errors``' keys: cov_log [p, p], se_log [p], ci [p, 2] and
     se_ok, from the observed information in log theta (one call of 2p models per problem)."""
     from . import fit as _fit
-    a = _expect_args(z, np.zeros((model.n, model.n)), np.zeros(model.n), sites, observe, dict(opt))
-    S = a.S
-    edge_len = np.asarray(z["edge.length"], dtype=np.float64)
-    rate0 = (a.NT - int(z["Nnode"])) / float(np.sum(edge_len))       # number of tips / tree length
+    a = _tips_tree(z, sites, observe, model.n, opt)
+    S, rate0 = a.S, _start_rate(z, a.T)
     if per_site:
         def batch(Qs, owner):
             return loglik_models(z, Qs, pid, sites=sites, observe=observe, site_of_model=owner, **opt)
@@ -664,10 +594,8 @@ def posterior_rates(z, model, pid, prior, iters, chains=4, sites=None, observe=N
         raise ValueError("posterior_rates needs an index model (ratemodel.er, sym, ard or index_model)")
     L = _lib.load()
     n, p = model.n, model.p
-    a = _expect_args(z, np.zeros((n, n)), np.zeros(n), sites, observe, dict(opt))
-    S = a.S
-    T = a.NT - int(z["Nnode"])
-    rate0 = T / float(np.sum(np.asarray(z["edge.length"], dtype=np.float64)))
+    a = _tips_tree(z, sites, observe, n, opt)
+    S, rate0 = a.S, _start_rate(z, a.T)
     theta_max = 100.0 * rate0 if theta_max is None else float(theta_max)
     per = int(chains)
     if per < 1:
@@ -693,16 +621,13 @@ def posterior_rates(z, model, pid, prior, iters, chains=4, sites=None, observe=N
     if pr.shape[1:] != (p, 2) or pr.shape[0] not in (1, Cn):
         raise ValueError("prior must be [p, 2] (shared) or [C, p, 2]")
     pr = np.ascontiguousarray(pr)
-    pid = np.ascontiguousarray(np.atleast_2d(np.asarray(pid, dtype=np.float64)))
-    if pid.shape[1] != n or pid.shape[0] not in (1, Cn):
-        raise ValueError("pid must have n entries, shared or one row per chain")
+    pid = _pid_rows(pid, n, Cn, per="chain")
     idx = np.ascontiguousarray(np.asarray(model.index, dtype=np.int32).T)     # column-major
     iters, thin = int(iters), int(thin)
     rows = max(1, -(-iters // max(thin, 1)))
-    cols = n + n * (n - 1)
     theta = np.zeros((rows, Cn, p))
     ll = np.zeros((rows, Cn))
-    st = np.zeros((rows, Cn, cols)) if stats else None
+    st = np.zeros((rows, Cn, _lib.stat_cols(n))) if stats else None
     rej = np.zeros((Cn, p), dtype=np.int32)
     status = np.zeros(Cn, dtype=np.int32)
     _lib.check(L.phm_gibbs_rates(C.byref(a.tree), n, _lib._p(idx, C.c_int32), p, Cn, _lib._p(th0, C.c_double),

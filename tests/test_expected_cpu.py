@@ -119,12 +119,8 @@ def _raw_call(z, Q, pid, observe=None, S=2, stats=True, loglik=True, tips=None, 
     Qf = np.asfortranarray(np.asarray(Q, dtype=np.float64))
     n = Qf.shape[0]
     pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    T = len(z["states"])
-    st = np.ascontiguousarray(np.tile(z["states"], (S, 1)) if tips is None else tips, dtype=np.int32)
-    tree = _lib.Tree(T, T - 1, 2 * T - 2, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), _lib._p(st.reshape(-1), C.c_int32),
-                     None, None, None)
+    pt = _lib.PlainTree(z, np.tile(z["states"], (S, 1)) if tips is None else tips)
+    tree = pt.c
     obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
     o = _lib.make_options(n_replicas=S, tips_per_replica=True, **opt)
     s = np.zeros((S, n * n)) if stats else None

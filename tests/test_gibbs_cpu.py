@@ -20,12 +20,8 @@ def _raw(z, model, C_=3, theta0=None, prior=None, n_prior=None, theta_max=50.0, 
     th0 = np.ascontiguousarray(np.full((C_, p), 0.5) if theta0 is None else theta0, dtype=np.float64)
     pr = np.ascontiguousarray(np.ones((1, p, 2)) if prior is None else prior, dtype=np.float64)
     pid = np.ascontiguousarray(np.full(n, 1.0 / n) if pid is None else pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    T = len(z["states"])
-    E = 2 * T - 2
-    st = np.ascontiguousarray(np.tile(z["states"], (S, 1)), dtype=np.int32)
-    t = _lib.Tree(T, T - 1, E, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), _lib._p(st.reshape(-1), C.c_int32), None, None, None)
+    pt = _lib.PlainTree(z, np.tile(z["states"], (S, 1)))
+    t = pt.c
     obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
     so = None if soc is None else np.ascontiguousarray(soc, dtype=np.int32)
     o = _lib.make_options(n_replicas=S, tips_per_replica=True)

@@ -166,7 +166,7 @@ def test_sizing_and_filling():
     E, NT = edge.shape[0], edge.shape[0] + 1
     H = K * D
     L = _lib.load()
-    a = api._expect_args(z, Qs[0], np.zeros(n), None, None, dict(seed=19))
+    pt, o = _lib.PlainTree(z, z["states"]), _lib.make_options(seed=19)
     Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))
     pid = np.full((1, n), 0.25)
 
@@ -174,8 +174,8 @@ def test_sizing_and_filling():
         stats = np.zeros((n * n, H))
         ll = np.zeros(K)
         nodes = np.zeros((H, NT), dtype=np.int32)
-        st = L.phm_sample_histories_models(C.byref(a.tree), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), 1, None, None, D,
-                                           C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
+        st = L.phm_sample_histories_models(C.byref(pt.c), n, K, _lib._p(Qf, C.c_double), _lib._p(pid, C.c_double), 1, None, None, D,
+                                           C.byref(o), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double),
                                            _lib._p(nodes, C.c_int32), _lib._p(off, C.c_int64), cap, _lib._p(dwell, C.c_double),
                                            _lib._p(state, C.c_int32))
         return st, (stats, ll, nodes)

@@ -168,11 +168,8 @@ def _raw(z, Qs, pid, R, seed, off=None, cap=0, dwell=None, state=None):
     K, n = Qs.shape[0], Qs.shape[1]
     Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))
     pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    E = z["edge"].shape[0]
-    T = E // 2 + 1
-    t = _lib.Tree(T, T - 1, E, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
+    pt = _lib.PlainTree(z)
+    t, T = pt.c, pt.T
     o = _lib.make_options(seed=seed)
     H = K * R
     tips = np.zeros((H, T), dtype=np.int32)

@@ -134,12 +134,10 @@ def _sim_call(off, cap, dwell, state, R=4, mapping="auto"):
     Q = np.asfortranarray(synth.make2sQ(0.3, 0.2, 0.4, 0.3, 2.0))
     pid = np.full(4, 0.25)
     edge, lens = synth.random_tree(8, 1.0, 3)
-    fe = np.asfortranarray(edge.astype(np.int32)).reshape(-1, order="F").copy()
-    lens = np.ascontiguousarray(lens)
-    tree = _lib.Tree(8, 7, 14, _lib._p(fe, C.c_int32), _lib._p(lens, C.c_double), None, None, None, None)
+    pt = _lib.PlainTree({"edge": edge, "edge.length": lens, "Nnode": 7})
     o = _lib.make_options(n_replicas=R, mapping=mapping)
     tips, stats = np.zeros((R, 8), dtype=np.int32), np.zeros((R, 21), order="F")
-    return L.phm_simulate_histories_maps(C.byref(tree), 4, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), None, C.byref(o),
+    return L.phm_simulate_histories_maps(C.byref(pt.c), 4, _lib._p(Q, C.c_double), _lib._p(pid, C.c_double), None, C.byref(o),
                                          _lib._p(tips, C.c_int32), None, _lib._p(stats, C.c_double), _lib._p(off, C.c_int64),
                                          int(cap), _lib._p(dwell, C.c_double), _lib._p(state, C.c_int32))
 

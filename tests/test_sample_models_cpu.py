@@ -180,12 +180,8 @@ def _raw(z, Qs, pid, draws=2, n_pid=None, S=2, observe=None, som=None, stats=Tru
     K, n = Qs.shape[0], Qs.shape[1]
     Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))
     pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    T = len(z["states"])
-    E = 2 * T - 2
-    st = np.ascontiguousarray(np.tile(z["states"], (S, 1)), dtype=np.int32)
-    t = _lib.Tree(T, T - 1, E, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), _lib._p(st.reshape(-1), C.c_int32), None, None, None)
+    pt = _lib.PlainTree(z, np.tile(z["states"], (S, 1)))
+    t = pt.c
     obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
     so = None if som is None else np.ascontiguousarray(som, dtype=np.int32)
     o = _lib.make_options(n_replicas=S, tips_per_replica=True)

@@ -73,10 +73,8 @@ def _raw_call(z, Q, pid, observe=None, R=4, tips=True, stats=True, **opt):
     Qf = np.asfortranarray(np.asarray(Q, dtype=np.float64))
     n = Qf.shape[0]
     pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    T = len(z["states"])
-    tree = _lib.Tree(T, T - 1, 2 * T - 2, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
+    pt = _lib.PlainTree(z)
+    tree, T = pt.c, pt.T
     obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
     o = _lib.make_options(n_replicas=R, **opt)
     t = np.zeros((R, T), dtype=np.int32) if tips else None

@@ -15,11 +15,8 @@ def _raw(z, Qs, pid, R=2, n_pid=None, observe=None, tips=True, stats=True, map_o
     K, n = Qs.shape[0], Qs.shape[1]
     Qf = np.ascontiguousarray(Qs.transpose(0, 2, 1))
     pid = np.ascontiguousarray(pid, dtype=np.float64)
-    edge = np.asfortranarray(np.asarray(z["edge"], dtype=np.int32)).reshape(-1, order="F").copy()
-    el = np.ascontiguousarray(z["edge.length"], dtype=np.float64)
-    T = len(z["states"])
-    E = 2 * T - 2
-    t = _lib.Tree(T, T - 1, E, _lib._p(edge, C.c_int32), _lib._p(el, C.c_double), None, None, None, None)
+    pt = _lib.PlainTree(z)
+    t, T = pt.c, pt.T
     obs = None if observe is None else np.ascontiguousarray(observe, dtype=np.int32)
     o = _lib.make_options(**opt)
     H = K * max(R, 1) if K * max(R, 1) < 4096 else 1                  # a refused call writes nothing
