@@ -9,6 +9,8 @@
 // Summation orders follow the arithmetic spec, so results match the CPU oracle bit for bit.
 #include "phm_exp.h"
 
+#include "phm_history.h"
+
 namespace phm {
 
 // ------------------------------------------------------------------------------------------------
@@ -662,6 +664,8 @@ __global__ __launch_bounds__(EXP_BLOCK) void exp_tiles_node_kernel(ExpTilesParam
 //    point, n(n-1) counters) and reach the per-sample accumulators once per group; NS = 0 (runtime n up to 64): one atomic per segment.
 constexpr int EXP_KL = 12;
 
+//  * This kernel keeps its own copy of the statistics lanes (phm_history.h) and of the map-row sink (phm_maps.h): on the shared
+//    pieces its sizing launch measured 1.3 % slower (docs/MEASUREMENTS.md, history producers).
 //  * MODE (phm_maps.h): MAPS_OFF = the plain sampler; MAPS_COUNT also stores every (branch, sample)'s segment count into
 //    p.maps.seg_cnt [edge][tile*64]; MAPS_WRITE also stores every segment (dwell, 1-based state) at the lane's cursor in row
 //    it * n_edge + b of p.maps.  Same draws and statistics in all three.
@@ -829,19 +833,10 @@ __global__ void exp_tiles_finish_kernel(ExpTilesParams p) {
   if (gid >= (int64_t)cols * p.N) return;
   const int c = (int)(gid / p.N), it = (int)(gid % p.N);
   const size_t npad = (size_t)p.n_tiles * 64;
-  p.out[(size_t)c * p.N + it] = c < n ? (double)(long long)p.dwfx[(size_t)c * npad + it] * p.fx_inv
-                                      : (double)p.cnt[(size_t)(c - n) * npad + it];
+  p.out[(size_t)c * p.N + it] = stat_cell_value(p.dwfx, p.cnt, n, c, npad, (size_t)it, p.fx_inv);
 }
 
 }  // namespace
-
-template <int MODE>
-void launch_exp_tiles_branch(const ExpTilesParams& p, int branch_blocks, int group, hipStream_t stream) {
-  if (p.n_states == 2) hipLaunchKernelGGL((exp_tiles_branch_kernel<2, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else if (p.n_states == 3) hipLaunchKernelGGL((exp_tiles_branch_kernel<3, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else if (p.n_states == 4) hipLaunchKernelGGL((exp_tiles_branch_kernel<4, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-  else hipLaunchKernelGGL((exp_tiles_branch_kernel<0, MODE>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream, p, group);
-}
 
 hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>& level_off, int branch_blocks, hipStream_t stream,
                             int maps_mode) {
@@ -853,9 +848,10 @@ hipError_t launch_exp_tiles(const ExpTilesParams& p, const std::vector<int32_t>&
   }
   // branches per wave-item: as many as still leave every SIMD a few waves (an R call with N = 1 000 samples has 16 tiles)
   const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.n_edge * p.n_tiles / 8192));
-  if (maps_mode == MAPS_COUNT) launch_exp_tiles_branch<MAPS_COUNT>(p, branch_blocks, group, stream);
-  else if (maps_mode == MAPS_WRITE) launch_exp_tiles_branch<MAPS_WRITE>(p, branch_blocks, group, stream);
-  else launch_exp_tiles_branch<MAPS_OFF>(p, branch_blocks, group, stream);
+  with_producer_form(maps_mode, p.n_states, [&](auto mode, auto ns) {
+    hipLaunchKernelGGL((exp_tiles_branch_kernel<decltype(ns)::value, decltype(mode)::value>), dim3(branch_blocks), dim3(EXP_BLOCK), 0, stream,
+                       p, group);
+  });
   const int64_t cells = (int64_t)(p.n_states + p.n_states * (p.n_states - 1)) * p.N;
   hipLaunchKernelGGL(exp_tiles_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
   return hipGetLastError();

@@ -30,38 +30,6 @@ __device__ __forceinline__ void replay_branch(int m, int ps, int cs, const doubl
   emit(cur_len, cur_s);
 }
 
-// Count: the row's segments, stored (a replayed sweep overwrites).  Write: (dwell, state + 1) from the row's offset while below
-// its end; a row whose count differs reports itself (lowest row of the launch wins).
-struct RowSink {
-  int64_t pos = 0, end = 0;
-  int cnt = 0;
-};
-
-template <int MODE>
-__device__ __forceinline__ void sink_begin(const McmcMapsLaunch& mp, int64_t k, RowSink& r) {
-  r.cnt = 0;
-  if (MODE == MAPS_WRITE) { r.pos = mp.dev.off[k] - mp.dev.base; r.end = mp.dev.off[k + 1] - mp.dev.base; }
-}
-
-template <int MODE>
-__device__ __forceinline__ void sink_emit(const McmcMapsLaunch& mp, RowSink& r, double len, int s) {
-  if (MODE == MAPS_WRITE) {
-    if (r.pos < r.end) { mp.dev.dwell[r.pos] = len; mp.dev.state[r.pos] = s + 1; }
-    ++r.pos;
-  } else {
-    ++r.cnt;
-  }
-}
-
-template <int MODE>
-__device__ __forceinline__ void sink_end(const McmcMapsLaunch& mp, int E, int b, int r_local, int pad, int64_t k, const RowSink& r) {
-  if (MODE == MAPS_WRITE) {
-    if (r.pos != r.end) atomicMin(mp.dev.bad_row, (unsigned long long)k);
-  } else {
-    mp.dev.seg_cnt[((size_t)mp.j * E + b) * pad + r_local] = (uint16_t)r.cnt;
-  }
-}
-
 // n <= 4: the tables of phm_tiles.hip (TileParams: B2 by value, col[k][end][NS])
 template <int NS, int MODE>
 __global__ __launch_bounds__(MM_BLOCK) void mcmc_maps_tiles_kernel(TileParams<NS> p, McmcMapsLaunch mp, int it) {
@@ -87,8 +55,8 @@ __global__ __launch_bounds__(MM_BLOCK) void mcmc_maps_tiles_kernel(TileParams<NS
     Stream su;
     su.open(ENT_BSTATE | (uint32_t)b, (uint32_t)it, rep, p.seed_lo, p.seed_hi);
     const int64_t k = ((int64_t)r * mp.J + mp.j) * E + b;
-    RowSink rs;
-    sink_begin<MODE>(mp, k, rs);
+    MapRow<MODE> mr;
+    mr.begin(mp.dev, k);
     uint32_t err = 0;                            // the branch kernel reports the sweep's errors
     auto draw = [&](int i, int sprev, uint32_t word) -> int {
       const int kk = min(m - i - 1, p.klong - 1);
@@ -98,8 +66,8 @@ __global__ __launch_bounds__(MM_BLOCK) void mcmc_maps_tiles_kernel(TileParams<NS
       for (int c = 0; c < NS; ++c) pr[c] = s_B2[sprev * NS + c] * beta[c];
       return sample_cat<NS>(pr, u01(word), err);
     };
-    replay_branch(m, ps, cs, in, su, draw, [&](double len, int s) { sink_emit<MODE>(mp, rs, len, s); });
-    sink_end<MODE>(mp, E, b, r, p.n_rep_pad, k, rs);
+    replay_branch(m, ps, cs, in, su, draw, [&](double len, int s) { mr.emit(len, s); });
+    mr.end(((size_t)mp.j * E + b) * p.n_rep_pad + r);
   }
 }
 
@@ -126,8 +94,8 @@ __global__ __launch_bounds__(MM_BLOCK) void mcmc_maps_wtiles_kernel(WtParams p, 
     Stream su;
     su.open(ENT_BSTATE | (uint32_t)b, (uint32_t)it, rep, p.seed_lo, p.seed_hi);
     const int64_t k = ((int64_t)r * mp.J + mp.j) * E + b;
-    RowSink rs;
-    sink_begin<MODE>(mp, k, rs);
+    MapRow<MODE> mr;
+    mr.begin(mp.dev, k);
     auto draw = [&](int i, int sprev, uint32_t word) -> int {
       const int kk = min(m - i - 1, p.klong - 1);
       const double* __restrict__ blk = p.blkL + (((size_t)kk * n + sprev) * n + cs) * p.ldb;
@@ -150,8 +118,8 @@ __global__ __launch_bounds__(MM_BLOCK) void mcmc_maps_wtiles_kernel(WtParams p, 
       }
       return idx;
     };
-    replay_branch(m, ps, cs, in, su, draw, [&](double len, int s) { sink_emit<MODE>(mp, rs, len, s); });
-    sink_end<MODE>(mp, E, b, r, p.n_rep_pad, k, rs);
+    replay_branch(m, ps, cs, in, su, draw, [&](double len, int s) { mr.emit(len, s); });
+    mr.end(((size_t)mp.j * E + b) * p.n_rep_pad + r);
   }
 }
 
@@ -170,9 +138,10 @@ __global__ __launch_bounds__(256) void mcmc_maps_transpose_kernel(const uint16_t
 template <int NS>
 hipError_t launch_mcmc_maps_tiles(const TileParams<NS>& p, const McmcMapsLaunch& m, int it, hipStream_t stream) {
   const dim3 g((unsigned)(((int64_t)p.n_groups * p.n_tiles + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64)));
-  if (m.mode == MAPS_COUNT) hipLaunchKernelGGL((mcmc_maps_tiles_kernel<NS, MAPS_COUNT>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
-  else if (m.mode == MAPS_WRITE) hipLaunchKernelGGL((mcmc_maps_tiles_kernel<NS, MAPS_WRITE>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
-  else return hipErrorInvalidValue;
+  if (m.mode != MAPS_COUNT && m.mode != MAPS_WRITE) return hipErrorInvalidValue;
+  with_map_mode(m.mode, [&](auto mode) {
+    if constexpr (mode != MAPS_OFF) hipLaunchKernelGGL((mcmc_maps_tiles_kernel<NS, mode>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
+  });
   return hipGetLastError();
 }
 
@@ -182,9 +151,10 @@ template hipError_t launch_mcmc_maps_tiles<4>(const TileParams<4>&, const McmcMa
 
 hipError_t launch_mcmc_maps_wtiles(const WtParams& p, const McmcMapsLaunch& m, int it, hipStream_t stream) {
   const dim3 g((unsigned)(((int64_t)p.n_groups * p.n_tiles + MM_BLOCK / 64 - 1) / (MM_BLOCK / 64)));
-  if (m.mode == MAPS_COUNT) hipLaunchKernelGGL((mcmc_maps_wtiles_kernel<MAPS_COUNT>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
-  else if (m.mode == MAPS_WRITE) hipLaunchKernelGGL((mcmc_maps_wtiles_kernel<MAPS_WRITE>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
-  else return hipErrorInvalidValue;
+  if (m.mode != MAPS_COUNT && m.mode != MAPS_WRITE) return hipErrorInvalidValue;
+  with_map_mode(m.mode, [&](auto mode) {
+    if constexpr (mode != MAPS_OFF) hipLaunchKernelGGL((mcmc_maps_wtiles_kernel<mode>), g, dim3(MM_BLOCK), 0, stream, p, m, it);
+  });
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "phm_device.h"
+#include "phm_history.h"
 
 namespace phm {
 
@@ -188,7 +189,6 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
   const int n_groups = (p.n_edge + group - 1) / group;
   const int64_t items = (int64_t)n_groups * p.n_tiles;
   const size_t npad = (size_t)p.n_tiles * 64;
-  constexpr int NA = NS > 0 ? NS : 1, NC = NS > 0 ? NS * (NS - 1) : 1;
   uint32_t err = 0;
   for (int64_t item = wslot; item < items; item += (int64_t)gridDim.x * (SM_BLOCK / 64)) {
     const int tile = (int)(item % p.n_tiles);
@@ -203,26 +203,9 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
     const double* __restrict__ Bk = p.B + l.k;
     const double* __restrict__ bt = p.beta + l.k;
     const uint32_t rep = l.rep;
-    unsigned long long acc_dw[NA];
-    uint32_t acc_ct[NC];
-#pragma unroll
-    for (int c = 0; c < NA; ++c) acc_dw[c] = 0ull;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc_ct[c] = 0u;
-    auto stat_add = [&](int col, double v) {           // dwell: fixed point, exact in any order
-      const unsigned long long fx = (unsigned long long)__double2ll_rn(v * p.fx_scale);
-      if (NS > 0) {
-#pragma unroll
-        for (int c = 0; c < NA; ++c) acc_dw[c] += (col == c) ? fx : 0ull;
-      } else if (valid) atomicAdd(p.dwfx + (size_t)col * npad + it, fx);
-    };
-    auto count = [&](int from, int to) {
-      const int col = from * (n - 1) + (to > from ? to - 1 : to);
-      if (NS > 0) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc_ct[c] += (col == c) ? 1u : 0u;
-      } else if (valid) atomicAdd(p.cnt + (size_t)col * npad + it, 1u);
-    };
+    StatLanes<NS, NS * (NS - 1)> st;
+    st.begin(p.dwfx, p.cnt, npad, it, p.fx_scale, valid);
+    auto count = [&](int from, int to) { st.count(from * (n - 1) + (to > from ? to - 1 : to)); };
     for (int qi = q0; qi < q1; ++qi) {
       const DownStep ds = p.down[qi];
       const int b = ds.edge;
@@ -230,18 +213,9 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
       const int a = nst[(q.n_tips + ds.parent) * 64 + lane];
       const int e = nst[crow * 64 + lane];
       const double tb = q.t[b];
-      const int64_t mrow = (tl.row0 + lane) * p.n_edge + b;
-      int64_t cur = 0, end = 0;
-      if constexpr (MODE == MAPS_WRITE) {
-        if (valid) { cur = p.maps.off[mrow] - p.maps.base; end = p.maps.off[mrow + 1] - p.maps.base; }
-      }
-      auto segment = [&](int col, double v) {
-        stat_add(col, v);
-        if constexpr (MODE == MAPS_WRITE) {
-          if (cur < end) { p.maps.dwell[cur] = v; p.maps.state[cur] = col + 1; }
-        }
-        if constexpr (MODE != MAPS_OFF) ++cur;
-      };
+      MapRow<MODE> mr;                                             // a lane without a live history: an empty row, no count stored
+      mr.begin(p.maps, (tl.row0 + lane) * p.n_edge + b, valid);
+      auto segment = [&](int col, double v) { st.dwell(col, v); mr.emit(v, col); };
       const double x = (!PACKED || valid) ? mu * tb : 0.0;         // packed: a lane without a live chain walks no series
       int N = 0;
       if (x > 0.0) {
@@ -306,19 +280,9 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int gro
       } else {
         segment(a, tb);                                              // mu = 0 or t = 0: the parent's state for the whole branch
       }
-      if constexpr (MODE == MAPS_COUNT) {
-        if (valid) p.maps.seg_cnt[(size_t)b * p.map_pad + (size_t)(tl.row0 + lane)] = (uint16_t)cur;
-      }
-      if constexpr (MODE == MAPS_WRITE) {
-        if (valid && cur != end) atomicMin(p.maps.bad_row, (unsigned long long)mrow);
-      }
+      if (valid) mr.end((size_t)b * p.map_pad + (size_t)(tl.row0 + lane));
     }
-    if (NS > 0 && valid) {
-#pragma unroll
-      for (int c = 0; c < NA; ++c) if (acc_dw[c]) atomicAdd(p.dwfx + (size_t)c * npad + it, acc_dw[c]);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) if (acc_ct[c]) atomicAdd(p.cnt + (size_t)c * npad + it, acc_ct[c]);
-    }
+    st.flush();
   }
   if (err) atomicOr(p.err, err);
 }
@@ -331,7 +295,7 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(SmParams p) {
   if (gid < cols * npad) {
     const int c = (int)(gid / npad);
     const int64_t it = gid % npad;
-    p.out[gid] = c < n ? (double)(long long)p.dwfx[(size_t)c * npad + it] * p.fx_inv : (double)p.cnt[(size_t)(c - n) * npad + it];
+    p.out[gid] = stat_cell_value(p.dwfx, p.cnt, n, c, (size_t)npad, (size_t)it, p.fx_inv);
     if (p.packed) {                                                  // the next iteration accumulates from zero
       if (c < n) p.dwfx[(size_t)c * npad + it] = 0ull;
       else p.cnt[(size_t)(c - n) * npad + it] = 0u;
@@ -347,16 +311,6 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(SmParams p) {
       const int row = (int)(cell % NT);
       p.nodes[cell] = (int32_t)p.nstate[((size_t)(it >> 6) * NT + row) * 64 + (it & 63)] + 1;
     }
-  }
-}
-
-template <int MODE, bool PACKED = false>
-void launch_branch(const SmParams& p, int blocks, int group, hipStream_t stream) {
-  switch (p.ll.n) {
-    case 2: hipLaunchKernelGGL((sm_branch_kernel<2, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    case 3: hipLaunchKernelGGL((sm_branch_kernel<3, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    case 4: hipLaunchKernelGGL((sm_branch_kernel<4, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
-    default: hipLaunchKernelGGL((sm_branch_kernel<0, MODE, PACKED>), dim3(blocks), dim3(SM_BLOCK), 0, stream, p, group); break;
   }
 }
 
@@ -385,10 +339,11 @@ hipError_t launch_sm_sample(const SmParams& p, const std::vector<int32_t>& level
   }
   // branches per wave-item: as many as still leave every SIMD a few waves
   const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.n_edge * p.n_tiles / 8192));
-  if (p.packed) launch_branch<MAPS_OFF, true>(p, branch_blocks, group, stream);
-  else if (maps_mode == MAPS_COUNT) launch_branch<MAPS_COUNT>(p, branch_blocks, group, stream);
-  else if (maps_mode == MAPS_WRITE) launch_branch<MAPS_WRITE>(p, branch_blocks, group, stream);
-  else launch_branch<MAPS_OFF>(p, branch_blocks, group, stream);
+  with_producer_form(maps_mode, p.ll.n, [&](auto mode, auto ns) {      // the packed form has no maps (checked above)
+    constexpr int NS = decltype(ns)::value, MODE = decltype(mode)::value;
+    if (p.packed) hipLaunchKernelGGL((sm_branch_kernel<NS, MAPS_OFF, true>), dim3(branch_blocks), dim3(SM_BLOCK), 0, stream, p, group);
+    else hipLaunchKernelGGL((sm_branch_kernel<NS, MODE, false>), dim3(branch_blocks), dim3(SM_BLOCK), 0, stream, p, group);
+  });
   const int n = p.ll.n;
   const int64_t cells = (int64_t)(n + n * (n - 1)) * p.n_tiles * 64;
   hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);

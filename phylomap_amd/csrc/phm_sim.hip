@@ -8,24 +8,11 @@
 // Q's jump weights (diagonal 0), their row totals and 1/(-q_ss) are staged in LDS once per workgroup (32 KB at 64 states).
 // Accumulators: n <= 4 in registers (selects, no dynamic register indexing); 5..64 states in the [col][replica] statistics
 // buffer itself -- a replica belongs to one lane, so plain read-modify-write, no atomics.
-#include "phm_sim.h"
+#include "phm_sim_walk.h"
 
 namespace phm {
 
 namespace {
-
-// first j with u * total <= w_0 + .. + w_j, `total` summed left to right beforehand
-template <int NS>
-__device__ __forceinline__ int sim_categorical(const double* __restrict__ w, double total, int n_rt, double u, uint32_t& err) {
-  const int n = NS > 0 ? NS : n_rt;
-  if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
-  const double thr = u * total;
-  double cum = w[0];
-  int idx = (thr <= cum) ? 0 : 1;
-#pragma unroll
-  for (int j = 1; j < n - 1; ++j) { cum += w[j]; idx += (thr <= cum) ? 0 : 1; }
-  return idx;
-}
 
 // MODE (phm_maps.h): MAPS_OFF = the plain simulation; MAPS_COUNT also stores every branch's segment count; MAPS_WRITE also
 // stores every segment (dwell, 1-based true state) at the lane's cursor in its row of p.maps.  The draws are the same in all three.
@@ -63,6 +50,7 @@ __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
 #pragma unroll
     for (int j = 0; j < AN; ++j) cnt[i][j] = 0u;
   }
+  const SimModel model = {s_q, s_tot, s_inv, 1, 0, n};              // the workgroup's LDS copy
   auto add_dwell = [&](int s, double x) {
     if constexpr (NS > 0) {
 #pragma unroll
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
   {
     double total = s_pid[0];
     for (int j = 1; j < n; ++j) total += s_pid[j];
-    root_state = sim_categorical<NS>(s_pid, total, n, stream_u(p.seed_lo, p.seed_hi, rep, SIM_ITER, ENT_NODE | root_id, 0), err);
+    root_state = sim_categorical<NS>(s_pid, 1, total, n, stream_u(p.seed_lo, p.seed_hi, rep, SIM_ITER, ENT_NODE | root_id, 0), err);
   }
   p.nstate[(size_t)(root_id - 1) * pad + r] = (uint8_t)root_state;
 
@@ -86,46 +74,28 @@ __global__ __launch_bounds__(SIM_BLOCK) void sim_kernel(SimParams p) {
     const DownStep d = p.down[k];                                  // wave-uniform
     const size_t parent_row = (size_t)(T + d.parent), child_row = (size_t)(d.child >= 0 ? T + d.child : ~d.child);
     const double t = p.edge_length[d.edge];
-    int s = p.nstate[parent_row * pad + r];
-    // maps: segments of this branch so far (count) / the write cursor and the end of row r * E + edge (write)
-    const size_t mrow = (size_t)r * p.n_edge + d.edge;
-    int64_t cur = 0, end = 0;
-    if constexpr (MODE == MAPS_WRITE) { cur = p.maps.off[mrow] - p.maps.base; end = p.maps.off[mrow + 1] - p.maps.base; }
-    auto segment = [&](int st, double x) {
-      add_dwell(st, x);
-      if constexpr (MODE == MAPS_WRITE) {
-        if (cur < end) { p.maps.dwell[cur] = x; p.maps.state[cur] = st + 1; }
-      }
-      if constexpr (MODE != MAPS_OFF) ++cur;
-    };
+    const int s0 = p.nstate[parent_row * pad + r];
+    const size_t mrow = (size_t)r * p.n_edge + d.edge;            // maps: row r * E + edge
+    MapRow<MODE> mr;
+    mr.begin(p.maps, (int64_t)mrow);
     Stream rs;
     rs.open(ENT_BSTATE | (uint32_t)d.edge, SIM_ITER, rep, p.seed_lo, p.seed_hi);
-    double pos = 0.0;
-    for (uint32_t j = 0;; ++j) {
-      const double ir = s_inv[s];
-      if (ir == 0.0) { segment(s, t - pos); break; }             // absorbing: the rest of the branch, no draw
-      const double gap = ir * neglog_u32(rs.draw_word(2u * j), s_ltab);
-      const double dab = pos + gap;
-      if (!(dab < t)) { segment(s, gap - (dab - t)); break; }    // seg_len - (dab - branchlength)
-      segment(s, gap);
-      if (j == (uint32_t)SIM_MAX_JUMPS) { err |= DERR_CAPACITY; atomicMin(&p.err[1], (uint32_t)d.edge); break; }
-      const int nx = sim_categorical<NS>(&s_q[s * n], s_tot[s], n, rs.draw(2u * j + 1u), err);
-      if constexpr (NS > 0) {
+    const int s = sim_walk_branch<NS>(
+        s0, t, rs, s_ltab, model,
+        [&](int st, double x) { add_dwell(st, x); mr.emit(x, st); },
+        [&](int from, int to) {
+          if constexpr (NS > 0) {
 #pragma unroll
-        for (int a = 0; a < NS; ++a)
+            for (int a = 0; a < NS; ++a)
 #pragma unroll
-          for (int b = 0; b < NS; ++b) cnt[a][b] += (s == a && nx == b) ? 1u : 0u;
-      } else {
-        col[(size_t)(n + s * n + nx) * pad] += 1.0;
-      }
-      s = nx;
-      pos = dab;
-    }
+              for (int b = 0; b < NS; ++b) cnt[a][b] += (from == a && to == b) ? 1u : 0u;
+          } else {
+            col[(size_t)(n + from * n + to) * pad] += 1.0;
+          }
+        },
+        [&]() { atomicMin(&p.err[1], (uint32_t)d.edge); }, err);
     p.nstate[child_row * pad + r] = (uint8_t)s;
-    if constexpr (MODE == MAPS_COUNT) p.maps.seg_cnt[(size_t)d.edge * pad + r] = (uint16_t)cur;   // one 128-byte row per wave
-    if constexpr (MODE == MAPS_WRITE) {
-      if (cur != end) atomicMin(p.maps.bad_row, (unsigned long long)mrow);
-    }
+    mr.end((size_t)d.edge * pad + r);                              // one 128-byte row of counts per wave
   }
 
   if constexpr (NS > 0) {
@@ -161,21 +131,11 @@ __global__ __launch_bounds__(256) void sim_transpose_kernel(const uint8_t* __res
 
 }  // namespace
 
-template <int MODE>
-void launch_simulate_mode(const SimParams& p, hipStream_t stream) {
-  const dim3 grid((p.n_rep + SIM_BLOCK - 1) / SIM_BLOCK);
-  switch (p.n_states) {
-    case 2: hipLaunchKernelGGL((sim_kernel<2, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    case 3: hipLaunchKernelGGL((sim_kernel<3, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    case 4: hipLaunchKernelGGL((sim_kernel<4, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-    default: hipLaunchKernelGGL((sim_kernel<0, MODE>), grid, dim3(SIM_BLOCK), 0, stream, p); break;
-  }
-}
-
 hipError_t launch_simulate(const SimParams& p, hipStream_t stream, int maps_mode) {
-  if (maps_mode == MAPS_COUNT) launch_simulate_mode<MAPS_COUNT>(p, stream);
-  else if (maps_mode == MAPS_WRITE) launch_simulate_mode<MAPS_WRITE>(p, stream);
-  else launch_simulate_mode<MAPS_OFF>(p, stream);
+  const dim3 grid((p.n_rep + SIM_BLOCK - 1) / SIM_BLOCK);
+  with_producer_form(maps_mode, p.n_states, [&](auto mode, auto ns) {
+    hipLaunchKernelGGL((sim_kernel<decltype(ns)::value, decltype(mode)::value>), grid, dim3(SIM_BLOCK), 0, stream, p);
+  });
   return hipGetLastError();
 }
 

@@ -1,12 +1,13 @@
 // phm_sim_models_api.cpp -- C-ABI of the forward simulation under many rate matrices (phm_simulate_histories_models, DESIGN.md
 // section 22): K models (Q_k, pid_k), R histories each, history h = k R + r being what phm_simulate_histories returns for global
-// replica replica_offset + h under (Q_k, pid_k).  Validation and the model tables on the host with phm_sim_api.cpp's arithmetic
-// (check_generator's row-major Q, IEEE 1 / (-q_ii), totals summed left to right); per device and per chunk of histories the model
+// replica replica_offset + h under (Q_k, pid_k).  Validation and the model tables on the host by the front end it shares with
+// phm_sim_api.cpp (phm_sim_host.h: check_generator's row-major Q, IEEE 1 / (-q_ii), totals summed left to right); per device and per chunk of histories the model
 // tables of the chunk (model-fastest), then the root, depth-level and finish launches of phm_simm.hip and phm_sim.hip's
 // transposing epilogue.  A shard of models is a contiguous range of histories, so section 14's per-shard map buffers
 // (phm_maps_host.h) serve unchanged.
 #include "phm_internal.h"
 #include "phm_maps_host.h"
+#include "phm_sim_host.h"
 #include "phm_simm.h"
 
 namespace {
@@ -29,9 +30,8 @@ struct SimmInput {
 int32_t simm_validate(const phm_tree* x, int32_t n, int32_t K, const double* Q, const double* pid, int32_t n_pid,
                       const int32_t* observe, int32_t replicates, const phm_options& o, const int32_t* tips, const double* stats,
                       SimmInput& in) {
-  if (!x || !Q || !pid || !tips || !stats)
-    return fail(PHM_ERR_BAD_INPUT, SMM_FN + "NULL argument (only observe, opt, nodes and the map arrays may be NULL)");
-  if (n < 2 || n > phm::SIM_MAX_STATES) return fail(PHM_ERR_BAD_INPUT, SMM_FN + "n_states must be in 2..64");
+  int32_t st = phm_sim::check_head(SMM_FN, "only observe, opt, nodes and the map arrays may be NULL", x, n, Q, pid, tips, stats);
+  if (st) return st;
   if (K < 1) return fail(PHM_ERR_BAD_INPUT, SMM_FN + "n_models must be >= 1");
   if (n_pid != 1 && n_pid != K) return fail(PHM_ERR_BAD_INPUT, SMM_FN + "n_pid must be 1 (shared) or n_models");
   if (replicates < 1) return fail(PHM_ERR_BAD_INPUT, SMM_FN + "replicates must be >= 1");
@@ -40,48 +40,23 @@ int32_t simm_validate(const phm_tree* x, int32_t n, int32_t K, const double* Q, 
   if (o.replica_offset < 0 || (int64_t)o.replica_offset + in.H > ((int64_t)1 << 32))
     return fail(PHM_ERR_BAD_INPUT, SMM_FN + "replica_offset + n_models * replicates = " + std::to_string((int64_t)o.replica_offset + in.H) +
                                        " does not fit in the 32-bit replica word");
-  if (!x->edge || !x->edge_length) return fail(PHM_ERR_BAD_INPUT, SMM_FN + "x$edge and x$edge.length are required");
-  std::string serr;
-  if (!phm::build_schedule(x->n_tips, x->n_node, x->n_edge, x->edge, in.sched, serr)) return fail(PHM_ERR_BAD_INPUT, "tree: " + serr);
-  in.n = n; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge; in.n_pid = n_pid; in.opt = o;
-  int32_t st = check_edge_lengths(x);
+  st = phm_sim::check_tree(SMM_FN, x, in.sched, in.edge_length);
   if (st) return st;
-  in.edge_length.assign(x->edge_length, x->edge_length + in.E);
+  in.n = n; in.T = x->n_tips; in.Nn = x->n_node; in.E = x->n_edge; in.n_pid = n_pid; in.opt = o;
   double tree_len = 0.0;
   for (int b = 0; b < in.E; ++b) tree_len += in.edge_length[b];
   (void)std::frexp(std::max(tree_len, 1.0), &in.fx_exp);
   const size_t nn = (size_t)n * n;
   in.qoff.resize((size_t)K * nn); in.qtot.resize((size_t)K * n); in.inv_rate.resize((size_t)K * n);
-  std::vector<double> qr;
   for (int k = 0; k < K; ++k) {
-    const std::string who = "model " + std::to_string(k) + ": ";
-    st = check_generator(Q + (size_t)k * nn, n, qr);
-    if (st) return fail(st, who + g_phm_err);
-    for (int i = 0; i < n; ++i) {
-      double* row = &qr[(size_t)i * n];
-      const double qii = row[i];
-      row[i] = 0.0;
-      double off = row[0];                                           // what sim_kernel sums: left to right from the first entry
-      for (int j = 1; j < n; ++j) off += row[j];
-      if (qii < 0.0 && !(off > 0.0)) return fail(PHM_ERR_BAD_INPUT, who + "Q: row " + std::to_string(i + 1) + " leaves its state but has no target");
-      in.qtot[(size_t)k * n + i] = off;
-      in.inv_rate[(size_t)k * n + i] = qii < 0.0 ? 1.0 / (-qii) : 0.0;   // 0: absorbing (q_ss = 0)
-    }
-    std::copy(qr.begin(), qr.end(), in.qoff.begin() + (size_t)k * nn);
+    st = phm_sim::model_tables(Q + (size_t)k * nn, n, "model " + std::to_string(k) + ": ", &in.qoff[(size_t)k * nn], &in.qtot[(size_t)k * n],
+                               &in.inv_rate[(size_t)k * n]);
+    if (st) return st;
   }
-  in.pid.assign(pid, pid + (size_t)n_pid * n);
-  in.ptot.resize(n_pid);
-  for (int k = 0; k < n_pid; ++k) {
-    double psum = 0.0;
-    st = check_root_prior(pid + (size_t)k * n, n, psum);
-    if (st) return fail(st, "pid column " + std::to_string(k) + ": " + g_phm_err);
-    double tot = pid[(size_t)k * n];
-    for (int j = 1; j < n; ++j) tot += pid[(size_t)k * n + j];
-    in.ptot[k] = tot;
-  }
-  st = check_observe(observe, n, in.state_map);
+  st = phm_sim::root_priors(pid, n_pid, n, true, in.pid, in.ptot);
   if (st) return st;
-  for (int i = 0; i < n; ++i) in.state_map.push_back(i + 1);
+  st = phm_sim::state_maps(observe, n, in.state_map);
+  if (st) return st;
   phm::depth_levels(in.sched, in.order, in.level_off);
   return PHM_OK;
 }
@@ -187,21 +162,13 @@ int32_t simm_device(const SimmInput& in, int32_t device, int64_t first, int64_t 
     if (errh & phm::DERR_CAPACITY) {
       unsigned long long caph = 0;
       HIPCHK(hipMemcpy(&caph, dcap.p, sizeof caph, hipMemcpyDeviceToHost));
-      return fail(PHM_ERR_CAPACITY, "model " + std::to_string(caph >> 32) + ": more than " + std::to_string(phm::SIM_MAX_JUMPS) +
-                                        " jumps on edge row " + std::to_string((caph & 0xFFFFFFFFull) + 1) +
-                                        " (samplethebranch stops there, R/sourceme.R:356)");
+      return phm_sim::capacity_refusal("model " + std::to_string(caph >> 32) + ": ", caph & 0xFFFFFFFFull);
     }
     st = device_status(errh);
     if (st) return st;
-    // statistics: [col][pad] -> the caller's column-major H x cols matrix, rows h0 .. h0 + Hc - 1
-    HIPCHK(hipMemcpy2D(stats + h0, sizeof(double) * (size_t)H, dout.p, sizeof(double) * pad, sizeof(double) * (size_t)Hc, cols,
-                       hipMemcpyDeviceToHost));
-    HIPCHK(phm::launch_sim_transpose(dns.as<uint8_t>(), T, (int)Hc, (int)pad, dmap.as<int32_t>(), dtr.as<int32_t>(), nullptr));
-    HIPCHK(hipMemcpy(tips + h0 * T, dtr.p, sizeof(int32_t) * (size_t)Hc * T, hipMemcpyDeviceToHost));
-    if (nodes) {
-      HIPCHK(phm::launch_sim_transpose(dns.as<uint8_t>(), rows, (int)Hc, (int)pad, dmap.as<int32_t>() + n, dtr.as<int32_t>(), nullptr));
-      HIPCHK(hipMemcpy(nodes + h0 * rows, dtr.p, sizeof(int32_t) * (size_t)Hc * rows, hipMemcpyDeviceToHost));
-    }
+    st = phm_sim::send_home(dout.as<double>(), dns.as<uint8_t>(), dmap.as<int32_t>(), dtr.as<int32_t>(), n, T, rows, (int)pad, h0, Hc,
+                            stats, H, tips, nodes);
+    if (st) return st;
   }
   if (mh) {
     HIPCHK(tm.start());

@@ -16,6 +16,9 @@
 
 #include <algorithm>
 
+#include "phm_history.h"
+#include "phm_sim_walk.h"
+
 namespace phm {
 
 namespace {
@@ -35,20 +38,6 @@ __device__ __forceinline__ SimmLane simm_lane(const SimmParams& p, int i) {
   return l;
 }
 
-// first j with u * total <= w_0 + .. + w_j, w_j at w[j st], `total` summed left to right beforehand
-template <int NS>
-__device__ __forceinline__ int simm_categorical(const double* __restrict__ w, size_t st, double total, int n_rt, double u,
-                                                uint32_t& err) {
-  const int n = NS > 0 ? NS : n_rt;
-  if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
-  const double thr = u * total;
-  double cum = w[0];
-  int idx = (thr <= cum) ? 0 : 1;
-#pragma unroll
-  for (int j = 1; j < n - 1; ++j) { cum += w[(size_t)j * st]; idx += (thr <= cum) ? 0 : 1; }
-  return idx;
-}
-
 // root: draw 0 of the stream (root node id, iteration SIM_ITER), categorical over the lane's pid
 __global__ __launch_bounds__(SIMM_BLOCK) void simm_root_kernel(SimmParams p) {
   const int i = blockIdx.x * SIMM_BLOCK + threadIdx.x;
@@ -58,8 +47,8 @@ __global__ __launch_bounds__(SIMM_BLOCK) void simm_root_kernel(SimmParams p) {
   uint32_t err = 0;
   int s = 0;
   if (l.valid)
-    s = simm_categorical<0>(p.pid + l.k, (size_t)p.Kp, p.ptot[l.k], p.n_states,
-                            stream_u(p.seed_lo, p.seed_hi, l.rep, SIM_ITER, ENT_NODE | root_id, 0), err);
+    s = sim_categorical<0>(p.pid + l.k, (size_t)p.Kp, p.ptot[l.k], p.n_states,
+                           stream_u(p.seed_lo, p.seed_hi, l.rep, SIM_ITER, ENT_NODE | root_id, 0), err);
   p.nstate[(size_t)(root_id - 1) * p.n_hist_pad + i] = (uint8_t)s;
   if (err) atomicOr(p.err, err);
 }
@@ -79,7 +68,6 @@ __global__ __launch_bounds__(SIMM_BLOCK) void simm_level_kernel(SimmParams p, in
   const int n_tiles = p.n_hist_pad / 64;
   const int n_groups = (end - begin + group - 1) / group;
   const int64_t items = (int64_t)n_groups * n_tiles;
-  constexpr int NA = NS > 0 ? NS : 1, NC = NS > 0 ? NS * NS : 1;
   uint32_t err = 0;
   for (int64_t item = wslot; item < items; item += (int64_t)gridDim.x * (SIMM_BLOCK / 64)) {
     const int tile = (int)(item % n_tiles);
@@ -87,79 +75,27 @@ __global__ __launch_bounds__(SIMM_BLOCK) void simm_level_kernel(SimmParams p, in
     const int i = tile * 64 + lane;
     const SimmLane l = simm_lane(p, i);
     if (!l.valid) continue;                                        // a lane past the last history of the chunk
-    unsigned long long acc_dw[NA];
-    uint32_t acc_ct[NC];
-#pragma unroll
-    for (int c = 0; c < NA; ++c) acc_dw[c] = 0ull;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc_ct[c] = 0u;
-    auto add_dwell = [&](int s, double x) {                        // fixed point: exact in any order
-      const unsigned long long fx = (unsigned long long)__double2ll_rn(x * p.fx_scale);
-      if constexpr (NS > 0) {
-#pragma unroll
-        for (int c = 0; c < NA; ++c) acc_dw[c] += (s == c) ? fx : 0ull;
-      } else {
-        atomicAdd(p.dwfx + (size_t)s * pad + i, fx);
-      }
-    };
-    auto count = [&](int from, int to) {
-      const int col = from * n + to;
-      if constexpr (NS > 0) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc_ct[c] += (col == c) ? 1u : 0u;
-      } else {
-        atomicAdd(p.cnt + (size_t)col * pad + i, 1u);
-      }
-    };
+    StatLanes<NS, NS * NS> st;                                     // counts by from * n + to
+    st.begin(p.dwfx, p.cnt, pad, (size_t)i, p.fx_scale);
+    const SimModel model = {p.qoff, p.qtot, p.inv_rate, Kp, l.k, n};   // model-fastest tables, the lane's model
     for (int qi = q0; qi < q1; ++qi) {
       const DownStep d = p.down[p.order[qi]];                      // wave-uniform
       const size_t parent_row = (size_t)(T + d.parent), child_row = (size_t)(d.child >= 0 ? T + d.child : ~d.child);
       const double t = p.edge_length[d.edge];
-      int s = p.nstate[parent_row * pad + i];
-      // maps: segments of this branch so far (count) / the write cursor and the end of the history's row of this edge (write)
-      const int64_t mrow = (p.map_row0 + i) * p.n_edge + d.edge;
-      int64_t cur = 0, stop = 0;
-      if constexpr (MODE == MAPS_WRITE) { cur = p.maps.off[mrow] - p.maps.base; stop = p.maps.off[mrow + 1] - p.maps.base; }
-      auto segment = [&](int st, double x) {
-        add_dwell(st, x);
-        if constexpr (MODE == MAPS_WRITE) {
-          if (cur < stop) { p.maps.dwell[cur] = x; p.maps.state[cur] = st + 1; }
-        }
-        if constexpr (MODE != MAPS_OFF) ++cur;
-      };
+      const int s0 = p.nstate[parent_row * pad + i];
+      MapRow<MODE> mr;                                             // maps: the history's row of this edge
+      mr.begin(p.maps, (p.map_row0 + i) * p.n_edge + d.edge);
       Stream rs;
       rs.open(ENT_BSTATE | (uint32_t)d.edge, SIM_ITER, l.rep, p.seed_lo, p.seed_hi);
-      double pos = 0.0;
-      for (uint32_t j = 0;; ++j) {
-        const double ir = p.inv_rate[(size_t)s * Kp + l.k];
-        if (ir == 0.0) { segment(s, t - pos); break; }             // absorbing: the rest of the branch, no draw
-        const double gap = ir * neglog_u32(rs.draw_word(2u * j), s_ltab);
-        const double dab = pos + gap;
-        if (!(dab < t)) { segment(s, gap - (dab - t)); break; }    // seg_len - (dab - branchlength)
-        segment(s, gap);
-        if (j == (uint32_t)SIM_MAX_JUMPS) {
-          err |= DERR_CAPACITY;
-          atomicMin(p.cap, ((unsigned long long)(p.k0 + (uint32_t)l.k) << 32) | (unsigned long long)(uint32_t)d.edge);
-          break;
-        }
-        const int nx = simm_categorical<NS>(p.qoff + (size_t)(s * n) * Kp + l.k, Kp, p.qtot[(size_t)s * Kp + l.k], n,
-                                            rs.draw(2u * j + 1u), err);
-        count(s, nx);
-        s = nx;
-        pos = dab;
-      }
+      const int s = sim_walk_branch<NS>(
+          s0, t, rs, s_ltab, model,
+          [&](int state, double x) { st.dwell(state, x); mr.emit(x, state); },
+          [&](int from, int to) { st.count(from * n + to); },
+          [&]() { atomicMin(p.cap, ((unsigned long long)(p.k0 + (uint32_t)l.k) << 32) | (unsigned long long)(uint32_t)d.edge); }, err);
       p.nstate[child_row * pad + i] = (uint8_t)s;
-      if constexpr (MODE == MAPS_COUNT) p.maps.seg_cnt[(size_t)d.edge * p.map_pad + (size_t)(p.map_row0 + i)] = (uint16_t)cur;
-      if constexpr (MODE == MAPS_WRITE) {
-        if (cur != stop) atomicMin(p.maps.bad_row, (unsigned long long)mrow);
-      }
+      mr.end((size_t)d.edge * p.map_pad + (size_t)(p.map_row0 + i));
     }
-    if constexpr (NS > 0) {
-#pragma unroll
-      for (int c = 0; c < NA; ++c) if (acc_dw[c]) atomicAdd(p.dwfx + (size_t)c * pad + i, acc_dw[c]);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) if (acc_ct[c]) atomicAdd(p.cnt + (size_t)c * pad + i, acc_ct[c]);
-    }
+    st.flush();
   }
   if (err) atomicOr(p.err, err);
 }
@@ -173,24 +109,9 @@ __global__ __launch_bounds__(256) void simm_finish_kernel(SimmParams p) {
   const int c = (int)(gid / pad);
   const int64_t i = gid % pad;
   double v;
-  if (c < n) v = (double)(long long)p.dwfx[(size_t)c * pad + i] * p.fx_inv;
-  else if (c < n + nn) v = (double)p.cnt[(size_t)(c - n) * pad + i];
+  if (c < n + nn) v = stat_cell_value(p.dwfx, p.cnt, n, c, (size_t)pad, (size_t)i, p.fx_inv);
   else v = (double)p.nstate[(size_t)(p.n_tips + p.root) * pad + i];
   p.out[gid] = v;
-}
-
-template <int MODE>
-void launch_level(const SimmParams& p, int blocks, int begin, int end, int group, hipStream_t stream) {
-#ifdef PHM_EXPERIMENT_SIMM_GENERIC        // measurement builds only (DESIGN.md section 22): 2..4 states through the 5..64-state form
-  hipLaunchKernelGGL((simm_level_kernel<0, MODE>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p, begin, end, group);
-  return;
-#endif
-  switch (p.n_states) {
-    case 2: hipLaunchKernelGGL((simm_level_kernel<2, MODE>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p, begin, end, group); break;
-    case 3: hipLaunchKernelGGL((simm_level_kernel<3, MODE>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p, begin, end, group); break;
-    case 4: hipLaunchKernelGGL((simm_level_kernel<4, MODE>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p, begin, end, group); break;
-    default: hipLaunchKernelGGL((simm_level_kernel<0, MODE>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p, begin, end, group); break;
-  }
 }
 
 }  // namespace
@@ -202,6 +123,11 @@ hipError_t launch_simulate_models(const SimmParams& p, const std::vector<int32_t
     return hipErrorInvalidValue;
   constexpr int W = SIMM_BLOCK / 64;
   const int64_t n_tiles = p.n_hist_pad / 64;
+#ifdef PHM_EXPERIMENT_SIMM_GENERIC        // measurement builds only (DESIGN.md section 22): 2..4 states through the 5..64-state form
+  const int n_form = 0;
+#else
+  const int n_form = p.n_states;
+#endif
   int n_launch = 0;
   hipLaunchKernelGGL(simm_root_kernel, dim3((p.n_hist_pad + SIMM_BLOCK - 1) / SIMM_BLOCK), dim3(SIMM_BLOCK), 0, stream, p);
   ++n_launch;
@@ -214,9 +140,10 @@ hipError_t launch_simulate_models(const SimmParams& p, const std::vector<int32_t
     if (max_group > 0) group = std::min(group, max_group);
     const int64_t items = (cnt + group - 1) / group * n_tiles;
     const int blocks = (int)std::min<int64_t>((items + W - 1) / W, 65536);
-    if (maps_mode == MAPS_COUNT) launch_level<MAPS_COUNT>(p, blocks, begin, end, group, stream);
-    else if (maps_mode == MAPS_WRITE) launch_level<MAPS_WRITE>(p, blocks, begin, end, group, stream);
-    else launch_level<MAPS_OFF>(p, blocks, begin, end, group, stream);
+    with_producer_form(maps_mode, n_form, [&](auto mode, auto ns) {
+      hipLaunchKernelGGL((simm_level_kernel<decltype(ns)::value, decltype(mode)::value>), dim3(blocks), dim3(SIMM_BLOCK), 0, stream, p,
+                         begin, end, group);
+    });
     ++n_launch;
   }
   const int64_t cells = (int64_t)(p.n_states + p.n_states * p.n_states + 1) * p.n_hist_pad;
