@@ -1120,9 +1120,11 @@ static void model_from_Q(const double* Q, int n, double Omega, double* B2, doubl
 static int mcmc_driver(const orc_tree* x, int n, const double* Q_cm, const double* pid,
                          const double* B_cm, double Omega, const int32_t* nen,
                          const int32_t* nodelist, int32_t root, int32_t N, int variant,
-                         int faithful_search, orc_rng* rng, double* out, orc_dump* dump, const double* prior, int dic) {
+                         int faithful_search, orc_rng* rng, double* out, orc_dump* dump, const double* prior, int dic,
+                         const double* Q_sched) {
   int e = check_tree(x); if (e) return e;
   if (dic && (!prior || !x->edge_length)) return ORC_ERR_BAD_INPUT;
+  if (Q_sched && prior) return ORC_ERR_BAD_INPUT;             /* a schedule takes the place of the updates */
   if (n < 2 || N < 0) return ORC_ERR_BAD_INPUT;
   /* variant | ORC_FORCE_NORMALISE: divide every internal partial-likelihood row by its sum (what makePLrcpp_bigtree :525 does)
    * in a driver that does not -- NOT in the reference: sumstatMCMC / SPARSEsumstatMCMC underflow on trees of thousands of tips
@@ -1211,6 +1213,9 @@ static int mcmc_driver(const orc_tree* x, int n, const double* Q_cm, const doubl
         for (int j = 1; j <= kk; ++j) updategammas(Q, n, Omega, prior, out, N, it, HS(2 + 2 * kk + j), j, 0);
       }
 #undef HS
+      model_from_Q(Q, n, Omega, B2, Bc, Qd);
+    } else if (Q_sched) {                                     /* the next iteration's Q is given, not drawn */
+      if (it + 1 < N) memcpy(Q, Q_sched + (size_t)(it + 1) * n * n, sizeof(double) * n * n);
       model_from_Q(Q, n, Omega, B2, Bc, Qd);
     }
   }
@@ -1314,7 +1319,7 @@ int orc_maketreelistMCMCmt(const orc_tree* const* xs, int treecount, int n, cons
 int orc_maketreelistMCMC(const orc_tree* x, int n, const double* Q_cm, const double* pid, const double* B_cm, double Omega,
                          const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N, int variant,
                          int faithful_search, orc_rng* rng, double* out, orc_dump* dump) {
-  return mcmc_driver(x, n, Q_cm, pid, B_cm, Omega, nen, nodelist, root, N, variant, faithful_search, rng, out, dump, NULL, 0);
+  return mcmc_driver(x, n, Q_cm, pid, B_cm, Omega, nen, nodelist, root, N, variant, faithful_search, rng, out, dump, NULL, 0, NULL);
 }
 
 /* maketreelistMCMCbf :1258-1305 (variant ORC_MCMC_BF, prior = 4 numbers) and maketreelistMCMCks :1802-1872
@@ -1326,7 +1331,27 @@ int orc_maketreelistMCMC_qupdate(const orc_tree* x, int n, const double* Q_cm, c
   if (!prior) return ORC_ERR_BAD_INPUT;
   /* variant | 16: the DIC drivers maketreelistMCMC2sDICt :3183-3264 / maketreelistMCMCksDICt :3300-3403 (one more column) */
   return mcmc_driver(x, n, Q_cm, pid, B_cm, Omega, nen, nodelist, root, N, variant & 15, faithful_search, rng, out, dump, prior,
-                     (variant & 16) != 0);
+                     (variant & 16) != 0, NULL);
+}
+
+/* The sweep of the KS / BF drivers under a GIVEN sequence of models: iteration `it` runs under Q_sched[it] (N row-major n x n
+ * matrices), the chain state carries over, no update is drawn, and B / the rexp rates are rebuilt from the next Q after every
+ * sweep exactly as the updating drivers rebuild them (model_from_Q); iteration 0 uses the caller's B like they do.  The parameter
+ * columns hold the scheduled Q's.  Counter-based mode only: there the updates draw on streams of their own (replica word
+ * 0xFFFFFFFF, entity 0xFFFFFF00 | id -- hs_u), so leaving them out moves none of the chain's draws and a schedule made of the Qs
+ * that orc_maketreelistMCMC_qupdate went through reproduces that run bit for bit; the tape and R-stream modes share one
+ * sequential stream between sweep and updates and are refused. */
+int orc_maketreelistMCMC_schedule(const orc_tree* x, int n, const double* Q_sched_rm, const double* pid, const double* B_cm,
+                                  double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
+                                  int variant, int faithful_search, orc_rng* rng, double* out, orc_dump* dump) {
+  if (!Q_sched_rm || !rng || rng->mode != 0 || N < 1 || n < 2) return ORC_ERR_BAD_INPUT;
+  if (variant != ORC_MCMC_KS && variant != ORC_MCMC_BF) return ORC_ERR_BAD_INPUT;
+  double* Q0 = (double*)malloc(sizeof(double) * n * n);       /* mcmc_driver reads its starting Q column-major */
+  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) Q0[i + (size_t)j * n] = Q_sched_rm[(size_t)i * n + j];
+  int e = mcmc_driver(x, n, Q0, pid, B_cm, Omega, nen, nodelist, root, N, variant, faithful_search, rng, out, dump, NULL, 0,
+                      Q_sched_rm);
+  free(Q0);
+  return e;
 }
 
 /* one iteration's updates applied to a row-major Q given a statistics row (test entry point) */

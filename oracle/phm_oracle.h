@@ -179,6 +179,13 @@ int orc_maketreelistMCMC_qupdate(const orc_tree* x, int n, const double* Q_cm, c
                                  int variant, const double* prior, int faithful_search, orc_rng* rng, double* out_cm,
                                  orc_dump* dump);
 
+/* The KS / BF sweep under a given sequence of models (no updates drawn): iteration `it` runs under Q_sched_rm[it] (N row-major
+ * n x n matrices), the chain state carries over, B and the rexp rates are rebuilt from the next Q after every sweep as the
+ * updating drivers rebuild them; the parameter columns hold the scheduled Q's.  Counter-based mode (rng.mode = 0) only. */
+int orc_maketreelistMCMC_schedule(const orc_tree* x, int n, const double* Q_sched_rm, const double* pid, const double* B_cm,
+                                  double Omega, const int32_t* nen, const int32_t* nodelist, int32_t root, int32_t N,
+                                  int variant, int faithful_search, orc_rng* rng, double* out_cm, orc_dump* dump);
+
 int orc_qupdate_apply(int variant, int n, double* Q_rm, double Omega, const double* prior, const double* row,
                       uint32_t seed_lo, uint32_t seed_hi, uint32_t iter);
 

@@ -161,6 +161,38 @@ def maketreelistMCMC(z, Q, pid, B, Omega, nen, nodelist, root, N, variant=PLAIN,
     return (out, rc, db) if dump else (out, rc)
 
 
+def maketreelistMCMC_schedule(z, Q_sched, pid, Omega, nen, nodelist, root, variant=KS, seed=1, replica=0, dump=False):
+    """orc_maketreelistMCMC_schedule: the KS / BF sweep with iteration ``it`` run under ``Q_sched[it]`` ([N, n, n]), no updates
+    drawn, the chain state carried over; the parameter columns are those of the scheduled Qs.  Counter-based streams only."""
+    Qs = np.ascontiguousarray(Q_sched, dtype=np.float64)
+    N, n = Qs.shape[0], Qs.shape[1]
+    assert Qs.shape == (N, n, n)
+    ft = FlatTree(z)
+    Bc = np.asfortranarray(np.eye(n) + Qs[0] / Omega)
+    pid = np.ascontiguousarray(pid, dtype=np.float64)
+    nen = np.ascontiguousarray(nen, dtype=np.int32)
+    nodelist = np.ascontiguousarray(nodelist, dtype=np.int32)
+    cols = n + n * n + 3 if variant == BF else n + n * n + 2 + 3 * (n // 2 - 1) + 1
+    out = np.zeros((N, cols), order="F")
+    rng, _ = make_rng(seed, replica)
+    db = DumpBuf(ft, n) if dump else None
+    rc = lib().orc_maketreelistMCMC_schedule(C.byref(ft.c), n, _ptr(Qs, C.c_double), _ptr(pid, C.c_double), _ptr(Bc, C.c_double),
+                                             C.c_double(Omega), _ptr(nen, C.c_int32), _ptr(nodelist, C.c_int32), int(root), int(N),
+                                             int(variant), 0, C.byref(rng), _ptr(out, C.c_double), C.byref(db.c) if db else None)
+    return (out, rc, db) if dump else (out, rc)
+
+
+def qupdate_apply(variant, Q, Omega, prior, row, seed, it):
+    """orc_qupdate_apply: (the Q that iteration ``it``'s updates make of ``Q`` and the statistics row ``row``, rc)"""
+    Qn = np.ascontiguousarray(Q, dtype=np.float64).copy()
+    prior = np.ascontiguousarray(prior, dtype=np.float64)
+    row = np.ascontiguousarray(row, dtype=np.float64)
+    rc = lib().orc_qupdate_apply(int(variant), Qn.shape[0], _ptr(Qn, C.c_double), C.c_double(Omega), _ptr(prior, C.c_double),
+                                 _ptr(row, C.c_double), C.c_uint32(seed & 0xFFFFFFFF), C.c_uint32((seed >> 32) & 0xFFFFFFFF),
+                                 C.c_uint32(it))
+    return Qn, rc
+
+
 def maketreelistMCMCmt(treelist, Q, pid, B, Omega, nen_m, nodelist_m, roots, N, prior, variant=MT, seed=1, replica=0,
                        faithful_search=False, rstream=False):
     """orc_maketreelistMCMCmt: nen_m / nodelist_m one row per tree (row-major), roots one entry per tree."""
