@@ -29,6 +29,9 @@ EXPORTS = [
     "phm_expected_through_time", "phm_loglik_models", "phm_expected_stats_models", "phm_sample_histories_models",
     "phm_gibbs_rates", "phm_ancestral_models", "phm_simulate_histories_models", "phm_ancestral_models_wide",
 ]
+# include/phylomap_hip_ext.h: entry points added after EXPORTS was recorded with the calls of tests/golden/api_calls (DESIGN.md
+# section 24); a regeneration of that record merges the two lists
+EXT_EXPORTS = ["phm_sample_histories_models_wide"]
 
 
 class PhmError(RuntimeError):
@@ -87,7 +90,7 @@ _lib = None
 
 
 def _argtypes():
-    """{symbol: argtypes} of include/phylomap_hip.h, from the argument runs that the entry points share"""
+    """{symbol: argtypes} of include/phylomap_hip.h and phylomap_hip_ext.h, from the argument runs that the entry points share"""
     i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
     pi, pl, pd, pt, po = (C.POINTER(t) for t in (C.c_int32, C.c_int64, C.c_double, Tree, Options))
     sweep = [pt, i32, pd, pd, pd, f64, pi, pi, i32, i32]     # tree, n, Q, pid, B, Omega, nen, nodelist, root, N
@@ -137,6 +140,7 @@ def _argtypes():
          "phm_simulate_histories_models": models[:7] + [i32, po, pi, pi, pd] + maps,
          "phm_sparse_kernel_source": [i32, pd, C.c_char_p, i32]}
     t["phm_maketreelistMCMCksmt"] = t["phm_maketreelistMCMCmt"]
+    t["phm_sample_histories_models_wide"] = t["phm_sample_histories_models"]
     for name in ("phm_maketreelistMCMC", "phm_maketreelistMCMC_bigtree", "phm_SPARSEmaketreelistMCMC", "phm_maketreelistMCMCks_sweep",
                  "phm_maketreelistMCMCbf_sweep"):
         t[name] = sweep + out

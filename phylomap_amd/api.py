@@ -471,9 +471,10 @@ def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=
 
 def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=None, nodes=False, maps=False, **opt):
     """``draws`` exact, independent histories given the tips for each of K rate matrices (and each site) in one call (DESIGN.md
-    section 19) -> phm_sample_histories_models: stochastic maps under the models of a fit and its uncertainty
+    sections 19 and 24) -> phm_sample_histories_models (2..8 states, the models across the lanes of the tree passes) or
+    phm_sample_histories_models_wide (9..64 states, one state per lane there): stochastic maps under the models of a fit and its uncertainty
     (``fit.sample_thetas``), of per-dataset fits or of a posterior sample of Q.  No burn-in, no jump cap (max(-q_ii) t_b up to
-    32 768), missing tips and ``observe`` maps allowed; 2..8 states.  ``Qs``, ``pid``, ``z``, ``sites``, ``observe`` and
+    32 768), missing tips and ``observe`` maps allowed; 2..64 states.  ``Qs``, ``pid``, ``z``, ``sites``, ``observe`` and
     ``site_of_model`` are ``loglik_models``'.  Returns ``(stats, loglik)``: [K, S, draws, n + n(n-1)] in ``expected_sumstat``'s
     columns and [K, S] (``loglik_models``' values bit for bit); with ``site_of_model`` the S axis is absent.  ``nodes=True``
     appends [K, S, draws, n_tips + Nnode] 1-based TRUE states by ape node id, tips included (a missing tip and the hidden state
@@ -489,10 +490,11 @@ def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=
     nst = np.zeros(hshape + (a.NT,), dtype=np.int32) if nodes else None
     args = head + (D, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double), _lib._p(nst, C.c_int32))
     res = (np.moveaxis(stats, 0, -1), ll) + ((nst,) if nodes else ())
+    fn = L.phm_sample_histories_models_wide if n > 8 else L.phm_sample_histories_models
     if not maps:
-        _lib.check(L.phm_sample_histories_models(*args, None, 0, None, None))
+        _lib.check(fn(*args, None, 0, None, None))
         return res
-    return res + (_two_phase_maps(L.phm_sample_histories_models, args, int(np.prod(hshape)), a.E),)
+    return res + (_two_phase_maps(fn, args, int(np.prod(hshape)), a.E),)
 
 
 AncestralStates = namedtuple("AncestralStates", ["loglik", "node_post", "joint_states", "joint_logp", "nodes"])

@@ -39,6 +39,8 @@ struct AwParams {
   double* jlogp;                               // [Ev] log of the joint maximum
 };
 
+// allows `fn` up to `bytes` of dynamic LDS on the current device (above the 64 KiB a launch gets unasked); once per (function, device)
+hipError_t aw_allow_lds(const void* fn, int bytes);
 // tip rows of L and sL
 hipError_t launch_aw_tips(const AwParams& p, hipStream_t stream);
 // one height level of the sum-product (joint = false: L, sL) or max-product (joint = true: M, sM, ptr) up pass: `steps` (device)

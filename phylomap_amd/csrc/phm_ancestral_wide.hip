@@ -30,21 +30,6 @@ constexpr int AW_BLOCK = 256;
 constexpr int AW_WALK = 4;                     // sites a group walks through the staged matrices
 constexpr double AW_LN2 = 0.69314718055994530942;
 
-// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the function object of the current device: set once per (function,
-// device) to the most its class can ask for (n = NP: 70 784 bytes at 64 states, above the 64 KiB a launch gets unasked)
-hipError_t aw_allow_lds(const void* fn, int bytes) {
-  static std::mutex mu;
-  static std::vector<std::pair<const void*, int>> done;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> guard(mu);
-  for (const auto& d : done) if (d.first == fn && d.second == dev) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) done.emplace_back(fn, dev);
-  return e;
-}
-
 template <int NP> struct AwShape {
   static constexpr int G = AW_BLOCK / NP;      // groups (items) of a workgroup
   static constexpr int LD = NP + 1;            // row of a staged matrix
@@ -338,6 +323,22 @@ hipError_t aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_
 }
 
 }  // namespace
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the function object of the current device: set once per (function,
+// device) to the most its class can ask for (here n = NP: 70 784 bytes at 64 states, above the 64 KiB a launch gets unasked);
+// phm_sample_wide.hip's table kernel asks through it as well
+hipError_t aw_allow_lds(const void* fn, int bytes) {
+  static std::mutex mu;
+  static std::vector<std::pair<const void*, int>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  std::lock_guard<std::mutex> guard(mu);
+  for (const auto& d : done) if (d.first == fn && d.second == dev) return hipSuccess;
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.emplace_back(fn, dev);
+  return e;
+}
 
 #define AW_DISPATCH(call16, call32, call64) (p.NP == 16 ? (call16) : p.NP == 32 ? (call32) : (call64))
 

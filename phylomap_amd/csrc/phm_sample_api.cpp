@@ -4,9 +4,8 @@
 // and per batch of tiles the root, node-level, branch and finish launches of phm_sample.hip, which read P, L and pid in place.
 // Histories are addressed by their global index h = e D + d (e: the evaluation's index into loglik), so a shard of models is a
 // contiguous range of histories and section 14's per-shard map buffers (phm_maps_host.h) serve unchanged.
-#include "phm_loglik_host.h"
 #include "phm_maps_host.h"
-#include "phm_sample.h"
+#include "phm_sample_host.h"
 
 #include <limits>
 
@@ -16,44 +15,6 @@ using namespace phm_ex;
 using namespace phm_ll;
 
 const std::string SM_FN = "phm_sample_histories_models: ";
-
-struct SmInput {
-  LlInput ll;
-  int cols = 0, D = 0, fx_exp = 0;
-  int64_t n_eval = 0, H = 0;                            // evaluations, histories
-  std::vector<int32_t> depth;                           // [K] M(mu_k max_b t_b)
-  std::vector<int32_t> order, level_off;                // s.down positions by the depth of the parent
-  phm_options opt;
-  int32_t* nodes = nullptr;
-};
-
-int32_t sm_prepare(SmInput& sm, int32_t draws) {
-  LlInput& in = sm.ll;
-  const int n = in.n;
-  if (draws < 1) return fail(PHM_ERR_BAD_INPUT, SM_FN + "draws must be >= 1");
-  if (n > phm::LL_LANE_MAX) return fail(PHM_ERR_UNSUPPORTED, SM_FN + "more than 8 states are not supported");
-  if ((int64_t)in.S * in.K > (int64_t)INT32_MAX) return fail(PHM_ERR_BAD_INPUT, SM_FN + "sites * models must fit in 31 bits (evaluation ids)");
-  sm.cols = n + n * (n - 1);
-  sm.D = draws;
-  sm.n_eval = in.paired ? in.K : (int64_t)in.S * in.K;
-  if (sm.n_eval > INT64_MAX / 4096 / draws) return fail(PHM_ERR_BAD_INPUT, SM_FN + "evaluations * draws overflows");
-  sm.H = sm.n_eval * draws;
-  const size_t nn = (size_t)n * n;
-  double t_max = 0.0, tree_len = 0.0;
-  for (int b = 0; b < in.E; ++b) { t_max = std::max(t_max, in.edge_length[b]); tree_len += in.edge_length[b]; }
-  (void)std::frexp(std::max(tree_len, 1.0), &sm.fx_exp);
-  sm.depth.resize(in.K);
-  for (int k = 0; k < in.K; ++k) {
-    double mu = 0.0;
-    for (int i = 0; i < n; ++i) mu = std::max(mu, -in.Qr[(size_t)k * nn + (size_t)i * n + i]);
-    for (int b = 0; b < in.E; ++b)
-      if (mu * in.edge_length[b] > phm::SM_MAX_JUMP_MEAN)
-        return fail(PHM_ERR_UNSUPPORTED, "model " + std::to_string(k) + ", edge row " + std::to_string(b + 1) + ": max(-q_ii) * t_b above 32768");
-    sm.depth[k] = phm::sm_stop_index(mu * t_max);
-  }
-  phm::depth_levels(in.sched, sm.order, sm.level_off);
-  return PHM_OK;
-}
 
 int32_t sm_device(const SmInput& sm, int32_t device, int64_t first, int64_t count, double* stats, double* loglik,
                   phm_maps::Host* mh, size_t si) {
@@ -255,7 +216,7 @@ int32_t phm_sample_histories_models(const phm_tree* x, int32_t n_states, int32_t
   int32_t st = ll_validate(SM_FN, x, n_states, n_models, Q, pid, n_pid, observe, site_of_model, o, sm.ll);
   if (st) return st;
   sm.opt = o; sm.nodes = nodes;
-  st = sm_prepare(sm, draws);
+  st = sm_prepare(SM_FN, 2, phm::LL_LANE_MAX, "more than 8 states are not supported", sm, draws);
   if (st) return st;
   const bool want_maps = map_off || map_dwell || map_state;
   phm_maps::Host mh;

@@ -1,0 +1,68 @@
+// phm_sample_wide.h -- kernel parameter block and launchers of the exact sampler of histories over many rate matrices and sites at
+// 9..64 states (phm_sample_wide.hip), behind phm_sample_histories_models_wide (phm_sample_wide_api.cpp).  DESIGN.md section 24.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "phm_ancestral_wide.h"
+#include "phm_maps.h"
+#include "phm_sample.h"
+#include "phm_sched.h"
+
+namespace phm {
+
+constexpr int SW_TABLE_BLOCK = 256;            // lanes of the workgroup that owns a model's table
+constexpr int SW_NODE_BLOCK = 256;             // four waves, one (tile, edge of the level) each
+constexpr int SW_BRANCH_BLOCK = 64;            // a workgroup is ONE wave: its LDS copy of B belongs to the item's model
+constexpr int64_t SW_ITEMS_MAX = (int64_t)1 << 30;   // (tile, branch) items of one launch: a grid dimension
+
+// row stride (doubles) of B in LDS: odd, so lanes on different rows of one column fall on different bank pairs
+__host__ __device__ inline int sw_row_stride(int n) { return n | 1; }
+
+// doubles of a model's table: rows m = 0 .. depth of n * n
+inline size_t sw_table_doubles(int n, int depth) { return ((size_t)depth + 1) * (size_t)n * n; }
+// dynamic LDS of the table kernel: B (padded rows) and the two ping-pong rows beta_m, beta_{m+1}
+inline size_t sw_table_lds_bytes(int n) { return sizeof(double) * ((size_t)n * sw_row_stride(n) + 2 * (size_t)n * n); }
+// dynamic LDS of the branch kernel: B (padded rows); the neglog table is static
+inline size_t sw_branch_lds_bytes(int n) { return sizeof(double) * (size_t)n * sw_row_stride(n); }
+
+// A tile is phm_sample.h's SmTile: 64 consecutive draws of one evaluation; ev is section 23's index model * Sc + site of the
+// launch and k the model in the chunk.
+struct SwParams {
+  int32_t n, NP, n_tips, n_node, n_edge, root_row;   // root_row: n_tips + internal index of the root
+  int32_t Kc, n_tiles;
+  size_t Ev;                                   // evaluations of the launch (Kc * Sc): row length of L
+  int64_t map_pad;                             // MAPS_COUNT: row length of maps.seg_cnt
+  uint32_t seed_lo, seed_hi, replica;
+  double fx_scale, fx_inv;
+  const double* Q;                             // [model][n][n] row-major
+  const double* P;                             // [model][edge][n][n] row-major (section 23)
+  const double* pid;                           // [model][n] normalised
+  const double* L;                             // [node row][Ev][NP] rescaled partial likelihoods (section 23)
+  const double* t;                             // [n_edge]
+  const SmTile* tiles;                         // [n_tiles]
+  const DownStep* down;                        // [n_edge] pre-order
+  const int32_t* order;                        // positions into down[], grouped by the depth of the parent
+  double* mu;                                  // [model]
+  double* B;                                   // [model][n][n] row-major: I + Q / mu (I when mu = 0)
+  const int32_t* depth_of;                     // [model] M(mu_k max_b t_b): the last row of the model's table
+  size_t tab_stride;                           // doubles between the tables of two models in `beta`
+  double* beta;                                // model k, row m: [e][c] = (B_k^m)[c, e], the n weights of a state draw contiguous
+  uint8_t* nstate;                             // [tile][n_tips + n_node][64] 0-based states by ape row
+  unsigned long long* dwfx;                    // [n][n_tiles * 64] dwell sums, fixed point
+  uint32_t* cnt;                               // [n (n-1)][n_tiles * 64]
+  double* out;                                 // [cols][n_tiles * 64]
+  int32_t* nodes;                              // NULL or [n_tiles * 64][n_tips + n_node] 1-based states
+  uint32_t* err;
+  MapsDev maps;
+};
+
+// mu, B and the table of models [0, Kc) of the chunk, a workgroup per model
+hipError_t launch_sw_table(const SwParams& p, hipStream_t stream);
+// root, node levels, branches and the finish of the tiles of p; level_off: boundaries of the depth levels in p.order (host)
+hipError_t launch_sw_sample(const SwParams& p, const std::vector<int32_t>& level_off, int maps_mode, hipStream_t stream);
+
+}  // namespace phm

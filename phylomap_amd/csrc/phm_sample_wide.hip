@@ -1,0 +1,284 @@
+// phm_sample_wide.hip -- exact, independent draws of histories given the tips for many rate matrices and sites at 9..64 states
+// (DESIGN.md section 24): section 19's sampler (phm_sample.hip) with the run-time state count, on section 23's buffers.  P_k(t_b)
+// is [model][edge][n][n] row-major and L is [node row][Ev][NP] as phm_ancestral_wide.hip leaves them; both are read in place.
+//
+// The unit of work is section 19's: a tile is 64 consecutive draws of ONE evaluation and a lane is one history, so the model is
+// wave-uniform and the serial per-history logic (the two-pass jump-count series, the time walk, the first-j categorical scan)
+// needs no cross-lane step.  Every sum is left to right over explicit products (the library is built with -ffp-contract=off).
+//
+//   table    a workgroup owns a model: mu_k, B_k = I + Q_k / mu_k and beta_m = B^m for m = 0 .. M(mu_k max t_b).  Row m is stored
+//            [e][c] = (B^m)[c, e], so the n weights beta_m[., e] of one state draw are a contiguous run.  beta_m and beta_{m+1}
+//            ping-pong in LDS: step m + 1 reads what step m wrote there, never its own global stores.
+//   root     a wave per tile; pid_k and L_root are wave-uniform.
+//   nodes    one launch per depth level, a wave per (tile, edge of the level); L_child is wave-uniform, the lane gathers its
+//            parent state's row of P.
+//   branch   a one-wave workgroup per (tile, branch).  B_k is staged in LDS (row stride n | 1) only when a lane of the wave
+//            drew two or more jumps, the one case in which a state is drawn; the neglog table sits in LDS.
+//   finish   fixed point -> double, counters -> double, node bytes -> 1-based int32.
+// Bounds: the series' loops end at the table depth (DERR_CAPACITY beyond it, nothing is read past the table), the walk at N <= M.
+#include "phm_sample_wide.h"
+
+#include <algorithm>
+
+#include "phm_device.h"
+#include "phm_history.h"
+
+namespace phm {
+
+namespace {
+
+// grid: model.  LDS: B [n][n | 1], two rows of the table [e][c].
+__global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
+  extern __shared__ __align__(16) double sw_lds[];
+  __shared__ double s_mu;
+  const int n = p.n, nn = n * n, LD = sw_row_stride(n);
+  const int k = blockIdx.x;
+  double* sB = sw_lds;
+  double* prev = sB + n * LD;
+  double* next = prev + nn;
+  const double* __restrict__ Qk = p.Q + (size_t)k * nn;
+  if (threadIdx.x == 0) {
+    double mu = 0.0;
+    for (int i = 0; i < n; ++i) mu = fmax(mu, -Qk[i * n + i]);
+    s_mu = mu;
+    p.mu[k] = mu;
+  }
+  __syncthreads();
+  const double mu = s_mu;
+  const int depth = p.depth_of[k];
+  double* __restrict__ tab = p.beta + (size_t)k * p.tab_stride;
+  for (int cell = threadIdx.x; cell < nn; cell += SW_TABLE_BLOCK) {
+    const int i = cell / n, j = cell - i * n;
+    const double d = i == j ? 1.0 : 0.0;
+    const double b = mu > 0.0 ? d + Qk[cell] / mu : d;
+    p.B[(size_t)k * nn + cell] = b;
+    sB[i * LD + j] = b;
+    prev[cell] = d;                                                  // beta_0 = I (symmetric: [e][c] as well)
+    tab[cell] = d;
+  }
+  __syncthreads();
+  for (int m = 0; m < depth; ++m) {                                  // beta_{m+1} = B beta_m, unfused left-to-right sums
+    double* __restrict__ row = tab + (size_t)(m + 1) * nn;
+    for (int cell = threadIdx.x; cell < nn; cell += SW_TABLE_BLOCK) {
+      const int e = cell / n, c = cell - e * n;
+      const double* b = sB + c * LD;
+      const double* v = prev + e * n;
+      double acc = b[0] * v[0];
+      for (int j = 1; j < n; ++j) acc += b[j] * v[j];
+      next[cell] = acc;
+      row[cell] = acc;
+    }
+    __syncthreads();                                                 // the hand-over: every cell of beta_{m+1} is in LDS
+    double* s = prev; prev = next; next = s;
+  }
+}
+
+// first j with u * sum(w) <= w_0 + .. + w_j, w_c = a[c] * b[c], sums left to right (sm_draw's run-time form)
+__device__ __forceinline__ int sw_draw(const double* __restrict__ a, const double* __restrict__ b, int n, double u, uint32_t& err) {
+  double total = a[0] * b[0];
+  for (int c = 1; c < n; ++c) total += a[c] * b[c];
+  if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
+  const double thr = u * total;
+  double cum = a[0] * b[0];
+  int idx = (thr <= cum) ? 0 : 1;
+  for (int c = 1; c < n - 1; ++c) { cum += a[c] * b[c]; idx += (thr <= cum) ? 0 : 1; }
+  return idx;
+}
+
+__global__ __launch_bounds__(SW_NODE_BLOCK) void sw_root_kernel(SwParams p) {
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x * (SW_NODE_BLOCK / 64) + (threadIdx.x >> 6);
+  if (tile >= p.n_tiles) return;
+  const SmTile tl = p.tiles[tile];
+  const int NT = p.n_tips + p.n_node;
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  uint32_t err = 0;
+  const double u = stream_u(p.seed_lo, p.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)p.root_row, 0);
+  const int s = sw_draw(p.pid + (size_t)tl.k * p.n, p.L + ((size_t)p.root_row * p.Ev + tl.ev) * p.NP, p.n, u, err);
+  p.nstate[((size_t)tile * NT + p.root_row) * 64 + lane] = (uint8_t)s;
+  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+}
+
+// one depth level: a wave per (tile, edge of the level) draws the child's state, tips included
+__global__ __launch_bounds__(SW_NODE_BLOCK) void sw_node_kernel(SwParams p, int begin, int end) {
+  const int lane = threadIdx.x & 63;
+  const int64_t item = (int64_t)blockIdx.x * (SW_NODE_BLOCK / 64) + (threadIdx.x >> 6);
+  const int n_lvl = end - begin;
+  if (item >= (int64_t)n_lvl * p.n_tiles) return;
+  const int n = p.n;
+  const int tile = (int)(item / n_lvl);
+  const DownStep ds = p.down[p.order[begin + (int)(item % n_lvl)]];
+  const SmTile tl = p.tiles[tile];
+  const int NT = p.n_tips + p.n_node;
+  const int crow = ds.child >= 0 ? p.n_tips + ds.child : ~ds.child;
+  uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+  const int a = nst[(p.n_tips + ds.parent) * 64 + lane];
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  uint32_t err = 0;
+  const double u = stream_u(p.seed_lo, p.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)crow, 0);
+  const int e = sw_draw(p.P + (((size_t)tl.k * p.n_edge + ds.edge) * n + a) * n, p.L + ((size_t)crow * p.Ev + tl.ev) * p.NP, n, u, err);
+  nst[crow * 64 + lane] = (uint8_t)e;
+  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+}
+
+// grid: (tile, branch) items, tile fastest; a workgroup is one wave
+template <int MODE>
+__global__ __launch_bounds__(SW_BRANCH_BLOCK) void sw_branch_kernel(SwParams p) {
+  extern __shared__ __align__(16) double sw_lds[];                   // B of the item's model, rows n | 1 apart
+  __shared__ __align__(16) double s_ltab[2 * PHM_LOGTAB_N];          // (1/c_j, log c_j) of the exponential variates (neglog_u32)
+  const int lane = threadIdx.x;
+  for (int i = lane; i < 2 * PHM_LOGTAB_N; i += SW_BRANCH_BLOCK) s_ltab[i] = logtab_entry(i);
+  const int n = p.n, nn = n * n, LD = sw_row_stride(n);
+  const int NT = p.n_tips + p.n_node;
+  const int64_t item = blockIdx.x;
+  const int tile = (int)(item % p.n_tiles);
+  const DownStep ds = p.down[(int)(item / p.n_tiles)];
+  const SmTile tl = p.tiles[tile];
+  const size_t npad = (size_t)p.n_tiles * 64;
+  const bool valid = lane < tl.n_valid;
+  const uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+  const double mu = p.mu[tl.k];
+  const int depth = p.depth_of[tl.k];
+  const double* __restrict__ Bk = p.B + (size_t)tl.k * nn;
+  const double* __restrict__ bt = p.beta + (size_t)tl.k * p.tab_stride;
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  const int b = ds.edge;
+  const int crow = ds.child >= 0 ? p.n_tips + ds.child : ~ds.child;
+  const int a = nst[(p.n_tips + ds.parent) * 64 + lane];
+  const int e = nst[crow * 64 + lane];
+  const double tb = p.t[b];
+  const double x = mu * tb;                                          // wave-uniform
+  uint32_t err = 0;
+  StatLanes<0, 0> st;
+  st.begin(p.dwfx, p.cnt, npad, (size_t)tile * 64 + lane, p.fx_scale, valid);
+  MapRow<MODE> mr;                                                   // a lane without a live history: an empty row, no count stored
+  mr.begin(p.maps, (tl.row0 + lane) * p.n_edge + b, valid);
+  auto segment = [&](int col, double v) { st.dwell(col, v); mr.emit(v, col); };
+  auto count = [&](int from, int to) { st.count(from * (n - 1) + (to > from ? to - 1 : to)); };
+  int N = 0;
+  Stream sr;
+  sr.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
+  if (x > 0.0) {
+    const double* __restrict__ ba = bt + (size_t)e * n + a;          // beta_m[a, e] at ba[m nn]
+    // first pass: the stopping index and the series' own total
+    double r = 1.0, Sp = 1.0, Sa = ba[0];
+    int R = 0, M = 0;
+    for (int m = 1;; ++m) {
+      const double rn = r * (x / (double)m);
+      if (m >= 2 && x < (double)m && rn <= 0x1p-60 * Sp * (1.0 - x / (double)(m + 1))) break;
+      if (m > depth) { err |= DERR_CAPACITY; break; }                // never with the host's depth: M is monotone in x
+      r = rn;
+      Sp += r;
+      Sa += r * ba[(size_t)m * nn];
+      M = m;
+      if (r > 0x1p512) { r *= 0x1p-512; Sp *= 0x1p-512; Sa *= 0x1p-512; ++R; }
+    }
+    if (!(Sa > 0.0) || isinf(Sa)) err |= DERR_ZERO_PROB;
+    const double thr = sr.draw(0) * Sa;
+    // second pass: the first m whose partial sum reaches the threshold
+    double cum = ba[0];
+    int rho = 0;
+    r = 1.0;
+    if (!(thr <= ldexp(cum, -512 * R))) {
+      N = M;
+      for (int m = 1; m <= M; ++m) {
+        r = r * (x / (double)m);
+        cum += r * ba[(size_t)m * nn];
+        if (r > 0x1p512) { r *= 0x1p-512; cum *= 0x1p-512; ++rho; }
+        if (thr <= ldexp(cum, -512 * (R - rho))) { N = m; break; }
+      }
+    }
+  }
+  if (__any(N >= 2)) {                                               // only then is a state drawn from B
+    for (int i = lane; i < nn; i += SW_BRANCH_BLOCK) {
+      const int row = i / n;
+      sw_lds[row * LD + (i - row * n)] = Bk[i];
+    }
+  }
+  __syncthreads();                                                   // the neglog table and B are staged
+  if (N > 0) {
+    // jump times: G = E_1 + .. + E_{N+1}, then the walk takes the same draws again
+    double G = 0.0;
+    for (int i = 1; i <= N + 1; ++i) G += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
+    Stream su;
+    su.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
+    int prev = a, sprev = a;
+    double tprev = 0.0, c = 0.0;
+    for (int i = 1; i <= N; ++i) {
+      c += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
+      int di = e;
+      if (i < N) {
+        const double u = su.draw((uint32_t)(N + 1 + i));
+        di = sw_draw(sw_lds + prev * LD, bt + ((size_t)(N - i) * nn + (size_t)e * n), n, u, err);
+      }
+      if (prev != di) {
+        const double ti = tb * (c / G);
+        segment(sprev, ti - tprev);
+        count(sprev, di);
+        tprev = ti; sprev = di;
+      }
+      prev = di;
+    }
+    segment(sprev, tb - tprev);
+  } else {
+    segment(a, tb);                                                  // no jump, mu = 0 or t = 0: the parent's state for the whole branch
+  }
+  if (valid) mr.end((size_t)b * p.map_pad + (size_t)(tl.row0 + lane));
+  if (err && valid) atomicOr(p.err, err);
+}
+
+__global__ __launch_bounds__(256) void sw_finish_kernel(SwParams p) {
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = p.n, cols = n + n * (n - 1);
+  const int64_t npad = (int64_t)p.n_tiles * 64;
+  const int NT = p.n_tips + p.n_node;
+  if (gid < cols * npad) {
+    const int c = (int)(gid / npad);
+    const int64_t it = gid % npad;
+    p.out[gid] = stat_cell_value(p.dwfx, p.cnt, n, c, (size_t)npad, (size_t)it, p.fx_inv);
+  }
+  if (p.nodes) {
+    for (int64_t cell = gid; cell < npad * NT; cell += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t it = cell / NT;
+      const int row = (int)(cell % NT);
+      p.nodes[cell] = (int32_t)p.nstate[((size_t)(it >> 6) * NT + row) * 64 + (it & 63)] + 1;
+    }
+  }
+}
+
+inline bool sw_ok(const SwParams& p) {
+  return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.n_edge >= 1;
+}
+
+}  // namespace
+
+hipError_t launch_sw_table(const SwParams& p, hipStream_t stream) {
+  if (!sw_ok(p) || !p.Q || !p.mu || !p.B || !p.beta || !p.depth_of || p.tab_stride < sw_table_doubles(p.n, 0)) return hipErrorInvalidValue;
+  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(sw_table_kernel), (int)sw_table_lds_bytes(EX_MAX_STATES));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sw_table_kernel, dim3(p.Kc), dim3(SW_TABLE_BLOCK), sw_table_lds_bytes(p.n), stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_sw_sample(const SwParams& p, const std::vector<int32_t>& level_off, int maps_mode, hipStream_t stream) {
+  if (!sw_ok(p) || p.n_tiles <= 0 || (int64_t)p.n_edge * p.n_tiles > SW_ITEMS_MAX) return hipErrorInvalidValue;
+  constexpr int W = SW_NODE_BLOCK / 64;
+  hipLaunchKernelGGL(sw_root_kernel, dim3((p.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
+  for (size_t l = 0; l + 1 < level_off.size(); ++l) {
+    const int64_t cnt = level_off[l + 1] - level_off[l];
+    if (cnt <= 0) continue;
+    const dim3 grid((unsigned)((cnt * p.n_tiles + W - 1) / W));
+    hipLaunchKernelGGL(sw_node_kernel, grid, dim3(SW_NODE_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
+  }
+  const dim3 items((unsigned)((int64_t)p.n_edge * p.n_tiles));
+  with_map_mode(maps_mode, [&](auto mode) {
+    constexpr int MODE = decltype(mode)::value;
+    hipLaunchKernelGGL((sw_branch_kernel<MODE>), items, dim3(SW_BRANCH_BLOCK), sw_branch_lds_bytes(p.n), stream, p);
+  });
+  const int n = p.n;
+  const int64_t cells = (int64_t)(n + n * (n - 1)) * p.n_tiles * 64;
+  hipLaunchKernelGGL(sw_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+
+}  // namespace phm
