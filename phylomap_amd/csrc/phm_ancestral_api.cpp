@@ -28,7 +28,7 @@ int32_t an_device(const AnInput& an, int32_t device, int64_t first, int64_t coun
   const int64_t S_eval = in.sites_per_model();
   const double nan = std::numeric_limits<double>::quiet_NaN(), ninf = -std::numeric_limits<double>::infinity();
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   LlLanes ln(in);
   DevBuf ddown, dsel;
   st = ln.upload_tree();
@@ -90,8 +90,7 @@ int32_t an_device(const AnInput& an, int32_t device, int64_t first, int64_t coun
     st = ln.expm(p);
     if (st) return st;
     HIPCHK(tm.stop());
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    HIPCHK(tm.add_to(kernel_ms));
 
     for (int64_t s0 = 0; s0 < S_eval; s0 += pl.Sc_max) {
       const int64_t Sc = std::min<int64_t>(pl.Sc_max, S_eval - s0);
@@ -126,8 +125,7 @@ int32_t an_device(const AnInput& an, int32_t device, int64_t first, int64_t coun
         HIPCHK(hipMemcpy(xh.data(), dx.p, (size_t)NT * Ev, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(jlh.data(), djl.p, sizeof(double) * Ev, hipMemcpyDeviceToHost));
       }
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
       // the output stage: [row][state][Ev] -> [evaluation][node][state]; an impossible evaluation gets NaN / 0 / -inf
       for (int64_t s = 0; s < Sc; ++s) {
         if (marg)                                        // eight models at a time: one cache line of a row feeds eight output rows

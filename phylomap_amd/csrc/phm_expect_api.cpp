@@ -115,7 +115,6 @@ int32_t ex_device_setup(const std::string& fn, const ExInput& in, ExDevice& d, K
   HIPCHK(upload(d.dB, in.B)); HIPCHK(upload(d.dq, in.qoff)); HIPCHK(upload(d.dpid, in.pid)); HIPCHK(upload(d.dobs, in.obs));
   HIPCHK(upload(d.dup, in.up)); HIPCHK(upload(d.ddown, in.down)); HIPCHK(upload(d.dchild, in.child_row));
   HIPCHK(upload(d.dwoff, in.w_off)); HIPCHK(upload(d.dw, in.w));
-  double ms = 0.0;
   HIPCHK(tm.start());
   HIPCHK(phm::launch_expm_pade(in.n, d.dQ.as<double>(), d.dt.as<double>(), d.dsq.as<int32_t>(), E, dwork.as<double>(), d.dP.as<double>(),
                                derr.as<uint32_t>(), nullptr));
@@ -123,8 +122,7 @@ int32_t ex_device_setup(const std::string& fn, const ExInput& in, ExDevice& d, K
   uint32_t derrh = 0;
   HIPCHK(hipMemcpy(&derrh, derr.p, sizeof derrh, hipMemcpyDeviceToHost));
   if (derrh) return fail(PHM_ERR_BAD_INPUT, fn + "singular Pade denominator in expm(Q t_b)");
-  HIPCHK(tm.elapsed(ms));
-  kernel_ms += ms;
+  HIPCHK(tm.add_to(kernel_ms));
   return PHM_OK;
 }
 
@@ -186,9 +184,7 @@ int32_t ex_run_passes(const std::string& fn, const ExInput& in, const ExDevice& 
     if (!std::isfinite(ps.ll_h[k]))
       return fail(PHM_ERR_ZERO_PROB, fn + "site " + std::to_string(site0 + k + 1) + " has probability 0 under Q (its tips are impossible)");
   if (loglik) std::memcpy(loglik + site0, ps.ll_h.data(), sizeof(double) * Sc);
-  double ms = 0.0;
-  HIPCHK(tm.elapsed(ms));
-  kernel_ms += ms;
+  HIPCHK(tm.add_to(kernel_ms));
   return PHM_OK;
 }
 
@@ -209,7 +205,7 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
   const size_t S = (size_t)in.S;
   ExDevice dev;
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   st = ex_device_setup(EX_FN, in, dev, tm, kernel_ms);
   if (st) return st;
 
@@ -257,8 +253,7 @@ int32_t ex_one_device(const ExInput& in, int32_t device, int64_t first, int64_t 
           HIPCHK(hipMemcpy2D(branch_stats + site0 + S * ((size_t)e0 + (size_t)E * col), sizeof(double) * S,
                              dout.as<double>() + (size_t)col * ne * Sp, sizeof(double) * Sp, sizeof(double) * Sc, ne,
                              hipMemcpyDeviceToHost));
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
     }
     HIPCHK(hipMemcpy2D(stats + site0, sizeof(double) * S, dtot.p, sizeof(double) * Sp, sizeof(double) * Sc, cols,
                        hipMemcpyDeviceToHost));

@@ -131,7 +131,7 @@ int32_t tt_one_device(const ExInput& in, const TtPlan& pl, int32_t device, int64
   const size_t nn = (size_t)n * n, S = (size_t)in.S;
   ExDevice dev;
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0, t_along = 0.0, t_branch = 0.0, t_reduce = 0.0;
+  double kernel_ms = 0.0, t_along = 0.0, t_branch = 0.0, t_reduce = 0.0;
   st = ex_device_setup(TT_FN, in, dev, tm, kernel_ms);
   if (st) return st;
   int64_t Sc_max = 0;
@@ -184,16 +184,14 @@ int32_t tt_one_device(const ExInput& in, const TtPlan& pl, int32_t device, int64
                                    dwork.as<double>(), dPi.as<double>(), derr.as<uint32_t>(), nullptr));
       HIPCHK(phm::launch_ex_along(ap, nq, nullptr));
       HIPCHK(tm.stop());
-      HIPCHK(tm.elapsed(ms));
-      t_along += ms;
+      HIPCHK(tm.add_to(t_along));
       if (occupancy && q0 < pl.n_cross) {
         int r0 = 0, r1 = 0;
         tt_ranges(pl.cross_off, q0, q0 + nq, r0, r1);
         HIPCHK(tm.start());
         HIPCHK(phm::launch_ex_range_sum(dpost.as<double>(), n, nq, q0, dcoff.as<int64_t>(), r0, r1, K, Sp, docc.as<double>(), nullptr));
         HIPCHK(tm.stop());
-        HIPCHK(tm.elapsed(ms));
-        t_reduce += ms;
+        HIPCHK(tm.add_to(t_reduce));
       }
       if (point_post && q0 + nq > pl.n_cross) {                  // [state][q - q0][Sp] -> site + S (point + n_points state)
         const int64_t a0 = std::max(q0, pl.n_cross);
@@ -226,21 +224,18 @@ int32_t tt_one_device(const ExInput& in, const TtPlan& pl, int32_t device, int64
         HIPCHK(hipMemcpyAsync(dsbe.as<double>() + (size_t)nk * Sp, pp.sL + (size_t)(in.T + in.sched.root) * Sp, sizeof(double) * Sp,
                               hipMemcpyDeviceToDevice, nullptr));
         HIPCHK(tm.stop());
-        HIPCHK(tm.elapsed(ms));
-        t_along += ms;
+        HIPCHK(tm.add_to(t_along));
         bp.w_off = dswoff.as<int64_t>() + k0; bp.root = nk; bp.n_out_edges = nk;
         HIPCHK(tm.start());
         HIPCHK(phm::launch_ex_branch(bp, nk, nullptr));
         HIPCHK(tm.stop());
-        HIPCHK(tm.elapsed(ms));
-        t_branch += ms;
+        HIPCHK(tm.add_to(t_branch));
         int r0 = 0, r1 = 0;
         tt_ranges(pl.bin_off, k0, k0 + nk, r0, r1);
         HIPCHK(tm.start());
         HIPCHK(phm::launch_ex_range_sum(dout.as<double>(), cols, nk, k0, dboff.as<int64_t>(), r0, r1, NB, Sp, dtot.as<double>(), nullptr));
         HIPCHK(tm.stop());
-        HIPCHK(tm.elapsed(ms));
-        t_reduce += ms;
+        HIPCHK(tm.add_to(t_reduce));
       }
       HIPCHK(hipMemcpy2D(bin_stats + site0, sizeof(double) * S, dtot.p, sizeof(double) * Sp, sizeof(double) * Sc, (size_t)cols * NB,
                          hipMemcpyDeviceToHost));

@@ -6,8 +6,7 @@
 // allocated once; per iteration there is one upload (Q) and one download (statistics, log-likelihoods and the error word).
 // Every random number is addressed by global indices only: histories by (site * C + chain, iteration + replica_offset) as
 // phm_sample_histories_models with draws = 1 addresses them, rates by (ENT_RATE | parameter, chain, iteration + replica_offset).
-#include "phm_loglik_host.h"
-#include "phm_sample.h"
+#include "phm_sample_host.h"
 
 #include <limits>
 
@@ -61,7 +60,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   const int64_t S_eval = in.sites_per_model();           // sites per chain
   const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   using Clock = std::chrono::steady_clock;
   const bool q_timing = g_phm_debug.q_timing != 0;      // host clock of the phases of an iteration, printed to stderr
   double up_ms = 0.0, run_ms = 0.0, host_ms = 0.0;
@@ -114,13 +113,12 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
 
   phm::SmParams sp = {};
   phm::LlParams& p = sp.ll;
-  sp.n_node = in.Nn; sp.n_edge = E; sp.root_row = T + in.sched.root;
-  sp.seed_lo = (uint32_t)(g.opt.seed & 0xFFFFFFFFull); sp.seed_hi = (uint32_t)(g.opt.seed >> 32);
-  sp.fx_scale = std::ldexp(1.0, 61 - g.fx_exp); sp.fx_inv = std::ldexp(1.0, g.fx_exp - 61);
-  sp.tiles = dtile.as<phm::SmTile>(); sp.down = ddown.as<phm::DownStep>(); sp.order = dorder.as<int32_t>();
+  phm::SmCore& sc = sp.core;
+  sm_fill_core(sc, in, g.opt, g.fx_exp);                 // replica: the iteration's, below
+  sc.tiles = dtile.as<phm::SmTile>(); sc.down = ddown.as<phm::DownStep>(); sc.order = dorder.as<int32_t>();
+  sc.nstate = dnst.as<uint8_t>(); sc.dwfx = ddw.as<unsigned long long>(); sc.cnt = dcnt.as<uint32_t>();
+  sc.out = dout.as<double>(); sc.nodes = nullptr; sc.err = derr.as<uint32_t>();
   sp.mu = dmu.as<double>(); sp.B = dB.as<double>(); sp.beta = dbeta.as<double>(); sp.depth_of = ddepth.as<int32_t>();
-  sp.nstate = dnst.as<uint8_t>(); sp.dwfx = ddw.as<unsigned long long>(); sp.cnt = dcnt.as<uint32_t>();
-  sp.out = dout.as<double>(); sp.nodes = nullptr; sp.err = derr.as<uint32_t>();
   sp.packed = 1; sp.t_max = g.t_max; sp.depth = g.depth; sp.lane_id = dlane.as<uint32_t>();
 
   for (int64_t c0 = 0; c0 < count; c0 += Kc_max) {
@@ -154,7 +152,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
     HIPCHK(hipMemset(ddw.p, 0, sizeof(unsigned long long) * n * npad));
     HIPCHK(hipMemset(dcnt.p, 0, sizeof(uint32_t) * (size_t)n * (n - 1) * npad));
     p = ln.params();
-    sp.n_tiles = nt;
+    sc.n_tiles = nt;
     const int branch_blocks = (int)std::min<int64_t>(((int64_t)E * nt + 3) / 4, 2048);
     const size_t out_n = (size_t)(cols + 1) * npad + 1;
 
@@ -212,7 +210,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
     const int n_threads = (int)std::max<int64_t>(1, std::min<int64_t>(16, Kc * np / 4096));
 
     for (int iter = 0; iter < g.iters; ++iter) {
-      sp.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
+      sc.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
       Clock::time_point t0 = Clock::now();
       HIPCHK(hipMemcpy(ln.dQ.p, Qh, sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
       up_ms += since(t0);
@@ -228,8 +226,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
       HIPCHK(phm::launch_sm_sample(sp, g.level_off, branch_blocks, phm::MAPS_OFF, nullptr));
       HIPCHK(tm.stop());
       HIPCHK(hipMemcpy(hout.p, dout.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
       run_ms += since(t0);
       t0 = Clock::now();
       const uint32_t derrh = (uint32_t)outh[out_n - 1];

@@ -95,6 +95,7 @@ struct KernelTimer {
     if (e == hipSuccess) ms = f;
     return e;
   }
+  hipError_t add_to(double& sum) { double ms = 0.0; const hipError_t e = elapsed(ms); sum += ms; return e; }   // sum += start .. stop
 };
 
 // page-locked host staging (async copies of a few KB between sweeps: a pageable hipMemcpy costs a synchronous ~15-30 us each)

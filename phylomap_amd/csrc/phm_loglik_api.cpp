@@ -21,7 +21,7 @@ int32_t ll_lanes_device(const LlInput& in, int32_t device, int64_t first, int64_
   if (st) return st;
   const int64_t S_eval = in.sites_per_model();
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   LlLanes ln(in);
   st = ln.upload_tree();
   if (st) return st;
@@ -40,8 +40,7 @@ int32_t ll_lanes_device(const LlInput& in, int32_t device, int64_t first, int64_
     st = ln.expm(p);
     if (st) return st;
     HIPCHK(tm.stop());
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    HIPCHK(tm.add_to(kernel_ms));
 
     for (int64_t s0 = 0; s0 < S_eval; s0 += pl.Sc_max) {
       const int64_t Sc = std::min<int64_t>(pl.Sc_max, S_eval - s0);
@@ -54,8 +53,7 @@ int32_t ll_lanes_device(const LlInput& in, int32_t device, int64_t first, int64_
       HIPCHK(tm.stop());
       st = ln.fetch_ll(Sc);
       if (st) return st;
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
       for (int64_t s = 0; s < Sc; ++s)
         for (int64_t k = 0; k < Kc; ++k) out[ll_eval_of(in, s0 + s, ln.m0 + k)] = ln.llh[(size_t)s * ln.Kp + k];
     }
@@ -84,7 +82,7 @@ int32_t ll_wide_device(const LlInput& in, int32_t device, int64_t first, int64_t
   st = ps.alloc(ex, (size_t)Sc_max);
   if (st) return st;
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   for (int64_t m = first; m < first + count; ++m) {
     ex.Qr.assign(in.Qr.begin() + (size_t)m * nn, in.Qr.begin() + (size_t)(m + 1) * nn);
     ex.pid.assign(in.pid.begin() + (size_t)m * n, in.pid.begin() + (size_t)(m + 1) * n);
@@ -114,8 +112,7 @@ int32_t ll_wide_device(const LlInput& in, int32_t device, int64_t first, int64_t
       HIPCHK(phm::launch_ex_root(pp, T + ex.sched.root, dev.dpid.as<double>(), nullptr));
       HIPCHK(tm.stop());
       HIPCHK(hipMemcpy(ps.ll_h.data(), ps.dll.p, sizeof(double) * Sc, hipMemcpyDeviceToHost));
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
       for (int64_t s = 0; s < Sc; ++s) out[ll_eval_of(in, s0 + s, m)] = std::isfinite(ps.ll_h[s]) ? ps.ll_h[s] : ninf;
     }
   }

@@ -48,24 +48,17 @@ __host__ __device__ inline int sm_stop_index(double x) {
   return SM_M_CAP;
 }
 
-struct SmParams {
-  LlParams ll;                                 // section 17's buffers, read in place: P [edge][n n][Kp], L [row][n][Ev], pid [n][Kp]
+// What the narrow and the wide sampler's parameter blocks share: the tiles of a launch, the streams, the accumulators and the
+// outputs (filled on the host by SmTiles::fill_core, phm_sample_host.h).
+struct SmCore {
   int32_t n_node, n_edge, root_row;            // root_row: n_tips + internal index of the root
   int32_t n_tiles;
-  int32_t depth;                               // rows of beta: m = 0 .. depth
-  int32_t* depth_of;                           // [Kp] every model's own depth M(mu_k max_b t_b) <= depth (packed: written by the table kernel)
-  int32_t packed;                              // 1: lane = chain (phm_gibbs_rates); a lane whose ll is not finite, or whose id is SM_LANE_IDLE, idles
-  double t_max;                                // packed: max_b t_b, from which the table kernel takes depth_of (DERR_CAPACITY above depth)
-  const uint32_t* lane_id;                     // packed: [n_tiles * 64] GLOBAL evaluation ids
   int64_t map_pad;                             // MAPS_COUNT: row length of maps.seg_cnt (histories of the shard, padded)
   uint32_t seed_lo, seed_hi, replica;          // replica: phm_options.replica_offset, added to the draw index
   double fx_scale, fx_inv;                     // fixed-point scale of the dwell accumulators (powers of two)
   const SmTile* tiles;                         // [n_tiles]
   const DownStep* down;                        // [n_edge] pre-order
   const int32_t* order;                        // positions into down[], grouped by the depth of the parent
-  double* mu;                                  // [Kp]
-  double* B;                                   // [n n][Kp] I + Q / mu (I when mu = 0)
-  double* beta;                                // [depth + 1][n n][Kp]: entry c n + e of row m is (B^m)[c, e]
   uint8_t* nstate;                             // [tile][n_tips + n_node][64] 0-based states by ape row
   unsigned long long* dwfx;                    // [n][n_tiles * 64] dwell sums, fixed point
   uint32_t* cnt;                               // [n (n-1)][n_tiles * 64]
@@ -74,6 +67,24 @@ struct SmParams {
   uint32_t* err;
   MapsDev maps;
 };
+
+struct SmParams {
+  LlParams ll;                                 // section 17's buffers, read in place: P [edge][n n][Kp], L [row][n][Ev], pid [n][Kp]
+  SmCore core;
+  int32_t depth;                               // rows of beta: m = 0 .. depth
+  int32_t* depth_of;                           // [Kp] every model's own depth M(mu_k max_b t_b) <= depth (packed: written by the table kernel)
+  int32_t packed;                              // 1: lane = chain (phm_gibbs_rates); a lane whose ll is not finite, or whose id is SM_LANE_IDLE, idles
+  double t_max;                                // packed: max_b t_b, from which the table kernel takes depth_of (DERR_CAPACITY above depth)
+  const uint32_t* lane_id;                     // packed: [n_tiles * 64] GLOBAL evaluation ids
+  double* mu;                                  // [Kp]
+  double* B;                                   // [n n][Kp] I + Q / mu (I when mu = 0)
+  double* beta;                                // [depth + 1][n n][Kp]: entry c n + e of row m is (B^m)[c, e]
+};
+
+// fixed point -> double, counters -> double, node bytes -> 1-based int32 of the tiles of c (n states, n_tips tips), for both
+// samplers.  packed_ll non-NULL (the narrow packed form only): the accumulators are zeroed for the next iteration, and the lanes'
+// ll (packed_ll[tile.ev + lane]) and the error word ride along in c.out.
+hipError_t launch_sm_finish(const SmCore& c, int n, int n_tips, const double* packed_ll, hipStream_t stream);
 
 // mu, B and beta of the models of the chunk (a lane owns a model), each to its own depth
 hipError_t launch_sm_table(const SmParams& p, hipStream_t stream);

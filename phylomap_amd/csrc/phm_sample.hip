@@ -17,6 +17,8 @@
 //   states       x_i drawn with weights B[x_{i-1}, c] beta_{N-i}[c]; equal neighbours merge.
 // Draw d of a branch stream: 0 the jump count, 1 .. N + 1 the exponentials, N + 1 + i the state x_i.
 // Segments, counts and dwell sums are exp_tiles_branch_kernel's (64-bit fixed point; maps modes of phm_maps.h).
+// The draw of a branch itself (sm_draw, sm_jump_count, sm_walk) is in phm_sample_branch.h (section 19a), shared with
+// phm_sample_wide.hip; the finish kernel here serves both samplers.
 //
 // Packed form (PACKED = true, DESIGN.md section 20, behind phm_gibbs_rates): one draw per evaluation, so lane = chain.  A tile is 64
 // consecutive chains of one site; the model, the evaluation, its id, mu, the table depth and the beta column are per lane
@@ -26,8 +28,8 @@
 
 #include <algorithm>
 
-#include "phm_device.h"
 #include "phm_history.h"
+#include "phm_sample_branch.h"
 
 namespace phm {
 
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_table_kernel(SmParams p) {
   int depth;
   if (p.packed) {                                                   // the chain's own depth, from the rates it has now
     depth = sm_stop_index(mu * p.t_max);
-    if (depth > p.depth) { atomicOr(p.err, DERR_CAPACITY); depth = p.depth; }
+    if (depth > p.depth) { atomicOr(p.core.err, DERR_CAPACITY); depth = p.depth; }
     p.depth_of[k] = depth;
   } else {
     depth = min(p.depth_of[k], p.depth);
@@ -65,27 +67,6 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_table_kernel(SmParams p) {
         for (int j = 1; j < n; ++j) acc += p.B[(size_t)(c * n + j) * Kp + k] * prev[(size_t)(j * n + e) * Kp];
         next[(size_t)(c * n + e) * Kp] = acc;
       }
-  }
-}
-
-// first j with u * sum(w) <= w_0 + .. + w_j, w_c = a[c sa] * b[c sb], sums left to right (section 2's rule)
-template <int NS>
-__device__ __forceinline__ int sm_draw(const double* __restrict__ a, size_t sa, const double* __restrict__ b, size_t sb, int n,
-                                       double u, uint32_t& err) {
-  if constexpr (NS > 0) {
-    double w[NS];
-#pragma unroll
-    for (int c = 0; c < NS; ++c) w[c] = a[c * sa] * b[c * sb];
-    return sample_cat<NS>(w, u, err);
-  } else {
-    double total = a[0] * b[0];
-    for (int c = 1; c < n; ++c) total += a[c * sa] * b[c * sb];
-    if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
-    const double thr = u * total;
-    double cum = a[0] * b[0];
-    int idx = (thr <= cum) ? 0 : 1;
-    for (int c = 1; c < n - 1; ++c) { cum += a[c * sa] * b[c * sb]; idx += (thr <= cum) ? 0 : 1; }
-    return idx;
   }
 }
 
@@ -113,13 +94,13 @@ __device__ __forceinline__ SmLane sm_lane(const SmParams& p, const SmTile& tl, i
     l.k = tl.k + lane;
     l.ev = tl.ev + lane;
     l.eval_id = p.lane_id[(size_t)tile * 64 + lane];
-    l.rep = p.replica;
+    l.rep = p.core.replica;
     l.valid = l.eval_id != SM_LANE_IDLE && isfinite(p.ll.ll[l.ev]);
   } else {
     l.k = tl.k;
     l.ev = tl.ev;
     l.eval_id = tl.eval_id;
-    l.rep = (uint32_t)(tl.d0 + lane) + p.replica;
+    l.rep = (uint32_t)(tl.d0 + lane) + p.core.replica;
     l.valid = lane < tl.n_valid;
   }
   return l;
@@ -130,19 +111,19 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_root_kernel(SmParams p) {
   const LlParams& q = p.ll;
   const int lane = threadIdx.x & 63;
   const int tile = blockIdx.x * (SM_BLOCK / 64) + (threadIdx.x >> 6);
-  if (tile >= p.n_tiles) return;
-  const SmTile tl = p.tiles[tile];
+  if (tile >= p.core.n_tiles) return;
+  const SmTile tl = p.core.tiles[tile];
   const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp;
-  const int NT = q.n_tips + p.n_node;
+  const int NT = q.n_tips + p.core.n_node;
   const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
   uint32_t err = 0;
   int s = 0;
   if (!PACKED || l.valid) {
-    const double u = stream_u(p.seed_lo, p.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)p.root_row, 0);
-    s = sm_draw_n<0>(q.pid + l.k, Kp, q.L + (size_t)p.root_row * q.n * Ev + l.ev, Ev, q.n, u, err);
+    const double u = stream_u(p.core.seed_lo, p.core.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)p.core.root_row, 0);
+    s = sm_draw_n<0>(q.pid + l.k, Kp, q.L + (size_t)p.core.root_row * q.n * Ev + l.ev, Ev, q.n, u, err);
   }
-  p.nstate[((size_t)tile * NT + p.root_row) * 64 + lane] = (uint8_t)s;
-  if (err && l.valid) atomicOr(p.err, err);
+  p.core.nstate[((size_t)tile * NT + p.core.root_row) * 64 + lane] = (uint8_t)s;
+  if (err && l.valid) atomicOr(p.core.err, err);
 }
 
 // one depth level: a wave per (tile, edge of the level) draws the child's state, tips included
@@ -152,169 +133,116 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_node_kernel(SmParams p, int begin
   const int lane = threadIdx.x & 63;
   const int64_t item = (int64_t)blockIdx.x * (SM_BLOCK / 64) + (threadIdx.x >> 6);
   const int n_lvl = end - begin;
-  if (item >= (int64_t)n_lvl * p.n_tiles) return;
+  if (item >= (int64_t)n_lvl * p.core.n_tiles) return;
   const int n = q.n;
   const int tile = (int)(item / n_lvl);
-  const DownStep ds = p.down[p.order[begin + (int)(item % n_lvl)]];
-  const SmTile tl = p.tiles[tile];
+  const DownStep ds = p.core.down[p.core.order[begin + (int)(item % n_lvl)]];
+  const SmTile tl = p.core.tiles[tile];
   const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp;
-  const int NT = q.n_tips + p.n_node;
+  const int NT = q.n_tips + p.core.n_node;
   const int crow = ds.child >= 0 ? q.n_tips + ds.child : ~ds.child;
-  uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+  uint8_t* __restrict__ nst = p.core.nstate + (size_t)tile * NT * 64;
   const int a = nst[(q.n_tips + ds.parent) * 64 + lane];
   const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
   uint32_t err = 0;
   int e = 0;
   if (!PACKED || l.valid) {
-    const double u = stream_u(p.seed_lo, p.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)crow, 0);
+    const double u = stream_u(p.core.seed_lo, p.core.seed_hi, l.rep, l.eval_id, ENT_NODE | (uint32_t)crow, 0);
     e = sm_draw_n<0>(q.P + ((size_t)ds.edge * n * n + (size_t)a * n) * Kp + l.k, Kp, q.L + (size_t)crow * n * Ev + l.ev, Ev, n, u, err);
   }
   nst[crow * 64 + lane] = (uint8_t)e;
-  if (err && l.valid) atomicOr(p.err, err);
+  if (err && l.valid) atomicOr(p.core.err, err);
 }
 
-// persistent waves over (tile, group of `group` consecutive branches in pre-order)
+// persistent waves over (tile, group of `group` consecutive branches in pre-order); the branch draw is phm_sample_branch.h's
 template <int NS, int MODE, bool PACKED = false>
 __global__ __launch_bounds__(SM_BLOCK) void sm_branch_kernel(SmParams p, int group) {
   __shared__ __align__(16) double s_ltab[2 * PHM_LOGTAB_N];        // (1/c_j, log c_j) of the exponential variates (neglog_u32)
   for (int i = threadIdx.x; i < 2 * PHM_LOGTAB_N; i += SM_BLOCK) s_ltab[i] = logtab_entry(i);
   __syncthreads();
   const LlParams& q = p.ll;
+  const SmCore& sc = p.core;
   const int lane = threadIdx.x & 63;
   const int wslot = blockIdx.x * (SM_BLOCK / 64) + (threadIdx.x >> 6);
   const int n = NS > 0 ? NS : q.n;
   const int nn = n * n;
   const size_t Kp = q.Kp;
-  const int NT = q.n_tips + p.n_node;
-  const int n_groups = (p.n_edge + group - 1) / group;
-  const int64_t items = (int64_t)n_groups * p.n_tiles;
-  const size_t npad = (size_t)p.n_tiles * 64;
+  const int NT = q.n_tips + sc.n_node;
+  const int n_groups = (sc.n_edge + group - 1) / group;
+  const int64_t items = (int64_t)n_groups * sc.n_tiles;
+  const size_t npad = (size_t)sc.n_tiles * 64;
   uint32_t err = 0;
   for (int64_t item = wslot; item < items; item += (int64_t)gridDim.x * (SM_BLOCK / 64)) {
-    const int tile = (int)(item % p.n_tiles);
-    const int q0 = (int)(item / p.n_tiles) * group, q1 = min(q0 + group, p.n_edge);
-    const SmTile tl = p.tiles[tile];
+    const int tile = (int)(item % sc.n_tiles);
+    const int q0 = (int)(item / sc.n_tiles) * group, q1 = min(q0 + group, sc.n_edge);
+    const SmTile tl = sc.tiles[tile];
     const size_t it = (size_t)tile * 64 + lane;
     const SmLane l = sm_lane<PACKED>(p, tl, tile, lane);
     const bool valid = l.valid;
-    const uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+    const uint8_t* __restrict__ nst = sc.nstate + (size_t)tile * NT * 64;
     const double mu = p.mu[l.k];
     const int depth = min(p.depth_of[l.k], p.depth);
-    const double* __restrict__ Bk = p.B + l.k;
-    const double* __restrict__ bt = p.beta + l.k;
-    const uint32_t rep = l.rep;
+    // model-fastest: B[c, j] at (c n + j) Kp + k, (B^m)[c, e] at (m nn + c n + e) Kp + k
+    const SmTable<size_t> tab = {p.B + l.k, (size_t)n * Kp, Kp, p.beta + l.k, (size_t)nn * Kp, (size_t)n * Kp, Kp};
     StatLanes<NS, NS * (NS - 1)> st;
-    st.begin(p.dwfx, p.cnt, npad, it, p.fx_scale, valid);
+    st.begin(sc.dwfx, sc.cnt, npad, it, sc.fx_scale, valid);
     auto count = [&](int from, int to) { st.count(from * (n - 1) + (to > from ? to - 1 : to)); };
     for (int qi = q0; qi < q1; ++qi) {
-      const DownStep ds = p.down[qi];
+      const DownStep ds = sc.down[qi];
       const int b = ds.edge;
       const int crow = ds.child >= 0 ? q.n_tips + ds.child : ~ds.child;
       const int a = nst[(q.n_tips + ds.parent) * 64 + lane];
       const int e = nst[crow * 64 + lane];
       const double tb = q.t[b];
       MapRow<MODE> mr;                                             // a lane without a live history: an empty row, no count stored
-      mr.begin(p.maps, (tl.row0 + lane) * p.n_edge + b, valid);
+      mr.begin(sc.maps, (tl.row0 + lane) * sc.n_edge + b, valid);
       auto segment = [&](int col, double v) { st.dwell(col, v); mr.emit(v, col); };
       const double x = (!PACKED || valid) ? mu * tb : 0.0;         // packed: a lane without a live chain walks no series
-      int N = 0;
-      if (x > 0.0) {
-        const double* __restrict__ ba = bt + (size_t)(a * n + e) * Kp;       // beta_m[a] at ba[m nn Kp]
-        // first pass: the stopping index and the series' own total
-        double r = 1.0, Sp = 1.0, Sa = ba[0];
-        int R = 0, M = 0;
-        for (int m = 1;; ++m) {
-          const double rn = r * (x / (double)m);
-          if (m >= 2 && x < (double)m && rn <= 0x1p-60 * Sp * (1.0 - x / (double)(m + 1))) break;
-          if (m > depth) { err |= DERR_CAPACITY; break; }            // never with the host's depth: M is monotone in x
-          r = rn;
-          Sp += r;
-          Sa += r * ba[(size_t)m * nn * Kp];
-          M = m;
-          if (r > 0x1p512) { r *= 0x1p-512; Sp *= 0x1p-512; Sa *= 0x1p-512; ++R; }
-        }
-        if (!(Sa > 0.0) || isinf(Sa)) err |= DERR_ZERO_PROB;
-        Stream sr;
-        sr.open(ENT_BUNIF | (uint32_t)b, l.eval_id, rep, p.seed_lo, p.seed_hi);
-        const double thr = sr.draw(0) * Sa;
-        // second pass: the first m whose partial sum reaches the threshold
-        double cum = ba[0];
-        int rho = 0;
-        r = 1.0;
-        if (!(thr <= ldexp(cum, -512 * R))) {
-          N = M;
-          for (int m = 1; m <= M; ++m) {
-            r = r * (x / (double)m);
-            cum += r * ba[(size_t)m * nn * Kp];
-            if (r > 0x1p512) { r *= 0x1p-512; cum *= 0x1p-512; ++rho; }
-            if (thr <= ldexp(cum, -512 * (R - rho))) { N = m; break; }
-          }
-        }
-        if (N > 0) {
-          // jump times: G = E_1 + .. + E_{N+1}, then the walk takes the same draws again
-          double G = 0.0;
-          for (int i = 1; i <= N + 1; ++i) G += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
-          Stream su;
-          su.open(ENT_BUNIF | (uint32_t)b, l.eval_id, rep, p.seed_lo, p.seed_hi);
-          int prev = a, sprev = a;
-          double tprev = 0.0, c = 0.0;
-          for (int i = 1; i <= N; ++i) {
-            c += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
-            int di = e;
-            if (i < N) {
-              const double u = su.draw((uint32_t)(N + 1 + i));
-              di = sm_draw<NS>(Bk + (size_t)(prev * n) * Kp, Kp, bt + ((size_t)(N - i) * nn + e) * Kp, (size_t)n * Kp, n, u, err);
-            }
-            if (prev != di) {
-              const double ti = tb * (c / G);
-              segment(sprev, ti - tprev);
-              count(sprev, di);
-              tprev = ti; sprev = di;
-            }
-            prev = di;
-          }
-          segment(sprev, tb - tprev);
-        } else {
-          segment(a, tb);
-        }
-      } else {
-        segment(a, tb);                                              // mu = 0 or t = 0: the parent's state for the whole branch
-      }
-      if (valid) mr.end((size_t)b * p.map_pad + (size_t)(tl.row0 + lane));
+      Stream sr;
+      sr.open(ENT_BUNIF | (uint32_t)b, l.eval_id, l.rep, sc.seed_lo, sc.seed_hi);
+      const int N = x > 0.0 ? sm_jump_count(tab, a, e, x, depth, sr, err) : 0;     // mu = 0 or t = 0: no jump
+      sm_walk<NS>(tab, n, a, e, tb, N, sr, s_ltab, err, segment, count);
+      if (valid) mr.end((size_t)b * sc.map_pad + (size_t)(tl.row0 + lane));
     }
     st.flush();
   }
-  if (err) atomicOr(p.err, err);
+  if (err) atomicOr(sc.err, err);
 }
 
-__global__ __launch_bounds__(256) void sm_finish_kernel(SmParams p) {
+__global__ __launch_bounds__(256) void sm_finish_kernel(SmCore sc, int n, int n_tips, const double* packed_ll) {
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = p.ll.n, cols = n + n * (n - 1);
-  const int64_t npad = (int64_t)p.n_tiles * 64;
-  const int NT = p.ll.n_tips + p.n_node;
+  const int cols = n + n * (n - 1);
+  const int64_t npad = (int64_t)sc.n_tiles * 64;
+  const int NT = n_tips + sc.n_node;
   if (gid < cols * npad) {
     const int c = (int)(gid / npad);
     const int64_t it = gid % npad;
-    p.out[gid] = stat_cell_value(p.dwfx, p.cnt, n, c, (size_t)npad, (size_t)it, p.fx_inv);
-    if (p.packed) {                                                  // the next iteration accumulates from zero
-      if (c < n) p.dwfx[(size_t)c * npad + it] = 0ull;
-      else p.cnt[(size_t)(c - n) * npad + it] = 0u;
+    sc.out[gid] = stat_cell_value(sc.dwfx, sc.cnt, n, c, (size_t)npad, (size_t)it, sc.fx_inv);
+    if (packed_ll) {                                                 // the next iteration accumulates from zero
+      if (c < n) sc.dwfx[(size_t)c * npad + it] = 0ull;
+      else sc.cnt[(size_t)(c - n) * npad + it] = 0u;
     }
   }
-  if (p.packed) {                                                    // one download per iteration: the lanes' ll and the error word ride along
-    if (gid < npad) p.out[(int64_t)cols * npad + gid] = p.ll.ll[p.tiles[gid >> 6].ev + (int)(gid & 63)];
-    if (gid == 0) p.out[(int64_t)(cols + 1) * npad] = (double)*p.err;
+  if (packed_ll) {                                                   // one download per iteration: the lanes' ll and the error word ride along
+    if (gid < npad) sc.out[(int64_t)cols * npad + gid] = packed_ll[sc.tiles[gid >> 6].ev + (int)(gid & 63)];
+    if (gid == 0) sc.out[(int64_t)(cols + 1) * npad] = (double)*sc.err;
   }
-  if (p.nodes) {
+  if (sc.nodes) {
     for (int64_t cell = gid; cell < npad * NT; cell += (int64_t)gridDim.x * blockDim.x) {
       const int64_t it = cell / NT;
       const int row = (int)(cell % NT);
-      p.nodes[cell] = (int32_t)p.nstate[((size_t)(it >> 6) * NT + row) * 64 + (it & 63)] + 1;
+      sc.nodes[cell] = (int32_t)sc.nstate[((size_t)(it >> 6) * NT + row) * 64 + (it & 63)] + 1;
     }
   }
 }
 
 }  // namespace
+
+hipError_t launch_sm_finish(const SmCore& c, int n, int n_tips, const double* packed_ll, hipStream_t stream) {
+  const int64_t cells = (int64_t)(n + n * (n - 1)) * c.n_tiles * 64;
+  hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, c, n, n_tips, packed_ll);
+  return hipGetLastError();
+}
 
 hipError_t launch_sm_table(const SmParams& p, hipStream_t stream) {
   if (p.ll.n < 2 || p.ll.n > LL_LANE_MAX || p.ll.Kp <= 0 || p.ll.Kp % 64 || p.depth < 0) return hipErrorInvalidValue;
@@ -324,30 +252,27 @@ hipError_t launch_sm_table(const SmParams& p, hipStream_t stream) {
 
 hipError_t launch_sm_sample(const SmParams& p, const std::vector<int32_t>& level_off, int branch_blocks, int maps_mode,
                             hipStream_t stream) {
-  if (p.ll.n < 2 || p.ll.n > LL_LANE_MAX || p.n_tiles <= 0 || branch_blocks <= 0) return hipErrorInvalidValue;
-  if (p.packed && (maps_mode != MAPS_OFF || !p.lane_id || p.nodes)) return hipErrorInvalidValue;
+  if (p.ll.n < 2 || p.ll.n > LL_LANE_MAX || p.core.n_tiles <= 0 || branch_blocks <= 0) return hipErrorInvalidValue;
+  if (p.packed && (maps_mode != MAPS_OFF || !p.lane_id || p.core.nodes)) return hipErrorInvalidValue;
   constexpr int W = SM_BLOCK / 64;
-  const dim3 root_grid((p.n_tiles + W - 1) / W);
+  const dim3 root_grid((p.core.n_tiles + W - 1) / W);
   if (p.packed) hipLaunchKernelGGL(sm_root_kernel<true>, root_grid, dim3(SM_BLOCK), 0, stream, p);
   else hipLaunchKernelGGL(sm_root_kernel<false>, root_grid, dim3(SM_BLOCK), 0, stream, p);
   for (size_t l = 0; l + 1 < level_off.size(); ++l) {
     const int64_t cnt = level_off[l + 1] - level_off[l];
     if (cnt <= 0) continue;
-    const dim3 grid((unsigned)((cnt * p.n_tiles + W - 1) / W));
+    const dim3 grid((unsigned)((cnt * p.core.n_tiles + W - 1) / W));
     if (p.packed) hipLaunchKernelGGL(sm_node_kernel<true>, grid, dim3(SM_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
     else hipLaunchKernelGGL(sm_node_kernel<false>, grid, dim3(SM_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
   }
   // branches per wave-item: as many as still leave every SIMD a few waves
-  const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.n_edge * p.n_tiles / 8192));
+  const int group = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)p.core.n_edge * p.core.n_tiles / 8192));
   with_producer_form(maps_mode, p.ll.n, [&](auto mode, auto ns) {      // the packed form has no maps (checked above)
     constexpr int NS = decltype(ns)::value, MODE = decltype(mode)::value;
     if (p.packed) hipLaunchKernelGGL((sm_branch_kernel<NS, MAPS_OFF, true>), dim3(branch_blocks), dim3(SM_BLOCK), 0, stream, p, group);
     else hipLaunchKernelGGL((sm_branch_kernel<NS, MODE, false>), dim3(branch_blocks), dim3(SM_BLOCK), 0, stream, p, group);
   });
-  const int n = p.ll.n;
-  const int64_t cells = (int64_t)(n + n * (n - 1)) * p.n_tiles * 64;
-  hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
-  return hipGetLastError();
+  return launch_sm_finish(p.core, p.ll.n, p.ll.n_tips, p.packed ? p.ll.ll : nullptr, stream);
 }
 
 }  // namespace phm

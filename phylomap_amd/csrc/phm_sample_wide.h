@@ -32,32 +32,20 @@ inline size_t sw_branch_lds_bytes(int n) { return sizeof(double) * (size_t)n * s
 // A tile is phm_sample.h's SmTile: 64 consecutive draws of one evaluation; ev is section 23's index model * Sc + site of the
 // launch and k the model in the chunk.
 struct SwParams {
-  int32_t n, NP, n_tips, n_node, n_edge, root_row;   // root_row: n_tips + internal index of the root
-  int32_t Kc, n_tiles;
+  SmCore core;                                 // phm_sample.h: tiles, streams, accumulators and outputs
+  int32_t n, NP, n_tips;
+  int32_t Kc;
   size_t Ev;                                   // evaluations of the launch (Kc * Sc): row length of L
-  int64_t map_pad;                             // MAPS_COUNT: row length of maps.seg_cnt
-  uint32_t seed_lo, seed_hi, replica;
-  double fx_scale, fx_inv;
   const double* Q;                             // [model][n][n] row-major
   const double* P;                             // [model][edge][n][n] row-major (section 23)
   const double* pid;                           // [model][n] normalised
   const double* L;                             // [node row][Ev][NP] rescaled partial likelihoods (section 23)
   const double* t;                             // [n_edge]
-  const SmTile* tiles;                         // [n_tiles]
-  const DownStep* down;                        // [n_edge] pre-order
-  const int32_t* order;                        // positions into down[], grouped by the depth of the parent
   double* mu;                                  // [model]
   double* B;                                   // [model][n][n] row-major: I + Q / mu (I when mu = 0)
   const int32_t* depth_of;                     // [model] M(mu_k max_b t_b): the last row of the model's table
   size_t tab_stride;                           // doubles between the tables of two models in `beta`
   double* beta;                                // model k, row m: [e][c] = (B_k^m)[c, e], the n weights of a state draw contiguous
-  uint8_t* nstate;                             // [tile][n_tips + n_node][64] 0-based states by ape row
-  unsigned long long* dwfx;                    // [n][n_tiles * 64] dwell sums, fixed point
-  uint32_t* cnt;                               // [n (n-1)][n_tiles * 64]
-  double* out;                                 // [cols][n_tiles * 64]
-  int32_t* nodes;                              // NULL or [n_tiles * 64][n_tips + n_node] 1-based states
-  uint32_t* err;
-  MapsDev maps;
 };
 
 // mu, B and the table of models [0, Kc) of the chunk, a workgroup per model

@@ -14,14 +14,15 @@
 //            parent state's row of P.
 //   branch   a one-wave workgroup per (tile, branch).  B_k is staged in LDS (row stride n | 1) only when a lane of the wave
 //            drew two or more jumps, the one case in which a state is drawn; the neglog table sits in LDS.
-//   finish   fixed point -> double, counters -> double, node bytes -> 1-based int32.
+//   finish   phm_sample.hip's kernel over the shared SmCore (launch_sm_finish).
+// The categorical draw, the jump-count series and the walk are phm_sample_branch.h's (section 19a), shared with phm_sample.hip.
 // Bounds: the series' loops end at the table depth (DERR_CAPACITY beyond it, nothing is read past the table), the walk at N <= M.
 #include "phm_sample_wide.h"
 
 #include <algorithm>
 
-#include "phm_device.h"
 #include "phm_history.h"
+#include "phm_sample_branch.h"
 
 namespace phm {
 
@@ -73,30 +74,18 @@ __global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
   }
 }
 
-// first j with u * sum(w) <= w_0 + .. + w_j, w_c = a[c] * b[c], sums left to right (sm_draw's run-time form)
-__device__ __forceinline__ int sw_draw(const double* __restrict__ a, const double* __restrict__ b, int n, double u, uint32_t& err) {
-  double total = a[0] * b[0];
-  for (int c = 1; c < n; ++c) total += a[c] * b[c];
-  if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
-  const double thr = u * total;
-  double cum = a[0] * b[0];
-  int idx = (thr <= cum) ? 0 : 1;
-  for (int c = 1; c < n - 1; ++c) { cum += a[c] * b[c]; idx += (thr <= cum) ? 0 : 1; }
-  return idx;
-}
-
 __global__ __launch_bounds__(SW_NODE_BLOCK) void sw_root_kernel(SwParams p) {
   const int lane = threadIdx.x & 63;
   const int tile = blockIdx.x * (SW_NODE_BLOCK / 64) + (threadIdx.x >> 6);
-  if (tile >= p.n_tiles) return;
-  const SmTile tl = p.tiles[tile];
-  const int NT = p.n_tips + p.n_node;
-  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  if (tile >= p.core.n_tiles) return;
+  const SmTile tl = p.core.tiles[tile];
+  const int NT = p.n_tips + p.core.n_node;
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.core.replica;
   uint32_t err = 0;
-  const double u = stream_u(p.seed_lo, p.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)p.root_row, 0);
-  const int s = sw_draw(p.pid + (size_t)tl.k * p.n, p.L + ((size_t)p.root_row * p.Ev + tl.ev) * p.NP, p.n, u, err);
-  p.nstate[((size_t)tile * NT + p.root_row) * 64 + lane] = (uint8_t)s;
-  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+  const double u = stream_u(p.core.seed_lo, p.core.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)p.core.root_row, 0);
+  const int s = sm_draw<0>(p.pid + (size_t)tl.k * p.n, 1, p.L + ((size_t)p.core.root_row * p.Ev + tl.ev) * p.NP, 1, p.n, u, err);
+  p.core.nstate[((size_t)tile * NT + p.core.root_row) * 64 + lane] = (uint8_t)s;
+  if (err && lane < tl.n_valid) atomicOr(p.core.err, err);
 }
 
 // one depth level: a wave per (tile, edge of the level) draws the child's state, tips included
@@ -104,44 +93,46 @@ __global__ __launch_bounds__(SW_NODE_BLOCK) void sw_node_kernel(SwParams p, int 
   const int lane = threadIdx.x & 63;
   const int64_t item = (int64_t)blockIdx.x * (SW_NODE_BLOCK / 64) + (threadIdx.x >> 6);
   const int n_lvl = end - begin;
-  if (item >= (int64_t)n_lvl * p.n_tiles) return;
+  if (item >= (int64_t)n_lvl * p.core.n_tiles) return;
   const int n = p.n;
   const int tile = (int)(item / n_lvl);
-  const DownStep ds = p.down[p.order[begin + (int)(item % n_lvl)]];
-  const SmTile tl = p.tiles[tile];
-  const int NT = p.n_tips + p.n_node;
+  const DownStep ds = p.core.down[p.core.order[begin + (int)(item % n_lvl)]];
+  const SmTile tl = p.core.tiles[tile];
+  const int NT = p.n_tips + p.core.n_node;
   const int crow = ds.child >= 0 ? p.n_tips + ds.child : ~ds.child;
-  uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+  uint8_t* __restrict__ nst = p.core.nstate + (size_t)tile * NT * 64;
   const int a = nst[(p.n_tips + ds.parent) * 64 + lane];
-  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.core.replica;
   uint32_t err = 0;
-  const double u = stream_u(p.seed_lo, p.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)crow, 0);
-  const int e = sw_draw(p.P + (((size_t)tl.k * p.n_edge + ds.edge) * n + a) * n, p.L + ((size_t)crow * p.Ev + tl.ev) * p.NP, n, u, err);
+  const double u = stream_u(p.core.seed_lo, p.core.seed_hi, rep, tl.eval_id, ENT_NODE | (uint32_t)crow, 0);
+  const int e = sm_draw<0>(p.P + (((size_t)tl.k * p.core.n_edge + ds.edge) * n + a) * n, 1, p.L + ((size_t)crow * p.Ev + tl.ev) * p.NP, 1, n, u, err);
   nst[crow * 64 + lane] = (uint8_t)e;
-  if (err && lane < tl.n_valid) atomicOr(p.err, err);
+  if (err && lane < tl.n_valid) atomicOr(p.core.err, err);
 }
 
-// grid: (tile, branch) items, tile fastest; a workgroup is one wave
+// grid: (tile, branch) items, tile fastest; a workgroup is one wave; the branch draw is phm_sample_branch.h's
 template <int MODE>
 __global__ __launch_bounds__(SW_BRANCH_BLOCK) void sw_branch_kernel(SwParams p) {
   extern __shared__ __align__(16) double sw_lds[];                   // B of the item's model, rows n | 1 apart
   __shared__ __align__(16) double s_ltab[2 * PHM_LOGTAB_N];          // (1/c_j, log c_j) of the exponential variates (neglog_u32)
+  const SmCore& sc = p.core;
   const int lane = threadIdx.x;
   for (int i = lane; i < 2 * PHM_LOGTAB_N; i += SW_BRANCH_BLOCK) s_ltab[i] = logtab_entry(i);
   const int n = p.n, nn = n * n, LD = sw_row_stride(n);
-  const int NT = p.n_tips + p.n_node;
+  const int NT = p.n_tips + sc.n_node;
   const int64_t item = blockIdx.x;
-  const int tile = (int)(item % p.n_tiles);
-  const DownStep ds = p.down[(int)(item / p.n_tiles)];
-  const SmTile tl = p.tiles[tile];
-  const size_t npad = (size_t)p.n_tiles * 64;
+  const int tile = (int)(item % sc.n_tiles);
+  const DownStep ds = sc.down[(int)(item / sc.n_tiles)];
+  const SmTile tl = sc.tiles[tile];
+  const size_t npad = (size_t)sc.n_tiles * 64;
   const bool valid = lane < tl.n_valid;
-  const uint8_t* __restrict__ nst = p.nstate + (size_t)tile * NT * 64;
+  const uint8_t* __restrict__ nst = sc.nstate + (size_t)tile * NT * 64;
   const double mu = p.mu[tl.k];
   const int depth = p.depth_of[tl.k];
   const double* __restrict__ Bk = p.B + (size_t)tl.k * nn;
-  const double* __restrict__ bt = p.beta + (size_t)tl.k * p.tab_stride;
-  const uint32_t rep = (uint32_t)(tl.d0 + lane) + p.replica;
+  // B in LDS, rows LD apart; the model's table, row m [e][c]: (B^m)[c, e] at m nn + e n + c
+  const SmTable<SmUnit> tab = {sw_lds, (size_t)LD, {}, p.beta + (size_t)tl.k * p.tab_stride, (size_t)nn, {}, (size_t)n};
+  const uint32_t rep = (uint32_t)(tl.d0 + lane) + sc.replica;
   const int b = ds.edge;
   const int crow = ds.child >= 0 ? p.n_tips + ds.child : ~ds.child;
   const int a = nst[(p.n_tips + ds.parent) * 64 + lane];
@@ -150,45 +141,14 @@ __global__ __launch_bounds__(SW_BRANCH_BLOCK) void sw_branch_kernel(SwParams p) 
   const double x = mu * tb;                                          // wave-uniform
   uint32_t err = 0;
   StatLanes<0, 0> st;
-  st.begin(p.dwfx, p.cnt, npad, (size_t)tile * 64 + lane, p.fx_scale, valid);
+  st.begin(sc.dwfx, sc.cnt, npad, (size_t)tile * 64 + lane, sc.fx_scale, valid);
   MapRow<MODE> mr;                                                   // a lane without a live history: an empty row, no count stored
-  mr.begin(p.maps, (tl.row0 + lane) * p.n_edge + b, valid);
+  mr.begin(sc.maps, (tl.row0 + lane) * sc.n_edge + b, valid);
   auto segment = [&](int col, double v) { st.dwell(col, v); mr.emit(v, col); };
   auto count = [&](int from, int to) { st.count(from * (n - 1) + (to > from ? to - 1 : to)); };
-  int N = 0;
   Stream sr;
-  sr.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
-  if (x > 0.0) {
-    const double* __restrict__ ba = bt + (size_t)e * n + a;          // beta_m[a, e] at ba[m nn]
-    // first pass: the stopping index and the series' own total
-    double r = 1.0, Sp = 1.0, Sa = ba[0];
-    int R = 0, M = 0;
-    for (int m = 1;; ++m) {
-      const double rn = r * (x / (double)m);
-      if (m >= 2 && x < (double)m && rn <= 0x1p-60 * Sp * (1.0 - x / (double)(m + 1))) break;
-      if (m > depth) { err |= DERR_CAPACITY; break; }                // never with the host's depth: M is monotone in x
-      r = rn;
-      Sp += r;
-      Sa += r * ba[(size_t)m * nn];
-      M = m;
-      if (r > 0x1p512) { r *= 0x1p-512; Sp *= 0x1p-512; Sa *= 0x1p-512; ++R; }
-    }
-    if (!(Sa > 0.0) || isinf(Sa)) err |= DERR_ZERO_PROB;
-    const double thr = sr.draw(0) * Sa;
-    // second pass: the first m whose partial sum reaches the threshold
-    double cum = ba[0];
-    int rho = 0;
-    r = 1.0;
-    if (!(thr <= ldexp(cum, -512 * R))) {
-      N = M;
-      for (int m = 1; m <= M; ++m) {
-        r = r * (x / (double)m);
-        cum += r * ba[(size_t)m * nn];
-        if (r > 0x1p512) { r *= 0x1p-512; cum *= 0x1p-512; ++rho; }
-        if (thr <= ldexp(cum, -512 * (R - rho))) { N = m; break; }
-      }
-    }
-  }
+  sr.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, sc.seed_lo, sc.seed_hi);
+  const int N = x > 0.0 ? sm_jump_count(tab, a, e, x, depth, sr, err) : 0;       // mu = 0 or t = 0: no jump
   if (__any(N >= 2)) {                                               // only then is a state drawn from B
     for (int i = lane; i < nn; i += SW_BRANCH_BLOCK) {
       const int row = i / n;
@@ -196,58 +156,13 @@ __global__ __launch_bounds__(SW_BRANCH_BLOCK) void sw_branch_kernel(SwParams p) 
     }
   }
   __syncthreads();                                                   // the neglog table and B are staged
-  if (N > 0) {
-    // jump times: G = E_1 + .. + E_{N+1}, then the walk takes the same draws again
-    double G = 0.0;
-    for (int i = 1; i <= N + 1; ++i) G += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
-    Stream su;
-    su.open(ENT_BUNIF | (uint32_t)b, tl.eval_id, rep, p.seed_lo, p.seed_hi);
-    int prev = a, sprev = a;
-    double tprev = 0.0, c = 0.0;
-    for (int i = 1; i <= N; ++i) {
-      c += neglog_u32(sr.draw_word((uint32_t)i), s_ltab);
-      int di = e;
-      if (i < N) {
-        const double u = su.draw((uint32_t)(N + 1 + i));
-        di = sw_draw(sw_lds + prev * LD, bt + ((size_t)(N - i) * nn + (size_t)e * n), n, u, err);
-      }
-      if (prev != di) {
-        const double ti = tb * (c / G);
-        segment(sprev, ti - tprev);
-        count(sprev, di);
-        tprev = ti; sprev = di;
-      }
-      prev = di;
-    }
-    segment(sprev, tb - tprev);
-  } else {
-    segment(a, tb);                                                  // no jump, mu = 0 or t = 0: the parent's state for the whole branch
-  }
-  if (valid) mr.end((size_t)b * p.map_pad + (size_t)(tl.row0 + lane));
-  if (err && valid) atomicOr(p.err, err);
-}
-
-__global__ __launch_bounds__(256) void sw_finish_kernel(SwParams p) {
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int n = p.n, cols = n + n * (n - 1);
-  const int64_t npad = (int64_t)p.n_tiles * 64;
-  const int NT = p.n_tips + p.n_node;
-  if (gid < cols * npad) {
-    const int c = (int)(gid / npad);
-    const int64_t it = gid % npad;
-    p.out[gid] = stat_cell_value(p.dwfx, p.cnt, n, c, (size_t)npad, (size_t)it, p.fx_inv);
-  }
-  if (p.nodes) {
-    for (int64_t cell = gid; cell < npad * NT; cell += (int64_t)gridDim.x * blockDim.x) {
-      const int64_t it = cell / NT;
-      const int row = (int)(cell % NT);
-      p.nodes[cell] = (int32_t)p.nstate[((size_t)(it >> 6) * NT + row) * 64 + (it & 63)] + 1;
-    }
-  }
+  sm_walk<0>(tab, n, a, e, tb, N, sr, s_ltab, err, segment, count);
+  if (valid) mr.end((size_t)b * sc.map_pad + (size_t)(tl.row0 + lane));
+  if (err && valid) atomicOr(sc.err, err);
 }
 
 inline bool sw_ok(const SwParams& p) {
-  return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.n_edge >= 1;
+  return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.core.n_edge >= 1;
 }
 
 }  // namespace
@@ -261,24 +176,21 @@ hipError_t launch_sw_table(const SwParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_sw_sample(const SwParams& p, const std::vector<int32_t>& level_off, int maps_mode, hipStream_t stream) {
-  if (!sw_ok(p) || p.n_tiles <= 0 || (int64_t)p.n_edge * p.n_tiles > SW_ITEMS_MAX) return hipErrorInvalidValue;
+  if (!sw_ok(p) || p.core.n_tiles <= 0 || (int64_t)p.core.n_edge * p.core.n_tiles > SW_ITEMS_MAX) return hipErrorInvalidValue;
   constexpr int W = SW_NODE_BLOCK / 64;
-  hipLaunchKernelGGL(sw_root_kernel, dim3((p.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
+  hipLaunchKernelGGL(sw_root_kernel, dim3((p.core.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
   for (size_t l = 0; l + 1 < level_off.size(); ++l) {
     const int64_t cnt = level_off[l + 1] - level_off[l];
     if (cnt <= 0) continue;
-    const dim3 grid((unsigned)((cnt * p.n_tiles + W - 1) / W));
+    const dim3 grid((unsigned)((cnt * p.core.n_tiles + W - 1) / W));
     hipLaunchKernelGGL(sw_node_kernel, grid, dim3(SW_NODE_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
   }
-  const dim3 items((unsigned)((int64_t)p.n_edge * p.n_tiles));
+  const dim3 items((unsigned)((int64_t)p.core.n_edge * p.core.n_tiles));
   with_map_mode(maps_mode, [&](auto mode) {
     constexpr int MODE = decltype(mode)::value;
     hipLaunchKernelGGL((sw_branch_kernel<MODE>), items, dim3(SW_BRANCH_BLOCK), sw_branch_lds_bytes(p.n), stream, p);
   });
-  const int n = p.n;
-  const int64_t cells = (int64_t)(n + n * (n - 1)) * p.n_tiles * 64;
-  hipLaunchKernelGGL(sw_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, p);
-  return hipGetLastError();
+  return launch_sm_finish(p.core, p.n, p.n_tips, nullptr, stream);
 }
 
 }  // namespace phm

@@ -60,7 +60,7 @@ int32_t sc_lanes_device(const ScInput& sc, int32_t device, int64_t first, int64_
   const int n_runs = (E + phm::SC_RUN - 1) / phm::SC_RUN;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   LlLanes ln(in);
   DevBuf ddown, dchild;
   st = ln.upload_tree();
@@ -107,8 +107,7 @@ int32_t sc_lanes_device(const ScInput& sc, int32_t device, int64_t first, int64_
     if (st) return st;
     HIPCHK(phm::launch_sc_model(sp, nullptr));
     HIPCHK(tm.stop());
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    HIPCHK(tm.add_to(kernel_ms));
 
     for (int64_t s0 = 0; s0 < S_eval; s0 += pl.Sc_max) {
       const int64_t Sc = std::min<int64_t>(pl.Sc_max, S_eval - s0);
@@ -132,8 +131,7 @@ int32_t sc_lanes_device(const ScInput& sc, int32_t device, int64_t first, int64_
       st = ln.fetch_ll(Sc);
       if (st) return st;
       HIPCHK(hipMemcpy(toth.data(), dtot.p, sizeof(double) * cols * Ev, hipMemcpyDeviceToHost));
-      HIPCHK(tm.elapsed(ms));
-      kernel_ms += ms;
+      HIPCHK(tm.add_to(kernel_ms));
       for (int64_t s = 0; s < Sc; ++s)
         for (int64_t k = 0; k < Kc; ++k) {
           const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);

@@ -72,7 +72,7 @@ int32_t simm_device(const SimmInput& in, int32_t device, int64_t first, int64_t 
   const int64_t R = in.R, H = in.H;
   const int64_t h_first = first * R, h_count = count * R;            // the shard's histories
   KernelTimer tm;
-  double kernel_ms = 0.0, ms = 0.0;
+  double kernel_ms = 0.0;
   const uint32_t err_init = 0u;
   const unsigned long long cap_init = ~0ull;
   DevBuf ddown, dorder, dlen, dmap, derr, dcap;
@@ -157,8 +157,7 @@ int32_t simm_device(const SimmInput& in, int32_t device, int64_t first, int64_t 
     HIPCHK(tm.stop());
     uint32_t errh = 0;
     HIPCHK(hipMemcpy(&errh, derr.p, sizeof errh, hipMemcpyDeviceToHost));
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    HIPCHK(tm.add_to(kernel_ms));
     if (errh & phm::DERR_CAPACITY) {
       unsigned long long caph = 0;
       HIPCHK(hipMemcpy(&caph, dcap.p, sizeof caph, hipMemcpyDeviceToHost));
@@ -174,8 +173,7 @@ int32_t simm_device(const SimmInput& in, int32_t device, int64_t first, int64_t 
     HIPCHK(tm.start());
     HIPCHK(msh.after_kernel(*mh, map_pad, nullptr));                 // sizing: counts -> offsets
     HIPCHK(tm.stop());
-    HIPCHK(tm.elapsed(ms));
-    kernel_ms += ms;
+    HIPCHK(tm.add_to(kernel_ms));
     st = msh.copy_home(*mh, si, "phm_simulate_histories_models");
     if (st) return st;
   }

@@ -9,7 +9,7 @@ import numpy as np
 WAVES_PER_BLOCK = 4                  # SM_BLOCK / 64 (phm_sample.h) and SIMM_BLOCK / 64 (phm_simm.h)
 ITEMS_PER_WAVE_TARGET = 8192         # the divisor of both group formulas
 GROUP_MAX = 16
-BRANCH_BLOCKS_MAX = 2048             # flush() in phm_sample_api.cpp, the chain chunk in phm_gibbs_api.cpp
+BRANCH_BLOCKS_MAX = 2048             # the launch of a flush in phm_sample_api.cpp, the chain chunk in phm_gibbs_api.cpp
 LEVEL_BLOCKS_MAX = 65536             # launch_simulate_models in phm_simm.hip
 
 
@@ -30,7 +30,7 @@ def group_sizes(count, group):
 def sampler_launch(n_edge, n_tiles):
     """One flush of phm_sample_histories_models (tile form) or one chunk of chains of phm_gibbs_rates (packed form).
       group          launch_sm_sample, phm_sample.hip: max(1, min(16, n_edge * n_tiles / 8192))
-      branch_blocks  phm_sample_api.cpp flush() and phm_gibbs_api.cpp: min((n_edge * n_tiles + 3) / 4, 2048)
+      branch_blocks  phm_sample_api.cpp (the launch of a flush) and phm_gibbs_api.cpp: min((n_edge * n_tiles + 3) / 4, 2048)
       items          sm_branch_kernel: ceil(n_edge / group) * n_tiles, walked with stride gridDim.x * 4"""
     group = max(1, min(GROUP_MAX, n_edge * n_tiles // ITEMS_PER_WAVE_TARGET))
     blocks = min((n_edge * n_tiles + 3) // 4, BRANCH_BLOCKS_MAX)
@@ -43,7 +43,7 @@ def sampler_launch(n_edge, n_tiles):
 
 def tiles_of_sample(n_eval, D, expect_chunk=0):
     """tiles of the flushes of a sample_histories call whose evaluations fit one chunk of models and sites (a tile: 64 draws of
-    one evaluation; phm_sample_api.cpp: Tc_max = min(tiles, expect_chunk))"""
+    one evaluation; sm_tiles_max of phm_sample_host.h: Tc_max = min(tiles, expect_chunk))"""
     total = n_eval * ((D + 63) // 64)
     cap = min(total, expect_chunk) if expect_chunk > 0 else total
     return [min(cap, total - t0) for t0 in range(0, total, cap)]
