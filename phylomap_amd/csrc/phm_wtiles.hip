@@ -59,151 +59,197 @@ __device__ __forceinline__ int sample_terms(int n, double u, Term term, uint32_t
 // 16 i + (l >> 4) + 4 q = 4 (4 i + q) + (l >> 4): exactly the B-operand slice of k-step 4 i + q.  So X <- Bc X is
 // MT * 4 MT MFMAs and the result feeds the next step as it stands; each output entry is the fused chain
 // fma(Bc[r][j], x[j], acc) with j ascending from +0 (k-steps in order, four k per MFMA in order).
+// The pieces below are what the pruning kernels (and, for the tile view, the node draws) share; lk = lane >> 4 throughout.
 // ---------------------------------------------------------------------------------------------------------------------
+
+// One tile's slice of the per-replica tables: PL [node][state][64], mcount [edge][64], nstate [node][64], tips [tip][64]
+// (or the one row of tip states every replica shares).
+struct WtTile {
+  double* PL;
+  const uint16_t* mcount;
+  const uint8_t* tips;
+  uint8_t* nstate;
+};
+__device__ __forceinline__ WtTile wt_tile(const WtParams& p, int tile) {
+  return {p.PL + (size_t)tile * p.n_node * p.n_states * 64, p.mcount + (size_t)tile * p.n_edge * 64,
+          p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips, p.nstate + (size_t)tile * p.n_node * 64};
+}
+// replica column j of a node's vector: state s of it is at [s * 64]
+__device__ __forceinline__ double* wt_column(const WtParams& p, const WtTile& t, int node, int j) {
+  return t.PL + ((size_t)node * p.n_states) * 64 + j;
+}
+__device__ __forceinline__ int wt_tip_state(const WtParams& p, const WtTile& t, int tip, int j) {
+  return p.tips_per_replica ? t.tips[tip * 64 + j] : p.tips[tip];
+}
+
+// entry (row, k) of the chain matrix padded with zeros: what lane l holds of A-operand fragment (i, s) at row = 16 i + (l & 15),
+// k = 4 s + (l >> 4)
+__device__ __forceinline__ double wt_bc_entry(const WtParams& p, int row, int k) {
+  return (row < p.n_states && k < p.n_states) ? p.Bc[row * p.n_states + k] : 0.0;
+}
+template <int MT>
+__device__ __forceinline__ void wt_load_frags(const WtParams& p, int lane, double (&Af)[MT][4 * MT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int s = 0; s < 4 * MT; ++s) Af[i][s] = wt_bc_entry(p, 16 * i + (lane & 15), 4 * s + (lane >> 4));
+}
+
+// One row tile of a vector as B operand / accumulator: register q = base[(row0 + 4 q) * stride], zero from state n on.  Stride 64
+// reads a replica's column of PL (wt_column) or of a parked copy, stride 1 a row of the chain table.
+__device__ __forceinline__ d4_t wt_load_tile(const double* __restrict__ base, int stride, int n, int row0) {
+  d4_t x;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = row0 + 4 * q;
+    x[q] = (row < n) ? base[(size_t)row * stride] : 0.0;
+  }
+  return x;
+}
+template <int MT>
+__device__ __forceinline__ void wt_load_rows(const double* __restrict__ base, int stride, int n, int lk, d4_t (&X)[MT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i) X[i] = wt_load_tile(base, stride, n, 16 * i + lk);
+}
+// the states below n of a vector into a column ([state][64])
+template <int MT>
+__device__ __forceinline__ void wt_store_rows(double* __restrict__ col, int n, int lk, const d4_t (&P)[MT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int row = 16 * i + lk + 4 * q;
+      if (row < n) col[(size_t)row * 64] = P[i][q];
+    }
+}
+
+// A tip child's vector for replica column j: a row of the chain table, the chain of the edge run from the unit vector of the
+// tip's state or (ks) from its parity mask.  A chain longer than the table is clamped and flagged.
+__device__ __forceinline__ const double* wt_tip_row(const WtParams& p, const WtTile& t, int child, int edge, int j, uint32_t& err) {
+  const int ts = wt_tip_state(p, t, ~child, j);
+  int k = (int)t.mcount[edge * 64 + j] - 1;
+  if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
+  return p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * p.ldt : p.colL + ((size_t)k * p.n_states + ts) * p.ldt;
+}
+
+// R = Bc^kj X with the chain matrix in registers: the wave runs to its longest chain on the matrix cores, column j keeps the
+// product of step kj (X is used up).  ks_used = ceil(n / 4), wave-uniform: the k-steps beyond multiply zeros and
+// fma(0, 0, acc) = acc, so skipping them changes nothing.
+template <int MT>
+__device__ __forceinline__ void wt_chain(const double (&Af)[MT][4 * MT], int ks_used, d4_t (&X)[MT], int kj, d4_t (&R)[MT]) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i) R[i] = X[i];
+  const int kmax = wave_max_count(kj);
+  for (int step = 1; step <= kmax; ++step) {
+    d4_t Y[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < 4 * MT; ++s)
+        if (s < ks_used) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[i][s], X[s >> 2][s & 3], acc, 0, 0, 0);
+      Y[i] = acc;
+    }
+    const bool mine = (kj == step);
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      X[i] = Y[i];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) R[i][q] = mine ? Y[i][q] : R[i][q];
+    }
+  }
+}
+
+// the parent's column = first (.) second (:510), / sum (:525)
+template <int MT>
+__device__ __forceinline__ void wt_finish(const WtParams& p, double* __restrict__ col, int lk, const d4_t (&R0)[MT], const d4_t (&R1)[MT]) {
+  d4_t P[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) P[i] = R0[i] * R1[i];
+  if (p.normalise) {
+    double t = 0.0;                                    // states lk, lk + 4, lk + 8, ... ascending: partial sum t_lk
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) t += P[i][q];
+    t = t + __shfl_xor(t, 16, 64);                     // t_0 + t_1 | t_2 + t_3
+    t = t + __shfl_xor(t, 32, 64);                     // (t_0 + t_1) + (t_2 + t_3)
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) P[i][q] = P[i][q] / t;
+  }
+  wt_store_rows(col, p.n_states, lk, P);
+}
+
+// a wave's whole tile at a node whose children are both tips: no chain to run, the four 16-column blocks in replica order
+template <int MT>
+__device__ __forceinline__ void wt_up_tip_pair(const WtParams& p, const WtTile& t, const UpStep& st, int lane, uint32_t& err) {
+  const int lr = lane & 15, lk = lane >> 4;
+  for (int nt = 0; nt < 4; ++nt) {
+    const int j = 16 * nt + lr;
+    d4_t R0[MT], R1[MT];
+    wt_load_rows(wt_tip_row(p, t, st.child[1], st.edge[1], j, err), 1, p.n_states, lk, R0);
+    wt_load_rows(wt_tip_row(p, t, st.child[0], st.edge[0], j, err), 1, p.n_states, lk, R1);
+    wt_finish(p, wt_column(p, t, st.parent, j), lk, R0, R1);
+  }
+}
+
+// The chain matrix in registers, a wave per (node, tile), the tile's replicas sorted by chain length.
 template <int MT>
 __global__ __launch_bounds__(WT_BLOCK) void wt_up_kernel(WtParams p, int begin, int end) {
-  constexpr int KS = 4 * MT;
   extern __shared__ __align__(16) double s_scr_all[];  // [wave][n][64]: the first child's vectors while the second child's chains run
   __shared__ uint8_t s_perm_all[WT_BLOCK / 64][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int n = p.n_states, ldt = p.ldt;
+  const int n = p.n_states;
   double* s_scr = s_scr_all + (size_t)wave * n * 64;      // n rows, not 16 MT (C5: pruning 21.0 -> 20.4 ms per sweep)
   uint8_t* s_perm = s_perm_all[wave];
-  double Af[MT][KS];                                   // the chain matrix as A-operand fragments, for the whole launch
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int row = 16 * i + lr, k = 4 * s + lk;
-      Af[i][s] = (row < n && k < n) ? p.Bc[row * n + k] : 0.0;
-    }
+  double Af[MT][4 * MT];                               // the chain matrix as A-operand fragments, for the whole launch
+  wt_load_frags(p, lane, Af);
   const int n_lvl = end - begin;
   const int64_t items = (int64_t)n_lvl * p.n_tiles;
-  const int ks_used = (n + 3) >> 2;                    // wave-uniform: fma(0, 0, acc) = acc, so the skipped steps change nothing
+  const int ks_used = (n + 3) >> 2;
   uint32_t err = 0;
   for (int64_t item = (int64_t)blockIdx.x * (WT_BLOCK / 64) + wave; item < items; item += (int64_t)gridDim.x * (WT_BLOCK / 64)) {
     const int tile = (int)(item % p.n_tiles), li = (int)(item / p.n_tiles);
     const UpStep st = p.up[p.up_order[begin + li]];
-    double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-    const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
-    const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
+    const WtTile t = wt_tile(p, tile);
 
     // The 64 replicas of the tile are dealt to the four 16-column MFMA blocks in the order of their chain lengths
     // (a block runs to the longest chain of its columns, so equal lengths side by side waste the fewest steps):
     // s_perm[r] = the lane (replica) of rank r; returns this lane's own chain length.
     auto sort_by_chain = [&](int edge) -> int {
-      const int k = (int)mct[edge * 64 + lane] - 1;
+      const int k = (int)t.mcount[edge * 64 + lane] - 1;
       int rank = 0;
-      for (int t = 0; t < 64; ++t) {
-        const int kt = __builtin_amdgcn_readlane(k, t);
-        rank += (kt < k || (kt == k && t < lane)) ? 1 : 0;
+      for (int u = 0; u < 64; ++u) {
+        const int ku = __builtin_amdgcn_readlane(k, u);
+        rank += (ku < k || (ku == k && u < lane)) ? 1 : 0;
       }
       s_perm[rank] = (uint8_t)lane;
       return k;
     };
-    // the child's vectors of replica column j as B-operand tiles
-    auto load_x = [&](int child, int j, d4_t (&X)[MT]) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          X[i][q] = (row < n) ? PLt[((size_t)child * n + row) * 64 + j] : 0.0;
-        }
-    };
-    // Bc^kj applied to them: kmax steps on the matrix cores, column j keeps the product of step kj
-    auto run_chain = [&](d4_t (&X)[MT], int kj, d4_t (&R)[MT]) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) R[i] = X[i];
-      const int kmax = wave_max_count(kj);
-      for (int step = 1; step <= kmax; ++step) {
-        d4_t Y[MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int s = 0; s < KS; ++s)                 // k-steps whose four input states are all >= n multiply zeros: skipped
-            if (s < ks_used) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[i][s], X[s >> 2][s & 3], acc, 0, 0, 0);
-          Y[i] = acc;
-        }
-        const bool mine = (kj == step);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          X[i] = Y[i];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) R[i][q] = mine ? Y[i][q] : R[i][q];
-        }
-      }
-    };
-    // a tip child: a row of the chain table (the chain run from a unit vector / the parity mask)
-    auto tipvec = [&](int child, int edge, int j, d4_t (&R)[MT]) {
-      const int tip = ~child;
-      const int ts = p.tips_per_replica ? tips_t[tip * 64 + j] : p.tips[tip];
-      int k = (int)mct[edge * 64 + j] - 1;
-      if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
-      const double* __restrict__ src = p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * ldt : p.colL + ((size_t)k * n + ts) * ldt;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          R[i][q] = (row < n) ? src[row] : 0.0;
-        }
-    };
-    // PL[parent] = first (.) second (:510), / sum (:525), for replica column j
-    auto finish = [&](int j, const d4_t (&R0)[MT], const d4_t (&R1)[MT]) {
-      d4_t P[MT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) P[i] = R0[i] * R1[i];
-      if (p.normalise) {
-        double t = 0.0;                                // states lk, lk + 4, lk + 8, ... ascending: partial sum t_lk
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) t += P[i][q];
-        t = t + __shfl_xor(t, 16, 64);                 // t_0 + t_1 | t_2 + t_3
-        t = t + __shfl_xor(t, 32, 64);                 // (t_0 + t_1) + (t_2 + t_3)
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) P[i][q] = P[i][q] / t;
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          if (row < n) PLt[((size_t)st.parent * n + row) * 64 + j] = P[i][q];
-        }
-    };
 
     // "first" = child[1] (:508), "second" = child[0] (:509)
     const bool int_first = st.child[1] >= 0, int_second = st.child[0] >= 0;
-    if (!int_first && !int_second) {
-      for (int nt = 0; nt < 4; ++nt) {
-        const int j = 16 * nt + lr;
-        d4_t R0[MT], R1[MT];
-        tipvec(st.child[1], st.edge[1], j, R0);
-        tipvec(st.child[0], st.edge[0], j, R1);
-        finish(j, R0, R1);
-      }
-    } else if (int_first != int_second) {
+    if (!int_first && !int_second) wt_up_tip_pair<MT>(p, t, st, lane, err);
+    else if (int_first != int_second) {
       // One wave per SIMD (the fragments of Bc take 128 registers): nothing else hides a load, so the next block's vectors and
       // this block's tip rows are requested BEFORE the chain of this block starts and arrive while the matrix cores run.
       const int ci = int_first ? 1 : 0;                // the internal child
       const int k = sort_by_chain(st.edge[ci]);
       d4_t X[MT], Xn[MT];
       int j = s_perm[lr];
-      load_x(st.child[ci], j, X);
+      wt_load_rows(wt_column(p, t, st.child[ci], j), 64, n, lk, X);
       for (int nt = 0; nt < 4; ++nt) {
         const int kj = __shfl(k, j, 64);
         const int jn = (nt < 3) ? s_perm[16 * (nt + 1) + lr] : j;
-        if (nt < 3) load_x(st.child[ci], jn, Xn);
+        if (nt < 3) wt_load_rows(wt_column(p, t, st.child[ci], jn), 64, n, lk, Xn);
         d4_t Rc[MT], Rt[MT];
-        tipvec(st.child[1 - ci], st.edge[1 - ci], j, Rt);
-        run_chain(X, kj, Rc);
-        if (int_first) finish(j, Rc, Rt); else finish(j, Rt, Rc);
+        wt_load_rows(wt_tip_row(p, t, st.child[1 - ci], st.edge[1 - ci], j, err), 1, n, lk, Rt);
+        wt_chain(Af, ks_used, X, kj, Rc);
+        double* out = wt_column(p, t, st.parent, j);
+        if (int_first) wt_finish(p, out, lk, Rc, Rt); else wt_finish(p, out, lk, Rt, Rc);
 #pragma unroll
         for (int i = 0; i < MT; ++i) X[i] = Xn[i];
         j = jn;
@@ -212,35 +258,29 @@ __global__ __launch_bounds__(WT_BLOCK) void wt_up_kernel(WtParams p, int begin, 
       const int k1 = sort_by_chain(st.edge[1]);
       d4_t X[MT], Xn[MT];
       int j = s_perm[lr];
-      load_x(st.child[1], j, X);
+      wt_load_rows(wt_column(p, t, st.child[1], j), 64, n, lk, X);
       for (int nt = 0; nt < 4; ++nt) {
         const int kj = __shfl(k1, j, 64);
         const int jn = (nt < 3) ? s_perm[16 * (nt + 1) + lr] : j;
-        if (nt < 3) load_x(st.child[1], jn, Xn);
+        if (nt < 3) wt_load_rows(wt_column(p, t, st.child[1], jn), 64, n, lk, Xn);
         d4_t R0[MT];
-        run_chain(X, kj, R0);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { const int row = 16 * i + lk + 4 * q; if (row < n) s_scr[row * 64 + j] = R0[i][q]; }
+        wt_chain(Af, ks_used, X, kj, R0);
+        wt_store_rows(s_scr + j, n, lk, R0);           // waits in LDS for the second child's
 #pragma unroll
         for (int i = 0; i < MT; ++i) X[i] = Xn[i];
         j = jn;
       }
       const int k0 = sort_by_chain(st.edge[0]);
       j = s_perm[lr];
-      load_x(st.child[0], j, X);
+      wt_load_rows(wt_column(p, t, st.child[0], j), 64, n, lk, X);
       for (int nt = 0; nt < 4; ++nt) {
         const int kj = __shfl(k0, j, 64);
         const int jn = (nt < 3) ? s_perm[16 * (nt + 1) + lr] : j;
-        if (nt < 3) load_x(st.child[0], jn, Xn);
+        if (nt < 3) wt_load_rows(wt_column(p, t, st.child[0], jn), 64, n, lk, Xn);
         d4_t R0[MT], R1[MT];
-        run_chain(X, kj, R1);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { const int row = 16 * i + lk + 4 * q; R0[i][q] = (row < n) ? s_scr[row * 64 + j] : 0.0; }
-        finish(j, R0, R1);
+        wt_chain(Af, ks_used, X, kj, R1);
+        wt_load_rows(s_scr + j, 64, n, lk, R0);
+        wt_finish(p, wt_column(p, t, st.parent, j), lk, R0, R1);
 #pragma unroll
         for (int i = 0; i < MT; ++i) X[i] = Xn[i];
         j = jn;
@@ -275,12 +315,9 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
   __shared__ uint8_t s_perm_all[WT_BLOCK / 64][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int n = p.n_states, ldt = p.ldt;
+  const int n = p.n_states;
   uint8_t* s_perm = s_perm_all[wave];
-  for (int f = wave; f < MT * KS; f += WT_BLOCK / 64) {
-    const int row = 16 * (f / KS) + lr, k = 4 * (f % KS) + lk;
-    s_A[f * 64 + lane] = (row < n && k < n) ? p.Bc[row * n + k] : 0.0;
-  }
+  for (int f = wave; f < MT * KS; f += WT_BLOCK / 64) s_A[f * 64 + lane] = wt_bc_entry(p, 16 * (f / KS) + lr, 4 * (f % KS) + lk);
   __syncthreads();
   const int n_lvl = end - begin;
   const int64_t items = (int64_t)n_lvl * p.n_tiles;
@@ -288,14 +325,12 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
   for (int64_t item = (int64_t)blockIdx.x * (WT_BLOCK / 64) + wave; item < items; item += (int64_t)gridDim.x * (WT_BLOCK / 64)) {
     const int tile = (int)(item % p.n_tiles), li = (int)(item / p.n_tiles);
     const UpStep st = p.up[p.up_order[begin + li]];
-    double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-    const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
-    const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
+    const WtTile t = wt_tile(p, tile);
 
     // rank of (chain length, lane) as in wt_up_kernel; the lengths of a tile span a few values, so the ranks come from one ballot
     // per VALUE (a counting sort: lanes of equal length keep their order) instead of one comparison per LANE
     auto sort_by_chain = [&](int edge) -> int {
-      const int k = (int)mct[edge * 64 + lane] - 1;
+      const int k = (int)t.mcount[edge * 64 + lane] - 1;
       const int khi = wave_max_count(k), klo = 65535 - wave_max_count(65535 - k);
       int rank = 0;
       if (khi - klo < 40) {
@@ -307,22 +342,13 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
           base += (int)__popcll(mask);
         }
       } else {
-        for (int t = 0; t < 64; ++t) {
-          const int kt = __builtin_amdgcn_readlane(k, t);
-          rank += (kt < k || (kt == k && t < lane)) ? 1 : 0;
+        for (int u = 0; u < 64; ++u) {
+          const int ku = __builtin_amdgcn_readlane(k, u);
+          rank += (ku < k || (ku == k && u < lane)) ? 1 : 0;
         }
       }
       s_perm[rank] = (uint8_t)lane;
       return k;
-    };
-    auto load_x = [&](int node, int j, d4_t (&X)[MT]) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          X[i][q] = (row < n) ? PLt[((size_t)node * n + row) * 64 + j] : 0.0;
-        }
     };
     // Bc^kj applied to the vectors in X, in place: kmax steps on the matrix cores, the lanes of column j stop taking the products
     // after step kj (a lane's four-state slices all belong to ONE column, l & 15: the finished column rides along unchanged)
@@ -366,69 +392,21 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
           for (int q = 0; q < 4; ++q) X[i][q] = live ? Y[i][q] : X[i][q];
       }
     };
-    auto tipvec = [&](int child, int edge, int j, d4_t (&R)[MT]) {
-      const int tip = ~child;
-      const int ts = p.tips_per_replica ? tips_t[tip * 64 + j] : p.tips[tip];
-      int k = (int)mct[edge * 64 + j] - 1;
-      if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
-      const double* __restrict__ src = p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * ldt : p.colL + ((size_t)k * n + ts) * ldt;
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          R[i][q] = (row < n) ? src[row] : 0.0;
-        }
-    };
-    auto store = [&](int j, const d4_t (&P)[MT]) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * i + lk + 4 * q;
-          if (row < n) PLt[((size_t)st.parent * n + row) * 64 + j] = P[i][q];
-        }
-    };
-    auto finish = [&](int j, const d4_t (&R0)[MT], const d4_t (&R1)[MT]) {      // first (.) second (:510), / sum (:525)
-      d4_t P[MT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) P[i] = R0[i] * R1[i];
-      if (p.normalise) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) t += P[i][q];
-        t = t + __shfl_xor(t, 16, 64);
-        t = t + __shfl_xor(t, 32, 64);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) P[i][q] = P[i][q] / t;
-      }
-      store(j, P);
-    };
 
     const bool int_first = st.child[1] >= 0, int_second = st.child[0] >= 0;
-    if (!int_first && !int_second) {
-      for (int nt = 0; nt < 4; ++nt) {
-        const int j = 16 * nt + lr;
-        d4_t R0[MT], R1[MT];
-        tipvec(st.child[1], st.edge[1], j, R0);
-        tipvec(st.child[0], st.edge[0], j, R1);
-        finish(j, R0, R1);
-      }
-    } else if (int_first != int_second) {
+    if (!int_first && !int_second) wt_up_tip_pair<MT>(p, t, st, lane, err);
+    else if (int_first != int_second) {
       const int ci = int_first ? 1 : 0;                // the internal child
       const int k = sort_by_chain(st.edge[ci]);
       for (int nt = 0; nt < 4; ++nt) {
         const int j = s_perm[16 * nt + lr];
         const int kj = __shfl(k, j, 64);
         d4_t X[MT], Rt[MT];
-        load_x(st.child[ci], j, X);
+        wt_load_rows(wt_column(p, t, st.child[ci], j), 64, n, lk, X);
         run_chain(X, kj);
-        tipvec(st.child[1 - ci], st.edge[1 - ci], j, Rt);
-        if (int_first) finish(j, X, Rt); else finish(j, Rt, X);
+        wt_load_rows(wt_tip_row(p, t, st.child[1 - ci], st.edge[1 - ci], j, err), 1, n, lk, Rt);
+        double* out = wt_column(p, t, st.parent, j);
+        if (int_first) wt_finish(p, out, lk, X, Rt); else wt_finish(p, out, lk, Rt, X);
       }
     } else {
       const int k1 = sort_by_chain(st.edge[1]);
@@ -436,9 +414,9 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
         const int j = s_perm[16 * nt + lr];
         const int kj = __shfl(k1, j, 64);
         d4_t X[MT];
-        load_x(st.child[1], j, X);
+        wt_load_rows(wt_column(p, t, st.child[1], j), 64, n, lk, X);
         run_chain(X, kj);
-        store(j, X);                                   // waits in the parent's row
+        wt_store_rows(wt_column(p, t, st.parent, j), n, lk, X);      // waits in the parent's row
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       const int k0 = sort_by_chain(st.edge[0]);
@@ -447,10 +425,10 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
         const int j = s_perm[16 * nt + lr];
         const int kj = __shfl(k0, j, 64);
         d4_t X[MT], R0[MT];
-        load_x(st.child[0], j, X);
+        wt_load_rows(wt_column(p, t, st.child[0], j), 64, n, lk, X);
         run_chain(X, kj);
-        load_x(st.parent, j, R0);
-        finish(j, R0, X);
+        wt_load_rows(wt_column(p, t, st.parent, j), 64, n, lk, R0);
+        wt_finish(p, wt_column(p, t, st.parent, j), lk, R0, X);
       }
     }
   }
@@ -472,20 +450,15 @@ __global__ __launch_bounds__(WT_BLOCK, wt_up2_waves(MT)) void wt_up2_kernel(WtPa
 template <int NP, int HB>
 __device__ __forceinline__ void wt_up_band_node(const WtParams& p, const WtBand& bd, int tile, const UpStep& st, int lane, uint32_t& err) {
   constexpr int W = 2 * HB + 1;
-  const int n = p.n_states, ldt = p.ldt;
-  double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-  const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
-  const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
+  const int n = p.n_states;
+  const WtTile t = wt_tile(p, tile);
+  double* __restrict__ PLt = t.PL;
   double R[2][NP];
 #pragma unroll
   for (int ch = 0; ch < 2; ++ch) {                     // ch 0: "first" = child[1] (:508); ch 1: "second" = child[0] (:509)
     const int child = st.child[1 - ch], edge = st.edge[1 - ch];
-    int k = (int)mct[edge * 64 + lane] - 1;
-    if (child < 0) {                                   // tip: a row of the chain table (the chain run from a unit vector / the parity mask)
-      const int tip = ~child;
-      const int ts = p.tips_per_replica ? tips_t[tip * 64 + lane] : p.tips[tip];
-      if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
-      const double2* __restrict__ src = reinterpret_cast<const double2*>(p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * ldt : p.colL + ((size_t)k * n + ts) * ldt);
+    if (child < 0) {                                   // tip: its row of the chain table, two states per load
+      const double2* __restrict__ src = reinterpret_cast<const double2*>(wt_tip_row(p, t, child, edge, lane, err));
 #pragma unroll
       for (int i = 0; i < NP; i += 2) {                // rows are 16-byte aligned and padded to an even length with zeros
         double2 v = {0.0, 0.0};
@@ -496,6 +469,7 @@ __device__ __forceinline__ void wt_up_band_node(const WtParams& p, const WtBand&
       double (&x)[NP] = R[ch];
 #pragma unroll
       for (int i = 0; i < NP; ++i) x[i] = (i < n) ? PLt[((size_t)child * n + i) * 64 + lane] : 0.0;
+      const int k = (int)t.mcount[edge * 64 + lane] - 1;
       const int kmax = wave_max_count(k);
       for (int step = 1; step <= kmax; ++step) {
         if (step <= k) {                               // x <- Bc x for the lanes still inside their chain
@@ -583,21 +557,14 @@ __global__ __launch_bounds__(WT_CL_BLOCK) void wt_up_band_cluster_kernel(WtParam
 // row blocks the row-split workgroups of wt_up_msplit_kernel are faster still.
 template <int MT>
 __global__ __launch_bounds__(WT_BLOCK) void wt_up_blocks_kernel(WtParams p, int begin, int end) {
-  constexpr int KS = 4 * MT;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int n = p.n_states, ldt = p.ldt;
-  double Af[MT][KS];                                   // the chain matrix as A-operand fragments, for the whole launch
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int row = 16 * i + lr, k = 4 * s + lk;
-      Af[i][s] = (row < n && k < n) ? p.Bc[row * n + k] : 0.0;
-    }
+  const int n = p.n_states;
+  double Af[MT][4 * MT];                               // the chain matrix as A-operand fragments, for the whole launch
+  wt_load_frags(p, lane, Af);
   const int n_lvl = end - begin;
   const int64_t items = (int64_t)n_lvl * p.n_tiles * 4;
-  const int ks_used = (n + 3) >> 2;                    // k-steps whose four input states are all >= n multiply zeros: skipped
+  const int ks_used = (n + 3) >> 2;
   uint32_t err = 0;
   for (int64_t item = (int64_t)blockIdx.x * (WT_BLOCK / 64) + wave; item < items; item += (int64_t)gridDim.x * (WT_BLOCK / 64)) {
     const int nt = (int)(item & 3);
@@ -605,81 +572,19 @@ __global__ __launch_bounds__(WT_BLOCK) void wt_up_blocks_kernel(WtParams p, int 
     const int tile = (int)(q4 % p.n_tiles), li = (int)(q4 / p.n_tiles);
     const UpStep st = p.up[p.up_order[begin + li]];
     const int j = 16 * nt + lr;                        // this lane's replica within the tile
-    double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-    const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
-    const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
+    const WtTile t = wt_tile(p, tile);
     d4_t R[2][MT];
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {                   // ch 0: "first" = child[1] (:508); ch 1: "second" = child[0] (:509)
       const int child = st.child[1 - ch], edge = st.edge[1 - ch];
-      int k = (int)mct[edge * 64 + j] - 1;
-      if (child < 0) {                                 // tip: a row of the chain table (the chain run from a unit vector)
-        const int tip = ~child;
-        const int ts = p.tips_per_replica ? tips_t[tip * 64 + j] : p.tips[tip];
-        if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
-        const double* __restrict__ src = p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * ldt : p.colL + ((size_t)k * n + ts) * ldt;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int row = 16 * i + lk + 4 * q;
-            R[ch][i][q] = (row < n) ? src[row] : 0.0;
-          }
-      } else {                                         // internal child: the chain itself, on the matrix cores
+      if (child < 0) wt_load_rows(wt_tip_row(p, t, child, edge, j, err), 1, n, lk, R[ch]);
+      else {                                           // segment counts differ per replica: run to the longest, keep the lane's own step
         d4_t X[MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int row = 16 * i + lk + 4 * q;
-            X[i][q] = (row < n) ? PLt[((size_t)child * n + row) * 64 + j] : 0.0;
-          }
-#pragma unroll
-        for (int i = 0; i < MT; ++i) R[ch][i] = X[i];
-        const int kmax = wave_max_count(k);            // segment counts differ per replica: run to the longest, keep step k
-        for (int step = 1; step <= kmax; ++step) {
-          d4_t Y[MT];
-#pragma unroll
-          for (int i = 0; i < MT; ++i) {
-            d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-              if (s < ks_used) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[i][s], X[s >> 2][s & 3], acc, 0, 0, 0);
-            Y[i] = acc;
-          }
-          const bool mine = (k == step);
-#pragma unroll
-          for (int i = 0; i < MT; ++i) {
-            X[i] = Y[i];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) R[ch][i][q] = mine ? Y[i][q] : R[ch][i][q];
-          }
-        }
+        wt_load_rows(wt_column(p, t, child, j), 64, n, lk, X);
+        wt_chain(Af, ks_used, X, (int)t.mcount[edge * 64 + j] - 1, R[ch]);
       }
     }
-    d4_t P[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) P[i] = R[0][i] * R[1][i];                     // :510
-    if (p.normalise) {                                                         // :525
-      double t = 0.0;                                  // states lk, lk + 4, lk + 8, ... ascending: partial sum t_lk
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t += P[i][q];
-      t = t + __shfl_xor(t, 16, 64);                   // t_0 + t_1 | t_2 + t_3
-      t = t + __shfl_xor(t, 32, 64);                   // (t_0 + t_1) + (t_2 + t_3)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) P[i][q] = P[i][q] / t;
-    }
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = 16 * i + lk + 4 * q;
-        if (row < n) PLt[((size_t)st.parent * n + row) * 64 + j] = P[i][q];
-      }
+    wt_finish(p, wt_column(p, t, st.parent, j), lk, R[0], R[1]);
   }
   if (err) atomicOr(p.err, err);
 }
@@ -696,13 +601,10 @@ __global__ __launch_bounds__(64 * MT) void wt_up_msplit_kernel(WtParams p, int b
   __shared__ double sP[NP * 16];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int n = p.n_states, ldt = p.ldt;
+  const int n = p.n_states;
   double Af[KS];                                        // row block w of the chain matrix as A-operand fragments
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const int row = 16 * w + lr, k = 4 * s + lk;
-    Af[s] = (row < n && k < n) ? p.Bc[row * n + k] : 0.0;
-  }
+  for (int s = 0; s < KS; ++s) Af[s] = wt_bc_entry(p, 16 * w + lr, 4 * s + lk);
   const int n_lvl = end - begin;
   const int64_t items = (int64_t)n_lvl * p.n_tiles * 4;
   const int ks_used = (n + 3) >> 2;
@@ -712,9 +614,7 @@ __global__ __launch_bounds__(64 * MT) void wt_up_msplit_kernel(WtParams p, int b
     const int64_t q4 = item >> 2;
     const int tile = (int)(q4 % p.n_tiles), li = (int)(q4 / p.n_tiles);
     const UpStep st = p.up[p.up_order[begin + li]];
-    double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-    const uint16_t* __restrict__ mct = p.mcount + (size_t)tile * p.n_edge * 64;
-    const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
+    const WtTile t = wt_tile(p, tile);
     // (blocks in replica order: dealing the replicas to the blocks by chain length, as the per-tile kernel does, was measured here
     //  too -- the rank computation and the 8-byte gathers it forces cost more than the shorter chains return: 0.66 vs 0.77 G/s on C4
     //  at 4 096 replicas)
@@ -723,26 +623,12 @@ __global__ __launch_bounds__(64 * MT) void wt_up_msplit_kernel(WtParams p, int b
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {                   // ch 0: "first" = child[1] (:508); ch 1: "second" = child[0] (:509)
       const int child = st.child[1 - ch], edge = st.edge[1 - ch];
-      int k = (int)mct[edge * 64 + j] - 1;
-      if (child < 0) {
-        const int tip = ~child;
-        const int ts = p.tips_per_replica ? tips_t[tip * 64 + j] : p.tips[tip];
-        if (k >= p.klong) { err |= DERR_CAPACITY; k = p.klong - 1; }
-        const double* __restrict__ src = p.tip_masks ? p.maskL + ((size_t)k * 2 + (ts & 1)) * ldt : p.colL + ((size_t)k * n + ts) * ldt;
+      if (child < 0) R[ch] = wt_load_tile(wt_tip_row(p, t, child, edge, j, err), 1, n, 16 * w + lk);
+      else {
+        R[ch] = wt_load_tile(wt_column(p, t, child, j), 64, n, 16 * w + lk);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * w + lk + 4 * q;
-          R[ch][q] = (row < n) ? src[row] : 0.0;
-        }
-      } else {
-        d4_t x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = 16 * w + lk + 4 * q;
-          x[q] = (row < n) ? PLt[((size_t)child * n + row) * 64 + j] : 0.0;
-          sX[0][row * 16 + lr] = x[q];
-        }
-        R[ch] = x;
+        for (int q = 0; q < 4; ++q) sX[0][(16 * w + lk + 4 * q) * 16 + lr] = R[ch][q];
+        const int k = (int)t.mcount[edge * 64 + j] - 1;
         const int kmax = wave_max_count(k);            // the same 16 chain lengths in every wave of the workgroup
         __syncthreads();
         for (int step = 1; step <= kmax; ++step) {
@@ -763,21 +649,22 @@ __global__ __launch_bounds__(64 * MT) void wt_up_msplit_kernel(WtParams p, int b
 #pragma unroll
       for (int q = 0; q < 4; ++q) sP[(16 * w + lk + 4 * q) * 16 + lr] = P[q];
       __syncthreads();
-      double t = 0.0;                                  // states lk, lk + 4, lk + 8, ... ascending: partial sum t_lk
+      double sum = 0.0;                                // states lk, lk + 4, lk + 8, ... ascending: partial sum t_lk, as wt_finish
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) t += sP[(16 * i + lk + 4 * q) * 16 + lr];
-      t = t + __shfl_xor(t, 16, 64);
-      t = t + __shfl_xor(t, 32, 64);
+        for (int q = 0; q < 4; ++q) sum += sP[(16 * i + lk + 4 * q) * 16 + lr];
+      sum = sum + __shfl_xor(sum, 16, 64);
+      sum = sum + __shfl_xor(sum, 32, 64);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) P[q] = P[q] / t;
+      for (int q = 0; q < 4; ++q) P[q] = P[q] / sum;
       __syncthreads();                                 // sP is rewritten by the next item
     }
+    double* __restrict__ out = wt_column(p, t, st.parent, j);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = 16 * w + lk + 4 * q;
-      if (row < n) PLt[((size_t)st.parent * n + row) * 64 + j] = P[q];
+      if (row < n) out[(size_t)row * 64] = P[q];
     }
   }
   if (err) atomicOr(p.err, err);
@@ -810,6 +697,41 @@ __global__ __launch_bounds__(WT_BLOCK) void wt_root_kernel(WtParams p, int it) {
 // numbers.  A wave is a workgroup of its own.  C4 at 65 536 replicas: two passes (32 states per round of loads) 6.7 ms per sweep;
 // two passes with the second one confined to the 16-state block the threshold falls into 5.5; one pass with all 122 values in
 // registers (one wave per SIMD) 6.2; this form 4.5 (profiles/r04_probe_c4_variants.log).
+
+// What the two kernels share.  Before the sums: the parent's state, and for an edge that is drawn (an internal child; ks: a tip too,
+// against its parity mask) the lane's row of the chain table (clamped and flagged beyond the table), the child's column of PL or
+// the tip's parity, and the uniform.  A plain tip is not drawn: its state is its datum (:612).
+struct WtDraw {
+  int ps, cs;                                          // the parent's state; the child's, where it is not drawn
+  bool drawn, internal;
+  int par;                                             // a drawn tip: its parity (the vector drawn against is 1 at the states of that parity)
+  const double2* row;                                  // e_ps^T B^(m-1), padded to ldt (even) with zeros
+  const double* PLc;                                   // state c of an internal child at [c * 64]
+  double u;
+};
+__device__ __forceinline__ WtDraw wt_draw_begin(const WtParams& p, const WtTile& t, int it, int tile, const DownStep& ds, int lane, uint32_t& err) {
+  WtDraw d = {};
+  d.ps = t.nstate[ds.parent * 64 + lane];
+  d.internal = ds.child >= 0;
+  d.drawn = d.internal || p.tip_masks;
+  const int ts = d.internal ? 0 : wt_tip_state(p, t, ~ds.child, lane);
+  d.cs = ts; d.par = ts & 1;
+  if (!d.drawn) return d;
+  int kk = (int)t.mcount[ds.edge * 64 + lane] - 1;
+  if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
+  d.row = reinterpret_cast<const double2*>(p.rowL + ((size_t)kk * p.n_states + d.ps) * p.ldt);
+  d.PLc = wt_column(p, t, d.internal ? ds.child : 0, lane);
+  const uint32_t node_id = d.internal ? (uint32_t)(ds.child + p.n_tips) : (uint32_t)~ds.child;
+  const uint32_t rep = (uint32_t)(p.replica_offset + tile * 64 + lane);
+  d.u = stream_u(p.seed_lo, p.seed_hi, rep, (uint32_t)it, ENT_NODE | node_id, 0);
+  return d;
+}
+// an internal child's state to the node states (:655), both ends of the edge to the branch kernel (updatenodestates :460-475)
+__device__ __forceinline__ void wt_draw_end(const WtParams& p, const WtTile& t, int tile, const DownStep& ds, int lane, int ps, int cs) {
+  if (ds.child >= 0) t.nstate[ds.child * 64 + lane] = (uint8_t)cs;
+  p.estate[((size_t)tile * p.n_edge + ds.edge) * 64 + lane] = (uint16_t)(ps | (cs << 8));
+}
+
 template <int MT>
 __global__ __launch_bounds__(64) void wt_down1_kernel(WtParams p, int it, int begin, int end) {
   constexpr int NP = 16 * MT;
@@ -818,29 +740,18 @@ __global__ __launch_bounds__(64) void wt_down1_kernel(WtParams p, int it, int be
   const int lane = threadIdx.x;
   const int item = blockIdx.x;
   const int n_lvl = end - begin;
-  const int n = p.n_states, ldt = p.ldt;
+  const int n = p.n_states;
   const int tile = item / n_lvl;
   const DownStep ds = p.down[p.down_order[begin + item % n_lvl]];
-  const int b = ds.edge;
-  const double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-  uint8_t* __restrict__ nst = p.nstate + (size_t)tile * p.n_node * 64;
-  const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
-  const uint32_t rep = (uint32_t)(p.replica_offset + tile * 64 + lane);
-  const int m = p.mcount[((size_t)tile * p.n_edge + b) * 64 + lane];
-  const int ps = nst[ds.parent * 64 + lane];
+  const WtTile t = wt_tile(p, tile);
   uint32_t err = 0;
-  int cs;
-  if (ds.child >= 0 || p.tip_masks) {
-    int kk = m - 1;
-    if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
-    const double2* __restrict__ src = reinterpret_cast<const double2*>(p.rowL + ((size_t)kk * n + ps) * ldt);
-    uint32_t node_id;
-    const bool internal = ds.child >= 0;
-    const double* __restrict__ PLc = PLt + (size_t)(internal ? ds.child : 0) * n * 64 + lane;
-    int par = 0;
-    if (internal) node_id = (uint32_t)(ds.child + p.n_tips);
-    else { const int tip = ~ds.child; par = (p.tips_per_replica ? tips_t[tip * 64 + lane] : p.tips[tip]) & 1; node_id = (uint32_t)tip; }
-    const double u = stream_u(p.seed_lo, p.seed_hi, rep, (uint32_t)it, ENT_NODE | node_id, 0);
+  const WtDraw d = wt_draw_begin(p, t, it, tile, ds, lane, err);
+  int cs = d.cs;
+  if (d.drawn) {
+    const double2* __restrict__ src = d.row;
+    const double* __restrict__ PLc = d.PLc;
+    const bool internal = d.internal;
+    const int par = d.par;
     // First half (states 0 .. 31): loads, products, running sums -> LDS ([state][lane], 16 KB); second half: the same with the sums
     // left in registers.  Nothing of the first half stays in registers while the second half's loads are in flight.
     double cum = 0.0;
@@ -873,18 +784,14 @@ __global__ __launch_bounds__(64) void wt_down1_kernel(WtParams p, int it, int be
     }
     const double total = cum;
     if (!(total > 0.0) || isinf(total)) err |= DERR_ZERO_PROB;
-    const double thr = u * total;
+    const double thr = d.u * total;
     cs = 0;
 #pragma unroll
     for (int j = 0; j < NP - 32; ++j) cs += (32 + j < n - 1 && !(thr <= hi[j])) ? 1 : 0;
 #pragma unroll
     for (int j = 0; j < 32; ++j) cs += !(thr <= s_cum[j * 64 + lane]) ? 1 : 0;     // n > 32: states 0 .. 31 are all <= n - 2
-    if (internal) nst[ds.child * 64 + lane] = (uint8_t)cs;                                   // :655
-  } else {
-    const int tip = ~ds.child;
-    cs = p.tips_per_replica ? tips_t[tip * 64 + lane] : p.tips[tip];            // :612
   }
-  p.estate[((size_t)tile * p.n_edge + b) * 64 + lane] = (uint16_t)(ps | (cs << 8));   // updatenodestates :460-475
+  wt_draw_end(p, t, tile, ds, lane, d.ps, cs);
   if (err) atomicOr(p.err, err);
 }
 
@@ -892,26 +799,15 @@ __global__ __launch_bounds__(64) void wt_down1_kernel(WtParams p, int it, int be
 // (tile, edge), four waves per workgroup.  C5: 4.05 -> 3.49 ms per sweep against the two-pass form (55 registers, eight waves per SIMD).
 template <int NP>
 __device__ __forceinline__ void wt_down1r_edge(const WtParams& p, int it, int tile, const DownStep& ds, int lane, uint32_t& err) {
-  const int n = p.n_states, ldt = p.ldt;
-  const int b = ds.edge;
-  const double* __restrict__ PLt = p.PL + (size_t)tile * p.n_node * n * 64;
-  uint8_t* __restrict__ nst = p.nstate + (size_t)tile * p.n_node * 64;
-  const uint8_t* __restrict__ tips_t = p.tips_per_replica ? p.tips + (size_t)tile * p.n_tips * 64 : p.tips;
-  const uint32_t rep = (uint32_t)(p.replica_offset + tile * 64 + lane);
-  const int m = p.mcount[((size_t)tile * p.n_edge + b) * 64 + lane];
-  const int ps = nst[ds.parent * 64 + lane];
-  int cs;
-  if (ds.child >= 0 || p.tip_masks) {
-    int kk = m - 1;
-    if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
-    const double2* __restrict__ src = reinterpret_cast<const double2*>(p.rowL + ((size_t)kk * n + ps) * ldt);
-    uint32_t node_id;
-    const bool internal = ds.child >= 0;
-    const double* __restrict__ PLc = PLt + (size_t)(internal ? ds.child : 0) * n * 64 + lane;
-    int par = 0;
-    if (internal) node_id = (uint32_t)(ds.child + p.n_tips);
-    else { const int tip = ~ds.child; par = (p.tips_per_replica ? tips_t[tip * 64 + lane] : p.tips[tip]) & 1; node_id = (uint32_t)tip; }
-    const double u = stream_u(p.seed_lo, p.seed_hi, rep, (uint32_t)it, ENT_NODE | node_id, 0);
+  const int n = p.n_states;
+  const WtTile t = wt_tile(p, tile);
+  const WtDraw d = wt_draw_begin(p, t, it, tile, ds, lane, err);
+  int cs = d.cs;
+  if (d.drawn) {
+    const double2* __restrict__ src = d.row;
+    const double* __restrict__ PLc = d.PLc;
+    const bool internal = d.internal;
+    const int par = d.par;
     double2 r[NP / 2];
     double pl[NP];
 #pragma unroll
@@ -925,16 +821,12 @@ __device__ __forceinline__ void wt_down1r_edge(const WtParams& p, int it, int ti
       pl[c] = cum;
     }
     if (!(cum > 0.0) || isinf(cum)) err |= DERR_ZERO_PROB;
-    const double thr = u * cum;
+    const double thr = d.u * cum;
     cs = 0;
 #pragma unroll
     for (int c = 0; c < NP; ++c) cs += (c < n - 1 && !(thr <= pl[c])) ? 1 : 0;
-    if (internal) nst[ds.child * 64 + lane] = (uint8_t)cs;                                   // :655
-  } else {
-    const int tip = ~ds.child;
-    cs = p.tips_per_replica ? tips_t[tip * 64 + lane] : p.tips[tip];            // :612
   }
-  p.estate[((size_t)tile * p.n_edge + b) * 64 + lane] = (uint16_t)(ps | (cs << 8));   // updatenodestates :460-475
+  wt_draw_end(p, t, tile, ds, lane, d.ps, cs);
 }
 
 template <int NP>
@@ -1403,29 +1295,33 @@ hipError_t launch_up_levels(const WtParams& p, const std::vector<int32_t>& up_of
     const int cnt = up_off[l + 1] - up_off[l];
     if (cnt <= 0) continue;
     const bool split = p.up_form == 2 || (p.up_form == 0 && (MT >= 2 ? p.n_tiles < msplit_tiles : few_tiles));
-    if (MT >= 2 && split) {
-      const int64_t items = (int64_t)cnt * p.n_tiles * 4;    // a workgroup of MT waves per (node, tile, block)
-      const unsigned grid = (unsigned)std::min<int64_t>(items, 4096);
-      hipLaunchKernelGGL(wt_up_msplit_kernel<MT>, dim3(grid), dim3(64 * MT), 0, stream, p, up_off[l], up_off[l + 1]);
-    } else if (split) {
-      const int64_t items = (int64_t)cnt * p.n_tiles * 4;    // a wave per (node, tile, block)
-      const unsigned grid = (unsigned)std::min<int64_t>((items + 3) / 4, 2048);
-      hipLaunchKernelGGL(wt_up_blocks_kernel<MT>, dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]);
-    } else if (MT >= 2 && p.up_form != 1) {             // up_form 1 keeps the kernel with the matrix in registers (measurement)
-      const int64_t items = (int64_t)cnt * p.n_tiles;        // a wave per (node, tile), two (17 .. 32 states: three) waves per SIMD
-      constexpr int M2 = MT >= 2 ? MT : 2;
-      const unsigned grid = (unsigned)std::min<int64_t>((items + 3) / 4, 256 * wt_up2_waves(M2));      // persistent workgroups
-      switch ((p.n_states + 3) / 4 - 4 * (M2 - 1)) {         // k-steps in the last row block: 1 .. 4
-        case 1: hipLaunchKernelGGL((wt_up2_kernel<M2, 4 * M2 - 3>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
-        case 2: hipLaunchKernelGGL((wt_up2_kernel<M2, 4 * M2 - 2>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
-        case 3: hipLaunchKernelGGL((wt_up2_kernel<M2, 4 * M2 - 1>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
-        default: hipLaunchKernelGGL((wt_up2_kernel<M2, 4 * M2>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
+    const int64_t items = (int64_t)cnt * p.n_tiles;          // (node, tile)
+    if (split) {
+      if constexpr (MT >= 2) {                               // a workgroup of MT waves per (node, tile, block)
+        const unsigned grid = (unsigned)std::min<int64_t>(4 * items, 4096);
+        hipLaunchKernelGGL(wt_up_msplit_kernel<MT>, dim3(grid), dim3(64 * MT), 0, stream, p, up_off[l], up_off[l + 1]);
+      } else {                                               // a wave per (node, tile, block)
+        const unsigned grid = (unsigned)std::min<int64_t>(items, 2048);
+        hipLaunchKernelGGL(wt_up_blocks_kernel<MT>, dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]);
       }
-    } else {
-      const int64_t items = (int64_t)cnt * p.n_tiles;        // a wave per (node, tile)
-      const unsigned grid = (unsigned)std::min<int64_t>((items + 3) / 4, 2048);      // persistent waves: the matrix fragments load once
-      hipLaunchKernelGGL(wt_up_kernel<MT>, dim3(grid), dim3(WT_BLOCK), lds, stream, p, up_off[l], up_off[l + 1]);
+      continue;
     }
+    if constexpr (MT >= 2) {
+      if (p.up_form != 1) {                                  // up_form 1 keeps the kernel with the matrix in registers (measurement)
+        // a wave per (node, tile), two (17 .. 32 states: three) waves per SIMD; persistent workgroups
+        const unsigned grid = (unsigned)std::min<int64_t>((items + 3) / 4, 256 * wt_up2_waves(MT));
+        switch ((p.n_states + 3) / 4 - 4 * (MT - 1)) {       // k-steps in the last row block: 1 .. 4
+          case 1: hipLaunchKernelGGL((wt_up2_kernel<MT, 4 * MT - 3>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
+          case 2: hipLaunchKernelGGL((wt_up2_kernel<MT, 4 * MT - 2>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
+          case 3: hipLaunchKernelGGL((wt_up2_kernel<MT, 4 * MT - 1>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
+          default: hipLaunchKernelGGL((wt_up2_kernel<MT, 4 * MT>), dim3(grid), dim3(WT_BLOCK), 0, stream, p, up_off[l], up_off[l + 1]); break;
+        }
+        continue;
+      }
+    }
+    // a wave per (node, tile); persistent waves: the matrix fragments load once
+    const unsigned grid = (unsigned)std::min<int64_t>((items + 3) / 4, 2048);
+    hipLaunchKernelGGL(wt_up_kernel<MT>, dim3(grid), dim3(WT_BLOCK), lds, stream, p, up_off[l], up_off[l + 1]);
   }
   return hipSuccess;
 }

@@ -61,14 +61,15 @@ def _reduced_is_the_sum(case, red, per):
         np.testing.assert_array_equal(red[:, -1], per.sum(0)[:, -1])
 
 
-DENSE = W.dense_cases()
+DENSE = W.dense_cases() + W.ks_form_cases()
 
 
 @pytest.mark.parametrize("case", DENSE, ids=[c.name for c in DENSE])
 def test_dense_every_pruning_form_against_the_oracle_and_each_other(case):
     """bottom and top of every class of ceil(n / 4) from 2 to 16, 150 replicas (22 live lanes in the third tile): the automatic
     form (few tiles: row-split workgroups, or a wave per block up to 16 states), the matrix in registers (1), the split forced (2)
-    and, from 17 states, the matrix in LDS (3: wt_up2_kernel<MT, ceil(n / 4)>) -- the same bits from each (phm_wtiles.hip's header)"""
+    and, from 17 states, the matrix in LDS (3: wt_up2_kernel<MT, ceil(n / 4)>) -- the same bits from each (phm_wtiles.hip's header).
+    The ks sweep at 12 and 34 states likewise (70 replicas): its tips are rows of the parity-mask table in every form"""
     first = None
     for run in case.runs:
         got, d = _engine_run(case, run, dump_replica=case.S - 1)

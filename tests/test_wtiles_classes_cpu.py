@@ -15,13 +15,14 @@ IDS = [c.name for c in ALL]
 def test_class_table_counts_and_ranges():
     """the table against the counts the kernel file's launchers spell out, and every n from 5 to 64 in exactly one class per family"""
     fam = {}
-    for name, (ns, _) in W.ALL_CLASSES.items():
+    for name, ns in W.ALL_CLASSES.items():
         fam.setdefault(name.split("<")[0], []).append((name, ns))
     assert {k: len(v) for k, v in fam.items()} == {
-        "wt_root_kernel": 1, "wt_stats_kernel": 1, "wt_up_kernel": 4, "wt_up_blocks_kernel": 4, "wt_up_msplit_kernel": 4, "wt_up2_kernel": 12,
+        "wt_root_kernel": 1, "wt_stats_kernel": 1, "wt_up_kernel": 4, "wt_up_blocks_kernel": 1, "wt_up_msplit_kernel": 3, "wt_up2_kernel": 12,
         "wt_up_band_kernel": 14, "wt_up_band_cluster_kernel": 14, "wt_down1r_kernel": 7, "wt_down1r_cluster_kernel": 7, "wt_down1_kernel": 2,
         "wt_branch_kernel": 10}
-    for k, lo, hi in (("wt_up_kernel", 5, 64), ("wt_up_blocks_kernel", 5, 64), ("wt_up_msplit_kernel", 5, 64), ("wt_up2_kernel", 17, 64),
+    assert len(W.ALL_CLASSES) == 76 and W.REACHABLE == set(W.ALL_CLASSES)
+    for k, lo, hi in (("wt_up_kernel", 5, 64), ("wt_up_blocks_kernel", 5, 16), ("wt_up_msplit_kernel", 17, 64), ("wt_up2_kernel", 17, 64),
                       ("wt_down1r_kernel", 5, 32), ("wt_down1r_cluster_kernel", 5, 32), ("wt_down1_kernel", 33, 64)):
         assert sorted(n for _, ns in fam[k] for n in ns) == list(range(lo, hi + 1)), k
     for name, ns in fam["wt_up2_kernel"]:
@@ -31,19 +32,17 @@ def test_class_table_counts_and_ranges():
         for name, ns in fam[k]:
             npad, hb = (int(a) for a in name[name.index("<") + 1:-1].split(","))
             assert all(4 * W.ceil_div(n, 4) == npad and 2 * hb + 1 < n for n in ns) and (ns[0] == npad - 3 or 2 * hb + 1 >= npad - 3), name
-    unreachable = {k for k, (_, why) in W.ALL_CLASSES.items() if why}
-    assert unreachable == {"wt_up_blocks_kernel<2>", "wt_up_blocks_kernel<3>", "wt_up_blocks_kernel<4>", "wt_up_msplit_kernel<1>"}
 
 
 def test_cases_cover_every_reachable_instantiation():
-    """no reachable entry of the table without a case whose dispatch names it, no answer of the dispatch outside the table, and every
-    case at an n its kernels are listed for"""
+    """no entry of the table -- every instantiation the kernel file holds -- without a case whose dispatch names it, no answer of the
+    dispatch outside the table, and every case at an n its kernels are listed for"""
     seen = {}
     for c in ALL:
         for run in c.runs:
             for k in c.kernels(run):
-                assert k in W.ALL_CLASSES and W.ALL_CLASSES[k][1] is None, (c.name, run, k)
-                assert c.n in W.ALL_CLASSES[k][0], (c.name, k)
+                assert k in W.ALL_CLASSES, (c.name, run, k)
+                assert c.n in W.ALL_CLASSES[k], (c.name, k)
                 seen.setdefault(k, set()).add(c.n)
     assert set(seen) == W.REACHABLE, sorted(W.REACHABLE - set(seen))
     # the instantiations the suite had never run, by name
@@ -92,8 +91,8 @@ def test_dense_cases_sit_on_the_class_edges():
 @pytest.mark.parametrize("npad,hb", W.BAND_CLASSES)
 def test_band_cases_sit_on_the_class_edges(npad, hb):
     lo, hi = W.band_ns(npad, hb)
-    assert (lo, hi) == (max(npad - 3, 2 * hb + 2), npad) and lo in W.ALL_CLASSES["wt_up_band_kernel<%d, %d>" % (npad, hb)][0]
-    assert lo - 1 not in W.ALL_CLASSES["wt_up_band_kernel<%d, %d>" % (npad, hb)][0]
+    assert (lo, hi) == (max(npad - 3, 2 * hb + 2), npad) and lo in W.ALL_CLASSES["wt_up_band_kernel<%d, %d>" % (npad, hb)]
+    assert lo - 1 not in W.ALL_CLASSES["wt_up_band_kernel<%d, %d>" % (npad, hb)]
     if npad == 8:
         assert lo == {1: 5, 2: 6}[hb]                     # the smallest n the host rule accepts
     else:
@@ -142,6 +141,14 @@ def test_b2l_slot_and_ks_cases_are_what_they_are_named_for():
         c = W.ks_small_case(kind, n)
         assert RC.slot_class(c.B) == slots == W.slot_count(c.B, "ks")
         assert all("wt_branch_kernel<true, true, true, %d>" % band in c.kernels(r) for r in c.runs)
+    # mask tip rows in every pruning form: the matrix-core kernels of one and of three row blocks, none replaced by a band kernel
+    up = {12: ("wt_up_blocks_kernel<1>", "wt_up_kernel<1>", "wt_up_blocks_kernel<1>"),
+          34: ("wt_up_msplit_kernel<3>", "wt_up_kernel<3>", "wt_up_msplit_kernel<3>", "wt_up2_kernel<3, 9>")}
+    for n in W.KS_FORM_NS:
+        c = W.ks_form_case(n)
+        assert c.ks and c.S == 70 and c.N == 6 and len(c.z["states"]) == 14 and set(c.z["states"].tolist()) <= {1, 2}
+        assert [r["pruning_form"] for r in c.runs] == list(W.dense_forms(n)) and len(up[n]) == len(c.runs)
+        assert all(k in c.kernels(r) for k, r in zip(up[n], c.runs)), [sorted(c.kernels(r)) for r in c.runs]
 
 
 @pytest.mark.parametrize("case", ALL, ids=IDS)

@@ -103,62 +103,58 @@ def branch_paths(n, B, variant, reduce):
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Every instantiation the launchers of phm_wtiles.hip hold, written out by hand from the kernel file and not derived from
-# ``dispatch``: (kernel, template arguments, smallest n, largest n, why no public entry point reaches it or None)
+# ``dispatch``: (kernel, template arguments, smallest n, largest n)
 # ---------------------------------------------------------------------------------------------------------------------------
-_SPLIT_HI = "launch_up_levels<MT >= 2> sends every split level to wt_up_msplit_kernel; instantiated only"
-_SPLIT_LO = "launch_up_levels<1> sends every split level to wt_up_blocks_kernel<1>; instantiated only"
 _T, _F = True, False
 _TABLE = (
-    ("wt_root_kernel", (), 5, 64, None), ("wt_stats_kernel", (), 5, 64, None),
+    ("wt_root_kernel", (), 5, 64), ("wt_stats_kernel", (), 5, 64),
     # the matrix in registers: pruning_form 1; <1> also pruning_form 3 and from WT_FEW_TILES tiles on
-    ("wt_up_kernel", (1,), 5, 16, None), ("wt_up_kernel", (2,), 17, 32, None), ("wt_up_kernel", (3,), 33, 48, None),
-    ("wt_up_kernel", (4,), 49, 64, None),
+    ("wt_up_kernel", (1,), 5, 16), ("wt_up_kernel", (2,), 17, 32), ("wt_up_kernel", (3,), 33, 48),
+    ("wt_up_kernel", (4,), 49, 64),
     # few tiles: a wave per 16-replica block (n <= 16), a workgroup of MT waves per block (n >= 17)
-    ("wt_up_blocks_kernel", (1,), 5, 16, None), ("wt_up_blocks_kernel", (2,), 17, 32, _SPLIT_HI),
-    ("wt_up_blocks_kernel", (3,), 33, 48, _SPLIT_HI), ("wt_up_blocks_kernel", (4,), 49, 64, _SPLIT_HI),
-    ("wt_up_msplit_kernel", (1,), 5, 16, _SPLIT_LO), ("wt_up_msplit_kernel", (2,), 17, 32, None),
-    ("wt_up_msplit_kernel", (3,), 33, 48, None), ("wt_up_msplit_kernel", (4,), 49, 64, None),
+    ("wt_up_blocks_kernel", (1,), 5, 16), ("wt_up_msplit_kernel", (2,), 17, 32),
+    ("wt_up_msplit_kernel", (3,), 33, 48), ("wt_up_msplit_kernel", (4,), 49, 64),
     # the matrix in LDS, <MT, KSU = ceil(n / 4)>: twelve schedules of MT * KSU fragments in chunks of eight
-    ("wt_up2_kernel", (2, 5), 17, 20, None), ("wt_up2_kernel", (2, 6), 21, 24, None), ("wt_up2_kernel", (2, 7), 25, 28, None),
-    ("wt_up2_kernel", (2, 8), 29, 32, None), ("wt_up2_kernel", (3, 9), 33, 36, None), ("wt_up2_kernel", (3, 10), 37, 40, None),
-    ("wt_up2_kernel", (3, 11), 41, 44, None), ("wt_up2_kernel", (3, 12), 45, 48, None), ("wt_up2_kernel", (4, 13), 49, 52, None),
-    ("wt_up2_kernel", (4, 14), 53, 56, None), ("wt_up2_kernel", (4, 15), 57, 60, None), ("wt_up2_kernel", (4, 16), 61, 64, None),
+    ("wt_up2_kernel", (2, 5), 17, 20), ("wt_up2_kernel", (2, 6), 21, 24), ("wt_up2_kernel", (2, 7), 25, 28),
+    ("wt_up2_kernel", (2, 8), 29, 32), ("wt_up2_kernel", (3, 9), 33, 36), ("wt_up2_kernel", (3, 10), 37, 40),
+    ("wt_up2_kernel", (3, 11), 41, 44), ("wt_up2_kernel", (3, 12), 45, 48), ("wt_up2_kernel", (4, 13), 49, 52),
+    ("wt_up2_kernel", (4, 14), 53, 56), ("wt_up2_kernel", (4, 15), 57, 60), ("wt_up2_kernel", (4, 16), 61, 64),
     # banded chain matrix <NP, HB>, a launch per level; the host wants 2 HB + 1 < n
-    ("wt_up_band_kernel", (8, 1), 5, 8, None), ("wt_up_band_kernel", (8, 2), 6, 8, None),
-    ("wt_up_band_kernel", (12, 1), 9, 12, None), ("wt_up_band_kernel", (12, 2), 9, 12, None),
-    ("wt_up_band_kernel", (16, 1), 13, 16, None), ("wt_up_band_kernel", (16, 2), 13, 16, None),
-    ("wt_up_band_kernel", (20, 1), 17, 20, None), ("wt_up_band_kernel", (20, 2), 17, 20, None),
-    ("wt_up_band_kernel", (24, 1), 21, 24, None), ("wt_up_band_kernel", (24, 2), 21, 24, None),
-    ("wt_up_band_kernel", (28, 1), 25, 28, None), ("wt_up_band_kernel", (28, 2), 25, 28, None),
-    ("wt_up_band_kernel", (32, 1), 29, 32, None), ("wt_up_band_kernel", (32, 2), 29, 32, None),
+    ("wt_up_band_kernel", (8, 1), 5, 8), ("wt_up_band_kernel", (8, 2), 6, 8),
+    ("wt_up_band_kernel", (12, 1), 9, 12), ("wt_up_band_kernel", (12, 2), 9, 12),
+    ("wt_up_band_kernel", (16, 1), 13, 16), ("wt_up_band_kernel", (16, 2), 13, 16),
+    ("wt_up_band_kernel", (20, 1), 17, 20), ("wt_up_band_kernel", (20, 2), 17, 20),
+    ("wt_up_band_kernel", (24, 1), 21, 24), ("wt_up_band_kernel", (24, 2), 21, 24),
+    ("wt_up_band_kernel", (28, 1), 25, 28), ("wt_up_band_kernel", (28, 2), 25, 28),
+    ("wt_up_band_kernel", (32, 1), 29, 32), ("wt_up_band_kernel", (32, 2), 29, 32),
     # the same over subtree clusters (a deep tree, or level_groups >= 2)
-    ("wt_up_band_cluster_kernel", (8, 1), 5, 8, None), ("wt_up_band_cluster_kernel", (8, 2), 6, 8, None),
-    ("wt_up_band_cluster_kernel", (12, 1), 9, 12, None), ("wt_up_band_cluster_kernel", (12, 2), 9, 12, None),
-    ("wt_up_band_cluster_kernel", (16, 1), 13, 16, None), ("wt_up_band_cluster_kernel", (16, 2), 13, 16, None),
-    ("wt_up_band_cluster_kernel", (20, 1), 17, 20, None), ("wt_up_band_cluster_kernel", (20, 2), 17, 20, None),
-    ("wt_up_band_cluster_kernel", (24, 1), 21, 24, None), ("wt_up_band_cluster_kernel", (24, 2), 21, 24, None),
-    ("wt_up_band_cluster_kernel", (28, 1), 25, 28, None), ("wt_up_band_cluster_kernel", (28, 2), 25, 28, None),
-    ("wt_up_band_cluster_kernel", (32, 1), 29, 32, None), ("wt_up_band_cluster_kernel", (32, 2), 29, 32, None),
+    ("wt_up_band_cluster_kernel", (8, 1), 5, 8), ("wt_up_band_cluster_kernel", (8, 2), 6, 8),
+    ("wt_up_band_cluster_kernel", (12, 1), 9, 12), ("wt_up_band_cluster_kernel", (12, 2), 9, 12),
+    ("wt_up_band_cluster_kernel", (16, 1), 13, 16), ("wt_up_band_cluster_kernel", (16, 2), 13, 16),
+    ("wt_up_band_cluster_kernel", (20, 1), 17, 20), ("wt_up_band_cluster_kernel", (20, 2), 17, 20),
+    ("wt_up_band_cluster_kernel", (24, 1), 21, 24), ("wt_up_band_cluster_kernel", (24, 2), 21, 24),
+    ("wt_up_band_cluster_kernel", (28, 1), 25, 28), ("wt_up_band_cluster_kernel", (28, 2), 25, 28),
+    ("wt_up_band_cluster_kernel", (32, 1), 29, 32), ("wt_up_band_cluster_kernel", (32, 2), 29, 32),
     # node draws <NP> per level and over clusters (n <= 32), <MT> in one pass beyond
-    ("wt_down1r_kernel", (8,), 5, 8, None), ("wt_down1r_kernel", (12,), 9, 12, None), ("wt_down1r_kernel", (16,), 13, 16, None),
-    ("wt_down1r_kernel", (20,), 17, 20, None), ("wt_down1r_kernel", (24,), 21, 24, None), ("wt_down1r_kernel", (28,), 25, 28, None),
-    ("wt_down1r_kernel", (32,), 29, 32, None),
-    ("wt_down1r_cluster_kernel", (8,), 5, 8, None), ("wt_down1r_cluster_kernel", (12,), 9, 12, None),
-    ("wt_down1r_cluster_kernel", (16,), 13, 16, None), ("wt_down1r_cluster_kernel", (20,), 17, 20, None),
-    ("wt_down1r_cluster_kernel", (24,), 21, 24, None), ("wt_down1r_cluster_kernel", (28,), 25, 28, None),
-    ("wt_down1r_cluster_kernel", (32,), 29, 32, None),
-    ("wt_down1_kernel", (3,), 33, 48, None), ("wt_down1_kernel", (4,), 49, 64, None),
+    ("wt_down1r_kernel", (8,), 5, 8), ("wt_down1r_kernel", (12,), 9, 12), ("wt_down1r_kernel", (16,), 13, 16),
+    ("wt_down1r_kernel", (20,), 17, 20), ("wt_down1r_kernel", (24,), 21, 24), ("wt_down1r_kernel", (28,), 25, 28),
+    ("wt_down1r_kernel", (32,), 29, 32),
+    ("wt_down1r_cluster_kernel", (8,), 5, 8), ("wt_down1r_cluster_kernel", (12,), 9, 12),
+    ("wt_down1r_cluster_kernel", (16,), 13, 16), ("wt_down1r_cluster_kernel", (20,), 17, 20),
+    ("wt_down1r_cluster_kernel", (24,), 21, 24), ("wt_down1r_cluster_kernel", (28,), 25, 28),
+    ("wt_down1r_cluster_kernel", (32,), 29, 32),
+    ("wt_down1_kernel", (3,), 33, 48), ("wt_down1_kernel", (4,), 49, 64),
     # branch paths <KS, SMALL, B2L, BAND>
-    ("wt_branch_kernel", (_F, _T, _T, 0), 5, 32, None), ("wt_branch_kernel", (_F, _T, _T, 1), 5, 32, None),
-    ("wt_branch_kernel", (_F, _T, _T, 2), 6, 32, None), ("wt_branch_kernel", (_F, _F, _F, 0), 33, 64, None),
-    ("wt_branch_kernel", (_F, _F, _T, 0), 33, 64, None),
-    ("wt_branch_kernel", (_T, _T, _T, 0), 5, 32, None), ("wt_branch_kernel", (_T, _T, _T, 1), 5, 32, None),
-    ("wt_branch_kernel", (_T, _T, _T, 2), 6, 32, None), ("wt_branch_kernel", (_T, _F, _F, 0), 33, 64, None),
-    ("wt_branch_kernel", (_T, _F, _T, 0), 33, 64, None),
+    ("wt_branch_kernel", (_F, _T, _T, 0), 5, 32), ("wt_branch_kernel", (_F, _T, _T, 1), 5, 32),
+    ("wt_branch_kernel", (_F, _T, _T, 2), 6, 32), ("wt_branch_kernel", (_F, _F, _F, 0), 33, 64),
+    ("wt_branch_kernel", (_F, _F, _T, 0), 33, 64),
+    ("wt_branch_kernel", (_T, _T, _T, 0), 5, 32), ("wt_branch_kernel", (_T, _T, _T, 1), 5, 32),
+    ("wt_branch_kernel", (_T, _T, _T, 2), 6, 32), ("wt_branch_kernel", (_T, _F, _F, 0), 33, 64),
+    ("wt_branch_kernel", (_T, _F, _T, 0), 33, 64),
 )
-ALL_CLASSES = {kname(k, *targs): (range(lo, hi + 1), why) for k, targs, lo, hi, why in _TABLE}
+ALL_CLASSES = {kname(k, *targs): range(lo, hi + 1) for k, targs, lo, hi in _TABLE}
 assert len(ALL_CLASSES) == len(_TABLE)
-REACHABLE = frozenset(k for k, (_, why) in ALL_CLASSES.items() if why is None)
+REACHABLE = frozenset(ALL_CLASSES)                                              # the launchers name no kernel they cannot launch
 
 _TRACE_NAME = re.compile(r"\b(wt_[a-z0-9_]+_kernel)\s*(<[^>]*>)?")
 
@@ -346,6 +342,27 @@ def ks_small_cases():
     return [ks_small_case(k, n) for k, n in KS_SMALL_CASES]
 
 
+KS_FORM_NS = (12, 34)
+
+
+@functools.lru_cache(maxsize=None)
+def ks_form_case(n):
+    """The ks sweep's tip rows (the parity-mask rows of the chain table) under every pruning form: the problems of
+    ks_small_case("dense", 12) and b2l_case("ks", 34), the smallest n that reach a one-row-block and a three-row-block kernel of each
+    form with mask tips"""
+    Q = RC.hidden_rates_Q(n)
+    pid = np.full(n, 1.0 / n)
+    z = RC.parity_tips(synth.make_tree(14, Q, _omega(Q), 900 + n, pid))
+    dense = {"sparse_chains": 2} if n <= 32 else {}
+    runs = tuple({"pruning_form": f, **dense} for f in dense_forms(n))
+    return Case(f"ks_forms_n{n}", f"ks sweep at n = {n}: mask tip rows in every pruning form", Q, pid, z, "ks", 6, 70, 37 if n <= 32 else 41,
+                REPLICAS_2_TILES, runs)
+
+
+def ks_form_cases():
+    return [ks_form_case(n) for n in KS_FORM_NS]
+
+
 def dense_cases():
     return [dense_case(n) for n in DENSE_NS] + [dense_case(n, "plain") for n in DENSE_PLAIN_NS]
 
@@ -363,7 +380,7 @@ def slot_cases():
 
 
 def all_cases():
-    return dense_cases() + band_cases() + b2l_cases() + slot_cases() + ks_small_cases()
+    return dense_cases() + band_cases() + b2l_cases() + slot_cases() + ks_small_cases() + ks_form_cases()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
