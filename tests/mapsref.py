@@ -94,9 +94,10 @@ def simulate(edge, edge_length, Q, pid, R, seed, replica_offset=0, observe=None)
     return tips, stats, (nodes + 1).astype(np.int32), _pack(rows, R, E)
 
 
-def sumstatEXP(z, Q, pid, N, nen, nodelist, root, L, R, dv, seed, replica, rescale=False):
+def sumstatEXP(z, Q, pid, N, nen, nodelist, root, L, R, dv, seed, replica, rescale=False, jumps=None):
     """pyref.sumstatEXP (maketreelistEXP :3001-3051, newunifSample :93-208) with the segments recorded: (out, (off, dwell,
-    state)).  Same draws in the same order; out is summed in edge-row order as pyref's."""
+    state)).  Same draws in the same order; out is summed in edge-row order as pyref's.  ``jumps``: a dict that receives the
+    number of jumps, virtual ones included, of every (sample, edge row)."""
     n = len(Q)
     E = len(z["edge"])
     T = len(z["states"])
@@ -123,6 +124,8 @@ def sumstatEXP(z, Q, pid, N, nen, nodelist, root, L, R, dv, seed, replica, resca
         PL[e1[ea] - 1] = row
     out = [[0.0] * (n + n * (n - 1)) for _ in range(N)]
     rows = {}
+    chains = {}                                                              # end state -> [B^k e_end], shared by every branch
+    ks = [] if jumps is not None else None
     for it in range(N):
         rm = [0] * (2 * T - 1)
         for i in range(T):
@@ -133,7 +136,10 @@ def sumstatEXP(z, Q, pid, N, nen, nodelist, root, L, R, dv, seed, replica, resca
             rm[node - 1] = pyref.sample([P[j][rm[e1[j] - 1]][c] * PL[node - 1][c] for c in range(n)],
                                         rng.u(it, pyref.ENT_NODE | (node - 1), 0))
         for b in range(E):
-            segs = _unif_segments(rm[e1[b] - 1], rm[e2[b] - 1], tl[b], P[b], B2, rate, n, lambda d: rng.u(it, pyref.ENT_BUNIF | b, d))
+            segs = _unif_segments(rm[e1[b] - 1], rm[e2[b] - 1], tl[b], P[b], B2, rate, n, lambda d: rng.u(it, pyref.ENT_BUNIF | b, d),
+                                  chains, ks)
+            if jumps is not None:
+                jumps[(it, b)] = ks.pop()
             for i in range(1, len(segs)):
                 x, y = segs[i - 1][1], segs[i][1]
                 out[it][n + x * (n - 1) + (y - 1 if x < y else y)] += 1.0
@@ -143,23 +149,32 @@ def sumstatEXP(z, Q, pid, N, nen, nodelist, root, L, R, dv, seed, replica, resca
     return out, _pack(rows, N, E)
 
 
-def _unif_segments(a, e, t, Pb, B2, rate, n, u):
-    """newunifSample(a, e, t, P_b[a, e]) as a list of (dwell, state0), virtual jumps dropped; u(d) is draw d of the branch"""
+def _unif_segments(a, e, t, Pb, B2, rate, n, u, chains=None, ks=None):
+    """newunifSample(a, e, t, P_b[a, e]) as a list of (dwell, state0), virtual jumps dropped; u(d) is draw d of the branch.
+    ``chains``: a dict that keeps the rows B^k e_end between calls (the same numbers; 64 states would recompute 300 products of
+    4 096 terms per branch otherwise); ``ks``: a list that receives the number of jumps drawn"""
     tp = Pb[a][e]
     dr = 0
     rU = u(dr); dr += 1
     lam = rate * t
     pk = pyref.pexp(-lam)
     cum = pk / tp if a == e else 0.0
-    beta = [[0.0] * n]
-    beta[0][e] = 1.0
+    beta = chains.get(e) if chains is not None else None
+    if beta is None:
+        beta = [[0.0] * n]
+        beta[0][e] = 1.0
+        if chains is not None:
+            chains[e] = beta
     k = 0
     while not cum > rU:
         k += 1
         assert k <= 300
-        beta.append(pyref.matvec_lr(B2, beta[k - 1]))
+        if len(beta) <= k:
+            beta.append(pyref.matvec_lr(B2, beta[k - 1]))
         pk = pk * lam / float(k)
         cum += pk * beta[k][a] / tp
+    if ks is not None:
+        ks.append(k)
     if k == 0 or (k == 1 and a == e):
         return [(t - 0.0, a)]
     if k == 1:
