@@ -574,8 +574,10 @@ def fit_ml(z, model, pid, sites=None, observe=None, per_site=False, starts=8, se
 def posterior_rates(z, model, pid, prior, iters, chains=4, sites=None, observe=None, per_site=False, theta0=None, theta_max=None,
                     thin=1, stats=True, **opt):
     """Posterior sample of the rates of an index model (``ratemodel.er`` / ``sym`` / ``ard`` / ``index_model``) by exact data
-    augmentation -> phm_gibbs_rates: the Bayesian counterpart of ``fit_ml``.  ``chains`` chains run in
-    lock-step, one per lane; every iteration draws an exact history given the tips and the chain's rates (``sample_histories``'
+    augmentation for 2..64 states (DESIGN.md sections 20 and 25) -> phm_gibbs_rates (2..8 states, one chain per lane) or
+    phm_gibbs_rates_wide (9..64 states, one site of a chain per lane; with ``per_site=True`` a chain has one site and a wave one
+    live lane): the Bayesian counterpart of ``fit_ml``.  ``chains`` chains run in lock-step; every iteration draws an exact
+    history given the tips and the chain's rates (``sample_histories``'
     sampler: no burn-in of the history, no jump cap) and then every rate from its Gamma full conditional.
     ``prior``: Gamma (shape, rate) per parameter, [p, 2] (or one pair for all) shared by the chains, or [C, p, 2].
     Joint (default): every chain sees all the sites; C = chains.  ``per_site=True``: ``chains`` chains per site in one call
@@ -632,11 +634,12 @@ def posterior_rates(z, model, pid, prior, iters, chains=4, sites=None, observe=N
     st = np.zeros((rows, Cn, _lib.stat_cols(n))) if stats else None
     rej = np.zeros((Cn, p), dtype=np.int32)
     status = np.zeros(Cn, dtype=np.int32)
-    _lib.check(L.phm_gibbs_rates(C.byref(a.tree), n, _lib._p(idx, C.c_int32), p, Cn, _lib._p(th0, C.c_double),
-                                 _lib._p(pr, C.c_double), pr.shape[0], theta_max, _lib._p(pid, C.c_double), pid.shape[0],
-                                 _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), iters, thin, C.byref(a.opt),
-                                 _lib._p(theta, C.c_double), _lib._p(ll, C.c_double), _lib._p(st, C.c_double),
-                                 _lib._p(rej, C.c_int32), _lib._p(status, C.c_int32)))
+    fn = L.phm_gibbs_rates_wide if n > 8 else L.phm_gibbs_rates
+    _lib.check(fn(C.byref(a.tree), n, _lib._p(idx, C.c_int32), p, Cn, _lib._p(th0, C.c_double),
+                  _lib._p(pr, C.c_double), pr.shape[0], theta_max, _lib._p(pid, C.c_double), pid.shape[0],
+                  _lib._p(a.obs, C.c_int32), _lib._p(som, C.c_int32), iters, thin, C.byref(a.opt),
+                  _lib._p(theta, C.c_double), _lib._p(ll, C.c_double), _lib._p(st, C.c_double),
+                  _lib._p(rej, C.c_int32), _lib._p(status, C.c_int32)))
     out = dict(theta=theta, loglik=ll, stats=st, rejected=rej, status=status)
     if per_site:
         lead = dict(theta=1, loglik=1, stats=1, rejected=0, status=0)         # axes before the chain axis

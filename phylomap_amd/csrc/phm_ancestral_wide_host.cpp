@@ -43,6 +43,14 @@ int32_t AwLanes::load_models(int64_t first, int64_t count) {
   return PHM_OK;
 }
 
+int32_t AwLanes::set_models(const double* Q, const int32_t* sq) {
+  const size_t nn = (size_t)in.n * in.n;
+  HIPCHK(hipMemcpy(dQ.p, Q, sizeof(double) * nn * Kc, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dsq.p, sq, sizeof(int32_t) * (size_t)in.E * Kc, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dbad.p, 0, sizeof(uint32_t) * Kc));
+  return PHM_OK;
+}
+
 int32_t AwLanes::expm() const {
   const int n = in.n, E = in.E;
   const size_t nn = (size_t)n * n;

@@ -61,6 +61,9 @@ struct AwLanes {
   int32_t upload_tree();                                // edge lengths, observe, the up steps
   int32_t alloc(const AwPlan& pl);                      // for chunks of pl.Kc_max models x pl.Sc_max sites
   int32_t load_models(int64_t first, int64_t count);    // the chunk's Q, pid and squaring counts, cleared error words; sets m0, Kc
+  // the loaded chunk's matrices replaced in place (phm_gibbs_rates_wide: Q(theta) of an iteration): Q [Kc][n * n] row-major and
+  // their squaring counts sq [Kc][E] (ex_squarings'), cleared error words; no buffer is reallocated
+  int32_t set_models(const double* Q, const int32_t* sq);
   int32_t expm() const;                                 // P_k(t_b) of every edge: one launch_expm_pade per model
   int32_t fetch_bad();                                  // the models' error words -> badh
   phm::AwParams params() const;                         // of the loaded chunk, what every driver sets; Sc is the driver's

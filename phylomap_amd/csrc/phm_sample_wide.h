@@ -46,11 +46,20 @@ struct SwParams {
   const int32_t* depth_of;                     // [model] M(mu_k max_b t_b): the last row of the model's table
   size_t tab_stride;                           // doubles between the tables of two models in `beta`
   double* beta;                                // model k, row m: [e][c] = (B_k^m)[c, e], the n weights of a state draw contiguous
+  // sites form only (section 25): a tile is 64 consecutive SITES of one chain, ev its first evaluation, eval_id that site's id
+  const double* ll;                            // [Ev] log-likelihoods of the evaluations: a lane whose own is not finite idles
+  uint32_t lane_stride;                        // the evaluation id of lane l is tile.eval_id + l * lane_stride (the chains of the call)
 };
 
 // mu, B and the table of models [0, Kc) of the chunk, a workgroup per model
 hipError_t launch_sw_table(const SwParams& p, hipStream_t stream);
 // root, node levels, branches and the finish of the tiles of p; level_off: boundaries of the depth levels in p.order (host)
 hipError_t launch_sw_sample(const SwParams& p, const std::vector<int32_t>& level_off, int maps_mode, hipStream_t stream);
+// Sites form, one iteration of phm_gibbs_rates_wide: root, node levels and branches of the tiles of p, one draw per evaluation
+// (p.core.replica is every lane's replica word), then the finish and the reduction: red [Kc][cols + 1] (every chain's columns and
+// its log-likelihood summed over its `sites` evaluations, one after the other, sites ascending) and one more value, the error
+// word.  The accumulators are left zeroed for the next iteration.  Chain k owns tiles [k, k + 1) * tiles_per_chain.
+hipError_t launch_sw_sample_sites(const SwParams& p, const std::vector<int32_t>& level_off, int sites, int tiles_per_chain, double* red,
+                                  hipStream_t stream);
 
 }  // namespace phm
