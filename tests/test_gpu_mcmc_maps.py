@@ -1,12 +1,14 @@
 """Stochastic maps of the MCMC samplers on the device (phm_maketreelistMCMC_maps) against their Python twin
-(tests/mcmcmapsref.py) bit for bit, against the samplers' own statistics on C3's tree, the two-phase contract (tampered offsets,
+(tests/mcmcmapsref.py) bit for bit, against the samplers' own statistics and four chains of the CPU oracle on C3's tree, the two-phase contract (tampered offsets,
 guard elements), capacity recovery, devices, the exact per-branch expectations, and a drawn history as the start of a chain."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import mcmcmapsclasses
 import mcmcmapsref
+import oracle_lib as O
 from phylomap_amd import _lib, api, synth
 from phylomap_amd.maps import Maps, history_tree
 
@@ -173,6 +175,31 @@ def test_c3_mcmc_maps_1024():
     inner = into[edge[:, 0]] >= 0
     multi = m.counts()[:, inner] > 1                                         # m_b = 1 keeps the child's state throughout
     assert np.array_equal(ns[:, inner, 0][multi], ns[:, into[edge[inner, 0]], 1][multi])
+    # Four chains against the oracle (tiles_branch_group = 4 at this size: several branches per wave in mcmc_maps_tiles_kernel): the
+    # path sweep ``it`` left is the chain state after it + 1 sweeps; merged, it is the map.  Offsets and states bit for bit, dwell
+    # within 4 L 2^-53 relative, L the longest branch of these chains on the oracle after any sweep (both sides add at most L
+    # positive numbers left to right).
+    nen, nodelist, root = _lib.tree_orders(z)
+    B = np.eye(n) + Q / Omega
+    chains, want, longest = (0, 63, 64, 1023), {}, 0
+    for r in chains:
+        for sweeps in range(1, N + 1):
+            _, rc, dump = O.maketreelistMCMC(z, Q, pid, B, Omega, nen, nodelist, root, sweeps, variant=O.BIGTREE, seed=0xC3, replica=r, dump=True)
+            assert rc == 0
+            longest = max(longest, int(dump.seg_count.max()))
+            if sweeps - 1 in its:
+                want[r, sweeps - 1] = mcmcmapsclasses.merged_dump(dump)
+    bar, worst = 4.0 * longest * 2.0 ** -53, 0.0
+    for r in chains:
+        for j, it in enumerate(its):
+            woff, wdwell, wstate = want[r, it]
+            k = (r * 2 + j) * E
+            lo, hi = off[k], off[k + E]
+            assert np.array_equal(off[k:k + E + 1] - lo, woff), (r, it)
+            assert np.array_equal(state[lo:hi] - 1, wstate), (r, it)
+            worst = max(worst, float(np.max(np.abs(dwell[lo:hi] - wdwell) / wdwell)))
+    print(f"C3 maps against the oracle: worst dwell error over the bar {worst / bar:.3g} (L = {longest})")
+    assert worst <= bar
     # a tampered offset table names its row and writes nothing past map_cap
     bad = 3 * E + 777
     off2 = off.copy()
