@@ -34,6 +34,8 @@ EXPORTS = [
 EXT_EXPORTS = ["phm_sample_histories_models_wide"]
 # include/phylomap_hip_ext2.h: entry points added after EXT_EXPORTS was pinned in its turn
 EXT2_EXPORTS = ["phm_gibbs_rates_wide"]
+# include/phylomap_hip_ext3.h: entry points added after EXT2_EXPORTS was pinned in its turn
+EXT3_EXPORTS = ["phm_expected_stats_models_wide"]
 
 
 class PhmError(RuntimeError):
@@ -92,7 +94,7 @@ _lib = None
 
 
 def _argtypes():
-    """{symbol: argtypes} of include/phylomap_hip.h, phylomap_hip_ext.h and phylomap_hip_ext2.h, from the argument runs that the entry points share"""
+    """{symbol: argtypes} of include/phylomap_hip.h, phylomap_hip_ext.h, phylomap_hip_ext2.h and phylomap_hip_ext3.h, from the argument runs that the entry points share"""
     i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
     pi, pl, pd, pt, po = (C.POINTER(t) for t in (C.c_int32, C.c_int64, C.c_double, Tree, Options))
     sweep = [pt, i32, pd, pd, pd, f64, pi, pi, i32, i32]     # tree, n, Q, pid, B, Omega, nen, nodelist, root, N
@@ -144,6 +146,7 @@ def _argtypes():
     t["phm_maketreelistMCMCksmt"] = t["phm_maketreelistMCMCmt"]
     t["phm_sample_histories_models_wide"] = t["phm_sample_histories_models"]
     t["phm_gibbs_rates_wide"] = t["phm_gibbs_rates"]
+    t["phm_expected_stats_models_wide"] = t["phm_expected_stats_models"]
     for name in ("phm_maketreelistMCMC", "phm_maketreelistMCMC_bigtree", "phm_SPARSEmaketreelistMCMC", "phm_maketreelistMCMCks_sweep",
                  "phm_maketreelistMCMCbf_sweep"):
         t[name] = sweep + out

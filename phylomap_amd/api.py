@@ -443,29 +443,35 @@ def expected_through_time(z, Q, pid, bounds=None, points=None, sites=None, obser
 
 
 def loglik_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **opt):
-    """log p(tips_s | Q_k, pid_k) for K rate matrices in one call -> phm_loglik_models: the likelihood a
-    fit evaluates, with the models across the lanes (2..8 states; wider models run one after the other).  ``Qs``: [K, n, n] (or
+    """log p(tips_s | Q_k, pid_k) for K rate matrices in one call (DESIGN.md sections 17 and 26) -> phm_loglik_models (2..8 states,
+    the models across the lanes) or phm_expected_stats_models_wide with no statistics asked for (9..64 states, one state per lane,
+    batched over models and sites; the same values bit for bit): the likelihood a fit evaluates.  ``Qs``: [K, n, n] (or
     one n x n matrix).  ``pid``: n values shared by every model, or [K, n].  ``z``, ``sites``, ``observe`` and the options are
     ``expected_sumstat``'s.  ``site_of_model`` None ("cross"): every model on every site, returns [K, S].  ``site_of_model`` = K
     0-based site indices ("paired"): model k on its own site alone, returns [K].  An impossible evaluation is ``-inf``."""
     L = _lib.load()
-    _, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
+    n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
     out = np.zeros(shape)
-    _lib.check(L.phm_loglik_models(*head, C.byref(a.opt), _lib._p(out, C.c_double)))
+    if n > 8:
+        _lib.check(L.phm_expected_stats_models_wide(*head, C.byref(a.opt), None, _lib._p(out, C.c_double)))
+    else:
+        _lib.check(L.phm_loglik_models(*head, C.byref(a.opt), _lib._p(out, C.c_double)))
     return out
 
 
 def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, **opt):
     """Exact E[dwell_i | tips_s, Q_k] and E[N_ij | tips_s, Q_k] with log p(tips_s | Q_k) for K rate matrices in one call
-     -> phm_expected_stats_models: ``expected_sumstat`` with the models across the lanes (2..8 states; wider
-    models run one after the other).  Every argument is ``loglik_models``'.  Returns ``(stats, loglik)``: [K, S, n + n(n-1)] and
+    (DESIGN.md sections 18 and 26) -> phm_expected_stats_models (2..8 states: ``expected_sumstat`` with the models across the
+    lanes) or phm_expected_stats_models_wide (9..64 states: one state per lane, batched over models and sites; a model that leaves
+    no state is served there too).  Every argument is ``loglik_models``'.  Returns ``(stats, loglik)``: [K, S, n + n(n-1)] and
     [K, S] ("cross"), or [K, n + n(n-1)] and [K] with ``site_of_model`` ("paired").  ``loglik`` is ``loglik_models``' value bit
     for bit; an impossible evaluation is ``-inf`` with a row of NaN."""
     L = _lib.load()
     n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
     ll = np.zeros(shape)
     stats = np.zeros((_lib.stat_cols(n),) + shape)                 # column slowest, evaluation (site fastest) within it
-    _lib.check(L.phm_expected_stats_models(*head, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double)))
+    fn = L.phm_expected_stats_models_wide if n > 8 else L.phm_expected_stats_models
+    _lib.check(fn(*head, C.byref(a.opt), _lib._p(stats, C.c_double), _lib._p(ll, C.c_double)))
     return np.moveaxis(stats, 0, -1), ll
 
 
