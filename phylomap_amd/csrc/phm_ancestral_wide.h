@@ -2,6 +2,8 @@
 // (phm_ancestral_wide.hip), behind phm_ancestral_models_wide (phm_ancestral_wide_api.cpp).  DESIGN.md section 23.
 #pragma once
 
+#include <type_traits>
+
 #include "phm_expect.h"
 
 namespace phm {
@@ -11,6 +13,14 @@ constexpr int AW_GRID_MAX = 65535;             // models, site tiles and selecte
 
 // lanes of one (evaluation, node) item: ex_branch_wide_kernel's classes
 inline int aw_lanes(int n) { return n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+
+// f(std::integral_constant<int, NP>) of the lane class, its value returned: constexpr int NP_ = decltype(np)::value
+template <class F>
+inline auto aw_with_lanes(int NP, F&& f) {
+  if (NP == 16) return f(std::integral_constant<int, 16>{});
+  if (NP == 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
+}
 
 // One state per lane.  An evaluation of the chunk is ev = model * Sc + site (Ev = Kc * Sc of them); every vector is a contiguous
 // row of NP doubles, the states past n zero.  Exponents are base-2 integers.  A tip's max-product vector is its row of L, so M
@@ -27,8 +37,11 @@ struct AwParams {
   double* L;                                   // [node row][Ev][NP] rescaled partial likelihoods
   int32_t* sL;                                 // [node row][Ev]
   double* ll;                                  // [Ev] log p(tips)
+  double* lam;                                 // [Ev] pid . L_root (rescaled: ll before the log and the exponent); NULL: not stored
   double* O;                                   // [node row][Ev][NP] rescaled outside vectors
   int32_t* sO;                                 // [node row][Ev]
+  double* F;                                   // [edge row][Ev][NP] F_b = O_parent (.) P(t_sib) L_sib, rescaled; NULL: not stored
+  int32_t* sF;                                 // [edge row][Ev]
   const int32_t* sel;                          // [J] node rows to report
   int32_t J;
   double* post;                                // [Ev][J][n] O (.) L over its own sum
@@ -46,9 +59,10 @@ hipError_t launch_aw_tips(const AwParams& p, hipStream_t stream);
 // one height level of the sum-product (joint = false: L, sL) or max-product (joint = true: M, sM, ptr) up pass: `steps` (device)
 // holds `count` UpStep entries
 hipError_t launch_aw_up(const AwParams& p, const UpStep* steps, int count, bool joint, hipStream_t stream);
-// log p(tips) of every evaluation; with O not NULL also the root's outside vector (pid, exponent 0)
+// log p(tips) of every evaluation; with O not NULL also the root's outside vector (pid, exponent 0), with lam not NULL also lam
 hipError_t launch_aw_root(const AwParams& p, hipStream_t stream);
-// one depth level of the down pass: O and sO of the children of `count` ExDown entries of `steps` (device)
+// one depth level of the down pass: O and sO of the children of `count` ExDown entries of `steps` (device); with F not NULL
+// also F and sF of their edge rows
 hipError_t launch_aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_t stream);
 // node posteriors of selected rows [j0, j0 + count)
 hipError_t launch_aw_post(const AwParams& p, int j0, int count, hipStream_t stream);

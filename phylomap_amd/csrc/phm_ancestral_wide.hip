@@ -15,7 +15,12 @@
 // row-major P[k][a] consecutively as stored.  A group's child vector is an LDS broadcast; the rows of two groups of one half-wave
 // are NP + 2 doubles apart per vector, which keeps them on different banks at NP = 16.
 // Every loop is bounded by n, the step count or the site tile; the arithmetic of the joint reconstruction is explicit products.
+// For section 26 (phm_scores_wide.hip) the root stores lam = pid_k . L_root, its chain's value before the log, and the down pass
+// has a second instantiation that stores F_b and its exponent (AwParams' lam, F and sF).  The lane pieces (shape, group maximum,
+// rescale, transposed staging) are phm_aw_device.h's.
 #include "phm_ancestral_wide.h"
+
+#include "phm_aw_device.h"
 
 #include <algorithm>
 #include <mutex>
@@ -26,41 +31,11 @@ namespace phm {
 
 namespace {
 
-constexpr int AW_BLOCK = 256;
 constexpr int AW_WALK = 4;                     // sites a group walks through the staged matrices
 constexpr double AW_LN2 = 0.69314718055994530942;
 
-template <int NP> struct AwShape {
-  static constexpr int G = AW_BLOCK / NP;      // groups (items) of a workgroup
-  static constexpr int LD = NP + 1;            // row of a staged matrix
-  static constexpr int VS = NP + 2;            // row of a staged vector
-};
-
 // doubles of LDS: two staged matrices, two vectors per group
 template <int NP> inline size_t aw_lds_doubles(int n) { return (size_t)2 * n * AwShape<NP>::LD + (size_t)2 * AwShape<NP>::G * AwShape<NP>::VS; }
-
-template <int NP> __device__ __forceinline__ double aw_group_max(double v) {
-  double m = fmax(0.0, v);
-#pragma unroll
-  for (int off = NP / 2; off >= 1; off >>= 1) m = fmax(m, __shfl_xor(m, off, NP));
-  return m;
-}
-
-// the value scaled by 2^-e with the maximum in [1/2, 1); e = 0 for an all-zero vector (ex_rescale)
-__device__ __forceinline__ double aw_rescale(double v, double mx, int& e) {
-  e = 0;
-  if (!(mx > 0.0)) return v;
-  (void)frexp(mx, &e);
-  return ldexp(v, -e);
-}
-
-// sP[j * LD + i] = P[i][j]
-template <int NP> __device__ __forceinline__ void aw_stage_t(double* sP, const double* __restrict__ P, int n) {
-  for (int e = threadIdx.x; e < n * n; e += AW_BLOCK) {
-    const int i = e / n, j = e - i * n;
-    sP[j * AwShape<NP>::LD + i] = P[e];
-  }
-}
 
 __global__ __launch_bounds__(AW_BLOCK) void aw_tips_kernel(AwParams p, int t0) {
   const size_t Ev = (size_t)p.Kc * p.Sc;
@@ -179,12 +154,14 @@ __global__ __launch_bounds__(AW_BLOCK) void aw_root_kernel(AwParams p) {
   if (a == 0) {
     double l = 0.0;
     for (int i = 0; i < n; ++i) l = fma(sV[(g * 2) * VS + i], sV[(g * 2 + 1) * VS + i], l);
+    if (p.lam) p.lam[ev] = l;
     p.ll[ev] = log(l) + (double)p.sL[(size_t)p.root * Ev + ev] * AW_LN2;
   }
 }
 
-// grid: (step, model, site tile).  F = O_p (.) (P_sib L_sib), O_c = P_b^T F.
-template <int NP>
+// grid: (step, model, site tile).  F = O_p (.) (P_sib L_sib), O_c = P_b^T F.  STORE_F: F and its exponent are stored per edge row
+// (the branch stage of phm_scores_wide.hip reads them).
+template <int NP, bool STORE_F>
 __global__ __launch_bounds__(AW_BLOCK) void aw_down_kernel(AwParams p, const ExDown* __restrict__ steps) {
   constexpr int G = AwShape<NP>::G, LD = AwShape<NP>::LD, VS = AwShape<NP>::VS;
   extern __shared__ __align__(16) double aw_lds[];
@@ -221,6 +198,7 @@ __global__ __launch_bounds__(AW_BLOCK) void aw_down_kernel(AwParams p, const ExD
       f = a < n ? p.O[((size_t)d.parent * Ev + ev) * NP + a] * acc : 0.0;
       f = aw_rescale(f, aw_group_max<NP>(f), eF);
       cf[a] = f;
+      if constexpr (STORE_F) p.F[((size_t)d.edge * Ev + ev) * NP + a] = f;
     }
     __syncthreads();
     if (!on) continue;
@@ -230,8 +208,11 @@ __global__ __launch_bounds__(AW_BLOCK) void aw_down_kernel(AwParams p, const ExD
     int eO;
     o = aw_rescale(o, aw_group_max<NP>(o), eO);
     p.O[((size_t)d.child * Ev + ev) * NP + a] = o;
-    if (a == 0)
-      p.sO[(size_t)d.child * Ev + ev] = p.sO[(size_t)d.parent * Ev + ev] + p.sL[(size_t)d.sib_child * Ev + ev] + eF + eO;
+    if (a == 0) {
+      const int32_t sF = p.sO[(size_t)d.parent * Ev + ev] + p.sL[(size_t)d.sib_child * Ev + ev] + eF;
+      if constexpr (STORE_F) p.sF[(size_t)d.edge * Ev + ev] = sF;
+      p.sO[(size_t)d.child * Ev + ev] = sF + eO;
+    }
   }
 }
 
@@ -313,12 +294,12 @@ hipError_t aw_up(const AwParams& p, const UpStep* steps, int count, hipStream_t 
   return hipGetLastError();
 }
 
-template <int NP>
+template <int NP, bool STORE_F>
 hipError_t aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
   const size_t lds = sizeof(double) * aw_lds_doubles<NP>(p.n);
-  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(aw_down_kernel<NP>), (int)(sizeof(double) * aw_lds_doubles<NP>(NP)));
+  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(aw_down_kernel<NP, STORE_F>), (int)(sizeof(double) * aw_lds_doubles<NP>(NP)));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((aw_down_kernel<NP>), dim3(count, p.Kc, aw_tiles<NP>(p)), dim3(AW_BLOCK), lds, stream, p, steps);
+  hipLaunchKernelGGL((aw_down_kernel<NP, STORE_F>), dim3(count, p.Kc, aw_tiles<NP>(p)), dim3(AW_BLOCK), lds, stream, p, steps);
   return hipGetLastError();
 }
 
@@ -340,8 +321,6 @@ hipError_t aw_allow_lds(const void* fn, int bytes) {
   return e;
 }
 
-#define AW_DISPATCH(call16, call32, call64) (p.NP == 16 ? (call16) : p.NP == 32 ? (call32) : (call64))
-
 hipError_t launch_aw_tips(const AwParams& p, hipStream_t stream) {
   if (!aw_ok(p) || !p.tips || !p.obs) return hipErrorInvalidValue;
   const size_t cells = (size_t)p.Kc * p.Sc * p.NP;
@@ -354,57 +333,58 @@ hipError_t launch_aw_tips(const AwParams& p, hipStream_t stream) {
 hipError_t launch_aw_up(const AwParams& p, const UpStep* steps, int count, bool joint, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   if (!aw_ok(p) || !steps || (joint && (!p.M || !p.sM || !p.ptr))) return hipErrorInvalidValue;
-  if (joint) return AW_DISPATCH((aw_up<16, true>(p, steps, count, stream)), (aw_up<32, true>(p, steps, count, stream)),
-                                (aw_up<64, true>(p, steps, count, stream)));
-  return AW_DISPATCH((aw_up<16, false>(p, steps, count, stream)), (aw_up<32, false>(p, steps, count, stream)),
-                     (aw_up<64, false>(p, steps, count, stream)));
+  return aw_with_lanes(p.NP, [&](auto np) {
+    constexpr int NP_ = decltype(np)::value;
+    return joint ? aw_up<NP_, true>(p, steps, count, stream) : aw_up<NP_, false>(p, steps, count, stream);
+  });
 }
 
 hipError_t launch_aw_root(const AwParams& p, hipStream_t stream) {
   if (!aw_ok(p) || !p.ll || (p.O && !p.sO)) return hipErrorInvalidValue;
-  const dim3 blk(AW_BLOCK);
-  if (p.NP == 16) hipLaunchKernelGGL((aw_root_kernel<16>), dim3(p.Kc, aw_rows<16>(p)), blk, 0, stream, p);
-  else if (p.NP == 32) hipLaunchKernelGGL((aw_root_kernel<32>), dim3(p.Kc, aw_rows<32>(p)), blk, 0, stream, p);
-  else hipLaunchKernelGGL((aw_root_kernel<64>), dim3(p.Kc, aw_rows<64>(p)), blk, 0, stream, p);
-  return hipGetLastError();
+  return aw_with_lanes(p.NP, [&](auto np) {
+    constexpr int NP_ = decltype(np)::value;
+    hipLaunchKernelGGL((aw_root_kernel<NP_>), dim3(p.Kc, aw_rows<NP_>(p)), dim3(AW_BLOCK), 0, stream, p);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_aw_down(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (!aw_ok(p) || !steps || !p.O || !p.sO) return hipErrorInvalidValue;
-  return AW_DISPATCH((aw_down<16>(p, steps, count, stream)), (aw_down<32>(p, steps, count, stream)), (aw_down<64>(p, steps, count, stream)));
+  if (!aw_ok(p) || !steps || !p.O || !p.sO || (p.F && !p.sF) || count > AW_GRID_MAX) return hipErrorInvalidValue;
+  return aw_with_lanes(p.NP, [&](auto np) {
+    constexpr int NP_ = decltype(np)::value;
+    return p.F ? aw_down<NP_, true>(p, steps, count, stream) : aw_down<NP_, false>(p, steps, count, stream);
+  });
 }
 
 hipError_t launch_aw_post(const AwParams& p, int j0, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   if (!aw_ok(p) || !p.O || !p.sel || !p.post || j0 < 0 || j0 + count > p.J) return hipErrorInvalidValue;
-  const dim3 blk(AW_BLOCK);
-  if (p.NP == 16) hipLaunchKernelGGL((aw_post_kernel<16>), dim3(count, p.Kc, aw_rows<16>(p)), blk, 0, stream, p, j0);
-  else if (p.NP == 32) hipLaunchKernelGGL((aw_post_kernel<32>), dim3(count, p.Kc, aw_rows<32>(p)), blk, 0, stream, p, j0);
-  else hipLaunchKernelGGL((aw_post_kernel<64>), dim3(count, p.Kc, aw_rows<64>(p)), blk, 0, stream, p, j0);
-  return hipGetLastError();
+  return aw_with_lanes(p.NP, [&](auto np) {
+    constexpr int NP_ = decltype(np)::value;
+    hipLaunchKernelGGL((aw_post_kernel<NP_>), dim3(count, p.Kc, aw_rows<NP_>(p)), dim3(AW_BLOCK), 0, stream, p, j0);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_aw_jroot(const AwParams& p, hipStream_t stream) {
   if (!aw_ok(p) || !p.M || !p.sM || !p.x || !p.jlogp) return hipErrorInvalidValue;
-  const dim3 blk(AW_BLOCK);
-  if (p.NP == 16) hipLaunchKernelGGL((aw_jroot_kernel<16>), dim3(p.Kc, aw_rows<16>(p)), blk, 0, stream, p);
-  else if (p.NP == 32) hipLaunchKernelGGL((aw_jroot_kernel<32>), dim3(p.Kc, aw_rows<32>(p)), blk, 0, stream, p);
-  else hipLaunchKernelGGL((aw_jroot_kernel<64>), dim3(p.Kc, aw_rows<64>(p)), blk, 0, stream, p);
-  return hipGetLastError();
+  return aw_with_lanes(p.NP, [&](auto np) {
+    constexpr int NP_ = decltype(np)::value;
+    hipLaunchKernelGGL((aw_jroot_kernel<NP_>), dim3(p.Kc, aw_rows<NP_>(p)), dim3(AW_BLOCK), 0, stream, p);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_aw_trace(const AwParams& p, const ExDown* steps, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   if (!aw_ok(p) || !steps || !p.ptr || !p.x || count > AW_GRID_MAX) return hipErrorInvalidValue;
   const size_t Ev = (size_t)p.Kc * p.Sc;
-  const dim3 grid((unsigned)((Ev + AW_BLOCK - 1) / AW_BLOCK), count), blk(AW_BLOCK);
-  if (p.NP == 16) hipLaunchKernelGGL((aw_trace_kernel<16>), grid, blk, 0, stream, p, steps);
-  else if (p.NP == 32) hipLaunchKernelGGL((aw_trace_kernel<32>), grid, blk, 0, stream, p, steps);
-  else hipLaunchKernelGGL((aw_trace_kernel<64>), grid, blk, 0, stream, p, steps);
-  return hipGetLastError();
+  const dim3 grid((unsigned)((Ev + AW_BLOCK - 1) / AW_BLOCK), count);
+  return aw_with_lanes(p.NP, [&](auto np) {
+    hipLaunchKernelGGL((aw_trace_kernel<decltype(np)::value>), grid, dim3(AW_BLOCK), 0, stream, p, steps);
+    return hipGetLastError();
+  });
 }
-
-#undef AW_DISPATCH
 
 }  // namespace phm

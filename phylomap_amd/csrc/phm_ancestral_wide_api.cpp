@@ -95,19 +95,16 @@ int32_t aw_device(const AnInput& an, int32_t device, int64_t first, int64_t coun
       st = ln.passes(p);
       if (st) return st;
       if (marg) {
-        for (size_t l = 0; l + 1 < an.down_off.size(); ++l)
-          for (int k0 = an.down_off[l]; k0 < an.down_off[l + 1]; k0 += step_max)
-            HIPCHK(phm::launch_aw_down(p, down + k0, std::min(step_max, an.down_off[l + 1] - k0), nullptr));
+        st = aw_level_steps(an.down_off, step_max, [&](int k0, int cnt) { return phm::launch_aw_down(p, down + k0, cnt, nullptr); });
+        if (st) return st;
         for (int j0 = 0; j0 < J; j0 += step_max) HIPCHK(phm::launch_aw_post(p, j0, std::min(step_max, J - j0), nullptr));
       }
       if (joint) {
-        for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-          for (int k0 = in.up_off[l]; k0 < in.up_off[l + 1]; k0 += step_max)
-            HIPCHK(phm::launch_aw_up(p, up + k0, std::min(step_max, in.up_off[l + 1] - k0), true, nullptr));
+        st = aw_level_steps(in.up_off, step_max, [&](int k0, int cnt) { return phm::launch_aw_up(p, up + k0, cnt, true, nullptr); });
+        if (st) return st;
         HIPCHK(phm::launch_aw_jroot(p, nullptr));
-        for (size_t l = 0; l + 1 < an.down_off.size(); ++l)
-          for (int k0 = an.down_off[l]; k0 < an.down_off[l + 1]; k0 += step_max)
-            HIPCHK(phm::launch_aw_trace(p, down + k0, std::min(step_max, an.down_off[l + 1] - k0), nullptr));
+        st = aw_level_steps(an.down_off, step_max, [&](int k0, int cnt) { return phm::launch_aw_trace(p, down + k0, cnt, nullptr); });
+        if (st) return st;
       }
       HIPCHK(tm.stop());
       st = ln.fetch_ll(Sc);
@@ -124,7 +121,7 @@ int32_t aw_device(const AnInput& an, int32_t device, int64_t first, int64_t coun
         for (int64_t s = 0; s < Sc; ++s) {
           const size_t at = (size_t)k * Sc + s;
           const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
-          const bool possible = !ln.badh[k] && std::isfinite(ln.llh[at]);
+          const bool possible = ln.possible(k, at);
           loglik[ev] = possible ? ln.llh[at] : ninf;
           if (marg) {
             double* out = node_post + (size_t)ev * row;

@@ -92,9 +92,8 @@ int32_t AwLanes::stage_tips(int64_t s0, int64_t Sc) {
 int32_t AwLanes::passes(const phm::AwParams& p) const {
   const phm::UpStep* up = dup.as<phm::UpStep>();
   HIPCHK(phm::launch_aw_tips(p, nullptr));
-  for (size_t l = 0; l + 1 < in.up_off.size(); ++l)
-    for (int k0 = in.up_off[l]; k0 < in.up_off[l + 1]; k0 += plan.step_max)
-      HIPCHK(phm::launch_aw_up(p, up + k0, std::min(plan.step_max, in.up_off[l + 1] - k0), false, nullptr));
+  const int32_t st = aw_level_steps(in.up_off, plan.step_max, [&](int k0, int cnt) { return phm::launch_aw_up(p, up + k0, cnt, false, nullptr); });
+  if (st) return st;
   HIPCHK(phm::launch_aw_root(p, nullptr));
   return PHM_OK;
 }

@@ -44,6 +44,14 @@ inline AwPlan aw_plan(size_t free_b, const LlInput& in, int64_t count, int chunk
   return pl;
 }
 
+// The level steps [off[l], off[l + 1]) of every level l, at most step_max of them a launch: launch(k0, count) -> hipError_t
+template <class F>
+inline int32_t aw_level_steps(const std::vector<int32_t>& off, int step_max, F&& launch) {
+  for (size_t l = 0; l + 1 < off.size(); ++l)
+    for (int k0 = off[l]; k0 < off[l + 1]; k0 += step_max) HIPCHK(launch(k0, std::min(step_max, off[l + 1] - k0)));
+  return PHM_OK;
+}
+
 // Section 23's device state for the models [.., ..) of one device.  The order of a driver: upload_tree, its own uploads, aw_plan
 // on hipMemGetInfo's free bytes, alloc, then per chunk of models load_models, expm, fetch_bad and params, and per chunk of sites
 // stage_tips, passes and fetch_ll.  No call here is timed: the driver brackets the launches with its KernelTimer, next to its own.
@@ -70,6 +78,8 @@ struct AwLanes {
   int32_t stage_tips(int64_t s0, int64_t Sc);           // paired: [model][tip] of the chunk's own sites; cross: [site][tip]
   int32_t passes(const phm::AwParams& p) const;         // tips, the up levels in steps of plan.step_max, root
   int32_t fetch_ll(int64_t Sc);                         // ll of Kc models x Sc sites -> llh
+  // after fetch_bad and fetch_ll: model k of the chunk has its P and the evaluation at llh[at] a finite log-likelihood
+  bool possible(int64_t k, size_t at) const { return !badh[k] && std::isfinite(llh[at]); }
 };
 
 }  // namespace phm_ll

@@ -66,11 +66,12 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   if (chunk > 0) { pl.Kc_max = std::min<int64_t>(pl.Kc_max, chunk); pl.step_max = std::min(pl.step_max, chunk); }
   const size_t Km = (size_t)pl.Kc_max, Tm = Km * (size_t)tpc;
 
-  DevBuf dmu, dB, dbeta, ddepth, dtile, dnst, ddw, dcnt, dred;
+  SwModels md;
+  DevBuf dtile, dnst, ddw, dcnt, dred;
   st = ln.alloc(pl);
   if (st) return st;
-  HIPCHK(dmu.alloc(sizeof(double) * Km)); HIPCHK(dB.alloc(sizeof(double) * nn * Km));
-  HIPCHK(dbeta.alloc(tab_b * Km)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Km));
+  st = md.alloc(n, Km, tab_stride);
+  if (st) return st;
   HIPCHK(dtile.alloc(sizeof(phm::SmTile) * Tm)); HIPCHK(dnst.alloc((size_t)NT * 64 * Tm));
   HIPCHK(ddw.alloc(sizeof(unsigned long long) * n * 64 * Tm)); HIPCHK(dcnt.alloc(sizeof(uint32_t) * (size_t)n * (n - 1) * 64 * Tm));
   const size_t red_max = (size_t)(cols + 1) * Km + 1;
@@ -91,9 +92,7 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   sc.tiles = dtile.as<phm::SmTile>(); sc.down = ddown.as<phm::DownStep>(); sc.order = dorder.as<int32_t>();
   sc.nstate = dnst.as<uint8_t>(); sc.dwfx = ddw.as<unsigned long long>(); sc.cnt = dcnt.as<uint32_t>();
   sc.out = nullptr; sc.nodes = nullptr; sc.err = derr.as<uint32_t>();
-  sp.n = n; sp.NP = phm::aw_lanes(n); sp.n_tips = in.T;
-  sp.Q = ln.dQ.as<double>(); sp.P = ln.dP.as<double>(); sp.pid = ln.dpid.as<double>(); sp.L = ln.dL.as<double>(); sp.t = ln.dt.as<double>();
-  sp.mu = dmu.as<double>(); sp.B = dB.as<double>(); sp.depth_of = ddepth.as<int32_t>(); sp.tab_stride = tab_stride; sp.beta = dbeta.as<double>();
+  md.fill(sp, ln);
   sp.ll = ln.dll.as<double>(); sp.lane_stride = (uint32_t)C;
 
   for (int64_t c0 = 0; c0 < count; c0 += pl.Kc_max) {
@@ -191,7 +190,7 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
       Clock::time_point t0 = Clock::now();
       st = ln.set_models(Qh, sqh);
       if (st) return st;
-      HIPCHK(hipMemcpy(ddepth.p, depth_h, sizeof(int32_t) * Kc, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(md.ddepth.p, depth_h, sizeof(int32_t) * Kc, hipMemcpyHostToDevice));
       up_ms += since(t0);
       t0 = Clock::now();
       HIPCHK(tm.start());

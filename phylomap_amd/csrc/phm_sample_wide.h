@@ -7,7 +7,7 @@
 
 #include <vector>
 
-#include "phm_ancestral_wide.h"
+#include "phm_ancestral_wide_host.h"
 #include "phm_maps.h"
 #include "phm_sample.h"
 #include "phm_sched.h"
@@ -63,3 +63,27 @@ hipError_t launch_sw_sample_sites(const SwParams& p, const std::vector<int32_t>&
                                   hipStream_t stream);
 
 }  // namespace phm
+
+namespace phm_ll {
+
+// The sampler's device state per model of a chunk (mu, B, the depths and the table), next to AwLanes' (the drivers of
+// phm_sample_wide_api.cpp and phm_gibbs_wide_api.cpp).
+struct SwModels {
+  DevBuf dmu, dB, dbeta, ddepth;
+  size_t tab_stride = 0;                       // doubles of a model's table
+
+  int32_t alloc(int n, size_t Km, size_t tab_doubles) {
+    tab_stride = tab_doubles;
+    HIPCHK(dmu.alloc(sizeof(double) * Km)); HIPCHK(dB.alloc(sizeof(double) * (size_t)n * n * Km));
+    HIPCHK(dbeta.alloc(sizeof(double) * tab_stride * Km)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Km));
+    return PHM_OK;
+  }
+  // what every chunk shares of sp: the state count and section 23's buffers of ln, and this state
+  void fill(phm::SwParams& sp, const AwLanes& ln) const {
+    sp.n = ln.in.n; sp.NP = phm::aw_lanes(ln.in.n); sp.n_tips = ln.in.T;
+    sp.Q = ln.dQ.as<double>(); sp.P = ln.dP.as<double>(); sp.pid = ln.dpid.as<double>(); sp.L = ln.dL.as<double>(); sp.t = ln.dt.as<double>();
+    sp.mu = dmu.as<double>(); sp.B = dB.as<double>(); sp.depth_of = ddepth.as<int32_t>(); sp.tab_stride = tab_stride; sp.beta = dbeta.as<double>();
+  }
+};
+
+}  // namespace phm_ll

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "phm_aw_device.h"
 #include "phm_history.h"
 #include "phm_sample_branch.h"
 
@@ -39,10 +40,8 @@ __global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
   double* next = prev + nn;
   const double* __restrict__ Qk = p.Q + (size_t)k * nn;
   if (threadIdx.x == 0) {
-    double mu = 0.0;
-    for (int i = 0; i < n; ++i) mu = fmax(mu, -Qk[i * n + i]);
-    s_mu = mu;
-    p.mu[k] = mu;
+    s_mu = aw_model_mu(Qk, n);
+    p.mu[k] = s_mu;
   }
   __syncthreads();
   const double mu = s_mu;
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
   for (int cell = threadIdx.x; cell < nn; cell += SW_TABLE_BLOCK) {
     const int i = cell / n, j = cell - i * n;
     const double d = i == j ? 1.0 : 0.0;
-    const double b = mu > 0.0 ? d + Qk[cell] / mu : d;
+    const double b = aw_model_b(Qk[cell], mu, d);
     p.B[(size_t)k * nn + cell] = b;
     sB[i * LD + j] = b;
     prev[cell] = d;                                                  // beta_0 = I (symmetric: [e][c] as well)
@@ -229,6 +228,19 @@ inline bool sw_ok(const SwParams& p) {
   return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.core.n_edge >= 1;
 }
 
+// root and node levels of the tiles of p, one launch per depth level
+template <bool SITES>
+void sw_nodes(const SwParams& p, const std::vector<int32_t>& level_off, hipStream_t stream) {
+  constexpr int W = SW_NODE_BLOCK / 64;
+  hipLaunchKernelGGL(sw_root_kernel<SITES>, dim3((p.core.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
+  for (size_t l = 0; l + 1 < level_off.size(); ++l) {
+    const int64_t cnt = level_off[l + 1] - level_off[l];
+    if (cnt <= 0) continue;
+    const dim3 grid((unsigned)((cnt * p.core.n_tiles + W - 1) / W));
+    hipLaunchKernelGGL(sw_node_kernel<SITES>, grid, dim3(SW_NODE_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
+  }
+}
+
 }  // namespace
 
 hipError_t launch_sw_table(const SwParams& p, hipStream_t stream) {
@@ -241,14 +253,7 @@ hipError_t launch_sw_table(const SwParams& p, hipStream_t stream) {
 
 hipError_t launch_sw_sample(const SwParams& p, const std::vector<int32_t>& level_off, int maps_mode, hipStream_t stream) {
   if (!sw_ok(p) || p.core.n_tiles <= 0 || (int64_t)p.core.n_edge * p.core.n_tiles > SW_ITEMS_MAX) return hipErrorInvalidValue;
-  constexpr int W = SW_NODE_BLOCK / 64;
-  hipLaunchKernelGGL(sw_root_kernel<false>, dim3((p.core.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
-  for (size_t l = 0; l + 1 < level_off.size(); ++l) {
-    const int64_t cnt = level_off[l + 1] - level_off[l];
-    if (cnt <= 0) continue;
-    const dim3 grid((unsigned)((cnt * p.core.n_tiles + W - 1) / W));
-    hipLaunchKernelGGL(sw_node_kernel<false>, grid, dim3(SW_NODE_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
-  }
+  sw_nodes<false>(p, level_off, stream);
   const dim3 items((unsigned)((int64_t)p.core.n_edge * p.core.n_tiles));
   with_map_mode(maps_mode, [&](auto mode) {
     constexpr int MODE = decltype(mode)::value;
@@ -263,14 +268,7 @@ hipError_t launch_sw_sample_sites(const SwParams& p, const std::vector<int32_t>&
   if (!p.ll || !red || p.core.nodes || sites < 1 || (size_t)p.Kc * sites != p.Ev || tiles_per_chain != (sites + 63) / 64 ||
       (int64_t)p.Kc * tiles_per_chain != p.core.n_tiles)
     return hipErrorInvalidValue;
-  constexpr int W = SW_NODE_BLOCK / 64;
-  hipLaunchKernelGGL(sw_root_kernel<true>, dim3((p.core.n_tiles + W - 1) / W), dim3(SW_NODE_BLOCK), 0, stream, p);
-  for (size_t l = 0; l + 1 < level_off.size(); ++l) {
-    const int64_t cnt = level_off[l + 1] - level_off[l];
-    if (cnt <= 0) continue;
-    const dim3 grid((unsigned)((cnt * p.core.n_tiles + W - 1) / W));
-    hipLaunchKernelGGL(sw_node_kernel<true>, grid, dim3(SW_NODE_BLOCK), 0, stream, p, level_off[l], level_off[l + 1]);
-  }
+  sw_nodes<true>(p, level_off, stream);
   const dim3 items((unsigned)((int64_t)p.core.n_edge * p.core.n_tiles));
   hipLaunchKernelGGL((sw_branch_kernel<MAPS_OFF, true>), items, dim3(SW_BRANCH_BLOCK), sw_branch_lds_bytes(p.n), stream, p);
   const int64_t cells = (int64_t)p.Kc * (p.n + p.n * (p.n - 1) + 1);

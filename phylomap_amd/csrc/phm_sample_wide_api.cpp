@@ -55,16 +55,13 @@ int32_t sw_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
     return fail(PHM_ERR_CAPACITY, tl.fn + "model " + std::to_string(k_deep) + ": its table of " + std::to_string(tab_b) + " bytes (" +
                                       std::to_string(depth_max + 1) + " rows of " + std::to_string(nn) + " doubles) does not fit in the " +
                                       std::to_string(pl.budget) + " bytes of HBM this call may use");
-  const size_t Km = (size_t)pl.Kc_max;
 
-  DevBuf dmu, dB, dbeta, ddepth;
+  SwModels md;
   st = ln.alloc(pl);
   if (st) return st;
-  HIPCHK(dmu.alloc(sizeof(double) * Km)); HIPCHK(dB.alloc(sizeof(double) * nn * Km));
-  HIPCHK(dbeta.alloc(tab_b * Km)); HIPCHK(ddepth.alloc(sizeof(int32_t) * Km));
-  sp.n = n; sp.NP = phm::aw_lanes(n); sp.n_tips = in.T;
-  sp.Q = ln.dQ.as<double>(); sp.P = ln.dP.as<double>(); sp.pid = ln.dpid.as<double>(); sp.L = ln.dL.as<double>(); sp.t = ln.dt.as<double>();
-  sp.mu = dmu.as<double>(); sp.B = dB.as<double>(); sp.depth_of = ddepth.as<int32_t>(); sp.tab_stride = tab_stride; sp.beta = dbeta.as<double>();
+  st = md.alloc(n, (size_t)pl.Kc_max, tab_stride);
+  if (st) return st;
+  md.fill(sp, ln);
   const SmTiles::Launch launch = [&]() { return phm::launch_sw_sample(sp, sm.level_off, tl.maps_mode(), nullptr); };
 
   for (int64_t c0 = 0; c0 < count; c0 += pl.Kc_max) {
@@ -72,7 +69,7 @@ int32_t sw_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
     const int64_t m0 = first + c0;                       // global index of this chunk's first model
     st = ln.load_models(m0, Kc);
     if (st) return st;
-    HIPCHK(hipMemcpy(ddepth.p, sm.depth.data() + m0, sizeof(int32_t) * Kc, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(md.ddepth.p, sm.depth.data() + m0, sizeof(int32_t) * Kc, hipMemcpyHostToDevice));
     sp.Kc = (int)Kc;
     HIPCHK(tm.start());
     st = ln.expm();
@@ -106,7 +103,7 @@ int32_t sw_device(const SmInput& sm, int32_t device, int64_t first, int64_t coun
           const int64_t site = in.paired ? in.site_of_model[m0 + k] : s0 + s;
           const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
           // an impossible evaluation (or a model whose Pade met a zero pivot) is not drawn: -inf, NaN rows, zero nodes, empty map rows
-          const bool possible = !ln.badh[k] && std::isfinite(ln.llh[at]);
+          const bool possible = ln.possible(k, at);
           loglik[ev] = possible ? ln.llh[at] : ninf;
           st = tl.add(ev, site, m0 + k, (int32_t)at, (int32_t)k, possible, launch);
           if (st) return st;

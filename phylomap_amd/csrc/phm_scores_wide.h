@@ -8,8 +8,9 @@
 
 namespace phm {
 
-// Section 23's buffers (aw: P, pid, L, sL, O, sO and the layout rules of AwParams: one state per lane, ev = model * Sc + site, rows
-// of NP doubles with the states past n zero, int32 exponents) and what the down pass with F and the branch stage add.
+// Section 23's buffers (aw: P, pid, L, sL, O, sO, the root's lam and the down pass' F, sF, and the layout rules of AwParams: one
+// state per lane, ev = model * Sc + site, rows of NP doubles with the states past n zero, int32 exponents) and what the branch
+// stage adds.
 struct ScwParams {
   AwParams aw;
   const double* Q;                             // [model][n][n] row-major
@@ -18,20 +19,13 @@ struct ScwParams {
   double* mu;                                  // [model] max_i(-q_ii)
   double* B;                                   // [model][n][n] row-major I + Q_k / mu_k (I when mu_k = 0)
   const int32_t* form;                         // [model][n_edge] sw_form_terms(mu_k t_b, SW_M_CAP): M of the short form, or SW_M_CAP + 1
-  double* F;                                   // [edge row][Ev][NP] F_b = O_parent (.) P(t_sib) L_sib, rescaled
-  int32_t* sF;                                 // [edge row][Ev]
-  double* lam;                                 // [Ev] pid . L_root (rescaled)
   double* runs;                                // [run of the launch][Ev][col] totals of SC_RUN edge rows each
   double* tot;                                 // [Ev][col], cols = n + n(n-1) (phm_expected_stats' column order)
 };
 
 // mu_k and B_k of the chunk's models
 hipError_t launch_scw_model(const ScwParams& p, hipStream_t stream);
-// lam = pid_k . L_root in state order (after the up pass; launch_aw_root has set O_root = pid_k, sO_root = 0)
-hipError_t launch_scw_root(const ScwParams& p, hipStream_t stream);
-// one depth level of the down pass, F_b and its exponent stored: `steps` (device) holds `count` ExDown entries
-hipError_t launch_scw_down(const ScwParams& p, const ExDown* steps, int count, hipStream_t stream);
-// branch stage of runs [r0, r0 + count): run r is edge rows [r SC_RUN, min(n_edge, (r + 1) SC_RUN)); runs[r - r0] gets its total
+// branch stage (after launch_aw_root with lam and launch_aw_down with F, sF on p.aw) of runs [r0, r0 + count): run r is edge rows [r SC_RUN, min(n_edge, (r + 1) SC_RUN)); runs[r - r0] gets its total
 hipError_t launch_scw_branch(const ScwParams& p, int r0, int count, hipStream_t stream);
 // tot += runs[0] + .. + runs[count - 1], one after the other (tot is continued across launches: the order is the run order)
 hipError_t launch_scw_total(const ScwParams& p, int count, hipStream_t stream);

@@ -1,11 +1,10 @@
 // phm_scores_wide.hip -- E[dwell_i | tips_s, Q_k] and E[N_ij | tips_s, Q_k] for many rate matrices at 9..64 states (DESIGN.md
-// section 26): section 18's down pass, branch stage and run totals in section 23's mapping, ONE STATE PER LANE, on top of
-// section 23's P_k(t_b) and up pass (phm_ancestral_wide.hip, launched unchanged: log p(tips | Q_k) is phm_loglik_models' value
-// bit for bit).
+// section 26): section 18's branch stage and run totals in section 23's mapping, ONE STATE PER LANE, on top of section 23's
+// P_k(t_b), up pass, root and down pass (phm_ancestral_wide.hip: log p(tips | Q_k) is phm_loglik_models' value bit for bit; the
+// root stores lam = pid_k . L_root and the down pass F_b with its exponent, AwParams' lam, F and sF).
 //
 // A group of NP lanes (16 / 32 / 64 for 9..16 / 17..32 / 33..64 states) owns an item; lane a holds state a, the lanes past n hold
 // zeros.  An evaluation of a chunk is ev = model * Sc + site; vectors are rows of NP doubles, exponents int32.
-//   * down pass: aw_down_kernel's arithmetic (ex_down_kernel's, in its pinned order) with F_b and its exponent stored
 //   * branch stage, a workgroup per (run of SC_RUN edge rows, model, tile of sites): B_k staged once, row-major and transposed,
 //     rows NP + 1 doubles apart; its groups walk SCW_WALK sites each and, per site, the edge rows of the run in edge order.
 //     I_b = sum_{l + r <= M} w_{l+r} u_l v_r^T with u_l = (B^T)^l F_b, v_r = B^r L_c; lane j owns column j of I in registers.
@@ -24,136 +23,37 @@
 // Every loop is bounded by n, M <= SW_M_CAP, SC_M_CAP, the run or the site tile.
 #include "phm_scores_wide.h"
 
+#include "phm_aw_device.h"
+
 #include <algorithm>
 
 namespace phm {
 
 namespace {
 
-constexpr int SCW_BLOCK = 256;                 // model, root, down and total kernels
+constexpr int SCW_BLOCK = 256;                 // model and total kernels
 constexpr int SCW_WALK = 4;                    // sites a group walks through the staged matrices
-
-// down pass: aw_down_kernel's workgroup
-template <int NP> struct ScwDown {
-  static constexpr int G = SCW_BLOCK / NP;
-  static constexpr int LD = NP + 1;            // row of a staged matrix
-  static constexpr int VS = NP + 2;            // row of a staged vector
-};
-template <int NP> inline size_t scw_down_lds_doubles(int n) { return (size_t)2 * n * ScwDown<NP>::LD + (size_t)2 * ScwDown<NP>::G * ScwDown<NP>::VS; }
 
 // branch stage: few groups per workgroup, because a fit calls with one site or a few and LDS holds SW_M_CAP + 1 vectors a group
 template <int NP> struct ScwBranch {
   static constexpr int G = NP == 16 ? 4 : 2;
   static constexpr int threads = G * NP;       // 64, 64, 128
-  static constexpr int LD = NP + 1;
-  static constexpr int VS = NP + 2;
+  static constexpr int LD = AwShape<NP>::LD;
+  static constexpr int VS = AwShape<NP>::VS;
   static constexpr int VR = SW_M_CAP + 1;      // rows of a group's V
   // B, B^T; V (A_m of the long form in its place); u ping-pong, the long form's v ping-pong; the weights
   static constexpr size_t lds_doubles = (size_t)2 * NP * LD + (size_t)G * VR * VS + (size_t)4 * G * VS + VR;
   static_assert(NP * NP <= VR * VS, "A_m of the long form lives in a group's V");
 };
 
-template <int NP> __device__ __forceinline__ double scw_group_max(double v) {
-  double m = fmax(0.0, v);
-#pragma unroll
-  for (int off = NP / 2; off >= 1; off >>= 1) m = fmax(m, __shfl_xor(m, off, NP));
-  return m;
-}
-
-// the value scaled by 2^-e with the maximum in [1/2, 1); e = 0 for an all-zero vector (ex_rescale)
-__device__ __forceinline__ double scw_rescale(double v, double mx, int& e) {
-  e = 0;
-  if (!(mx > 0.0)) return v;
-  (void)frexp(mx, &e);
-  return ldexp(v, -e);
-}
-
 // grid: (model).  sc_model_kernel's values.
 __global__ __launch_bounds__(SCW_BLOCK) void scw_model_kernel(ScwParams q) {
   const int n = q.aw.n, k = blockIdx.x;
   const size_t nn = (size_t)n * n;
   const double* __restrict__ Qk = q.Q + (size_t)k * nn;
-  double mu = 0.0;
-  for (int i = 0; i < n; ++i) mu = fmax(mu, -Qk[(size_t)i * n + i]);
+  const double mu = aw_model_mu(Qk, n);
   if (threadIdx.x == 0) q.mu[k] = mu;
-  for (int e = threadIdx.x; e < n * n; e += SCW_BLOCK) {
-    const double d = e / n == e % n ? 1.0 : 0.0;
-    q.B[(size_t)k * nn + e] = mu > 0.0 ? d + Qk[e] / mu : d;
-  }
-}
-
-// one lane per evaluation: lam = pid_k . L_root in state order (ex_root_kernel's chain)
-__global__ __launch_bounds__(SCW_BLOCK) void scw_root_kernel(ScwParams q) {
-  const AwParams& p = q.aw;
-  const size_t Ev = (size_t)p.Kc * p.Sc;
-  const size_t ev = (size_t)blockIdx.x * SCW_BLOCK + threadIdx.x;
-  if (ev >= Ev) return;
-  const int k = (int)(ev / p.Sc);
-  const double* __restrict__ Lr = p.L + ((size_t)p.root * Ev + ev) * p.NP;
-  double l = 0.0;
-  for (int i = 0; i < p.n; ++i) l = fma(p.pid[(size_t)k * p.n + i], Lr[i], l);
-  q.lam[ev] = l;
-}
-
-// grid: (step, model, site tile).  aw_down_kernel with F_b and its exponent stored: F = O_p (.) (P_sib L_sib), O_c = P_b^T F.
-template <int NP>
-__global__ __launch_bounds__(SCW_BLOCK) void scw_down_kernel(ScwParams q, const ExDown* __restrict__ steps) {
-  constexpr int G = ScwDown<NP>::G, LD = ScwDown<NP>::LD, VS = ScwDown<NP>::VS;
-  extern __shared__ __align__(16) double scw_lds[];
-  const AwParams& p = q.aw;
-  const int n = p.n;
-  double* sPs = scw_lds;                                           // sibling branch, transposed: sPs[j * LD + i] = P[i][j]
-  double* sPb = sPs + n * LD;                                      // this branch, row-major [k][i] as stored
-  double* sV = sPb + n * LD;
-  const ExDown d = steps[blockIdx.x];
-  const int k = blockIdx.y;
-  const int g = threadIdx.x / NP, a = threadIdx.x % NP;
-  const size_t Ev = (size_t)p.Kc * p.Sc, nn = (size_t)n * n;
-  const double* __restrict__ Pm = p.P + (size_t)k * p.n_edge * nn;
-  {
-    const double* __restrict__ Ps = Pm + (size_t)d.sib_edge * nn;
-    const double* __restrict__ Pb = Pm + (size_t)d.edge * nn;
-    for (int e = threadIdx.x; e < n * n; e += SCW_BLOCK) {
-      const int i = e / n, j = e - i * n;
-      sPs[j * LD + i] = Ps[e];
-      sPb[e] = Pb[e];
-    }
-  }
-  double* cs = sV + (g * 2) * VS;
-  double* cf = sV + (g * 2 + 1) * VS;
-  for (int w = 0; w < SCW_WALK; ++w) {
-    const int sb = (blockIdx.z * SCW_WALK + w) * G;                // uniform over the workgroup
-    if (sb >= p.Sc) break;
-    const int s = sb + g;
-    const bool on = s < p.Sc;
-    const size_t ev = (size_t)k * p.Sc + (on ? s : 0);
-    __syncthreads();                                               // the matrices are staged; the last item's vectors are read
-    if (on) cs[a] = p.L[((size_t)d.sib_child * Ev + ev) * NP + a];
-    __syncthreads();
-    double f = 0.0;
-    int eF = 0;
-    if (on) {
-      double acc = 0.0;
-      for (int j = 0; j < n; ++j) acc = fma(sPs[j * LD + a], cs[j], acc);
-      f = a < n ? p.O[((size_t)d.parent * Ev + ev) * NP + a] * acc : 0.0;
-      f = scw_rescale(f, scw_group_max<NP>(f), eF);
-      cf[a] = f;
-      q.F[((size_t)d.edge * Ev + ev) * NP + a] = f;
-    }
-    __syncthreads();
-    if (!on) continue;
-    double o = 0.0;
-    for (int kk = 0; kk < n; ++kk) o = fma(sPb[kk * n + a], cf[kk], o);   // lanes past n read inside the staged block and are zeroed
-    if (a >= n) o = 0.0;
-    int eO;
-    o = scw_rescale(o, scw_group_max<NP>(o), eO);
-    p.O[((size_t)d.child * Ev + ev) * NP + a] = o;
-    if (a == 0) {
-      const int32_t sF = p.sO[(size_t)d.parent * Ev + ev] + p.sL[(size_t)d.sib_child * Ev + ev] + eF;
-      q.sF[(size_t)d.edge * Ev + ev] = sF;
-      p.sO[(size_t)d.child * Ev + ev] = sF + eO;
-    }
-  }
+  for (int e = threadIdx.x; e < n * n; e += SCW_BLOCK) q.B[(size_t)k * nn + e] = aw_model_b(Qk[e], mu, e / n == e % n ? 1.0 : 0.0);
 }
 
 __device__ __forceinline__ int scw_count_col(int n, int i, int j) { return n + i * (n - 1) + (j < i ? j : j - 1); }
@@ -203,13 +103,13 @@ __global__ __launch_bounds__(ScwBranch<NP>::threads) void scw_branch_kernel(ScwP
     const int s = sb + g;
     const bool on = s < p.Sc;                                      // a group past the last site repeats site sb and stores nothing
     const size_t ev = (size_t)k * p.Sc + (on ? s : sb);
-    const double lam = q.lam[ev];
+    const double lam = p.lam[ev];
     const int e_root = p.sL[(size_t)p.root * Ev + ev];
     double* out = q.runs + ((size_t)blockIdx.x * Ev + ev) * cols;
     // an item's vectors and exponents are loaded while the item before it is computed
-    double u0n = q.F[((size_t)b_begin * Ev + ev) * NP + a];
+    double u0n = p.F[((size_t)b_begin * Ev + ev) * NP + a];
     double v0n = p.L[((size_t)q.child[b_begin] * Ev + ev) * NP + a];
-    int eFn = q.sF[(size_t)b_begin * Ev + ev], eLn = p.sL[(size_t)q.child[b_begin] * Ev + ev];
+    int eFn = p.sF[(size_t)b_begin * Ev + ev], eLn = p.sL[(size_t)q.child[b_begin] * Ev + ev];
     for (int b = b_begin; b < b_end; ++b) {
       const int M = q.form[(size_t)k * p.n_edge + b];              // uniform over the workgroup
       const double t = q.t[b];
@@ -217,9 +117,9 @@ __global__ __launch_bounds__(ScwBranch<NP>::threads) void scw_branch_kernel(ScwP
       const int eF = eFn, eL = eLn;
       if (b + 1 < b_end) {
         const int cn = q.child[b + 1];
-        u0n = q.F[((size_t)(b + 1) * Ev + ev) * NP + a];
+        u0n = p.F[((size_t)(b + 1) * Ev + ev) * NP + a];
         v0n = p.L[((size_t)cn * Ev + ev) * NP + a];
-        eFn = q.sF[(size_t)(b + 1) * Ev + ev];
+        eFn = p.sF[(size_t)(b + 1) * Ev + ev];
         eLn = p.sL[(size_t)cn * Ev + ev];
       }
       const double x = still ? 0.0 : mu * t;
@@ -351,21 +251,10 @@ inline bool scw_ok(const ScwParams& q) {
   const AwParams& p = q.aw;
   return p.n >= AW_MIN_STATES && p.n <= EX_MAX_STATES && p.NP == aw_lanes(p.n) && p.Kc >= 1 && p.Kc <= AW_GRID_MAX && p.Sc >= 1 &&
          p.Sc <= AW_GRID_MAX && (size_t)p.Kc * p.Sc * p.n * p.n <= (size_t)INT32_MAX && p.root >= p.n_tips && p.P && p.pid && p.L &&
-         p.sL && p.O && p.sO && q.Q && q.t && q.child && q.mu && q.B && q.form && q.F && q.sF && q.lam && q.runs && q.tot;
+         p.sL && p.O && p.sO && p.F && p.sF && p.lam && q.Q && q.t && q.child && q.mu && q.B && q.form && q.runs && q.tot;
 }
 
-template <int NP> inline int scw_down_tiles(const AwParams& p) { return (p.Sc + ScwDown<NP>::G * SCW_WALK - 1) / (ScwDown<NP>::G * SCW_WALK); }
 template <int NP> inline int scw_branch_tiles(const AwParams& p) { return (p.Sc + ScwBranch<NP>::G * SCW_WALK - 1) / (ScwBranch<NP>::G * SCW_WALK); }
-
-template <int NP>
-hipError_t scw_down(const ScwParams& q, const ExDown* steps, int count, hipStream_t stream) {
-  const AwParams& p = q.aw;
-  const hipError_t e = aw_allow_lds(reinterpret_cast<const void*>(scw_down_kernel<NP>), (int)(sizeof(double) * scw_down_lds_doubles<NP>(NP)));
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((scw_down_kernel<NP>), dim3(count, p.Kc, scw_down_tiles<NP>(p)), dim3(SCW_BLOCK), sizeof(double) * scw_down_lds_doubles<NP>(p.n),
-                     stream, q, steps);
-  return hipGetLastError();
-}
 
 template <int NP>
 hipError_t scw_branch(const ScwParams& q, int r0, int count, hipStream_t stream) {
@@ -385,24 +274,11 @@ hipError_t launch_scw_model(const ScwParams& q, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_scw_root(const ScwParams& q, hipStream_t stream) {
-  if (!scw_ok(q)) return hipErrorInvalidValue;
-  const size_t Ev = (size_t)q.aw.Kc * q.aw.Sc;
-  hipLaunchKernelGGL(scw_root_kernel, dim3((unsigned)((Ev + SCW_BLOCK - 1) / SCW_BLOCK)), dim3(SCW_BLOCK), 0, stream, q);
-  return hipGetLastError();
-}
-
-hipError_t launch_scw_down(const ScwParams& q, const ExDown* steps, int count, hipStream_t stream) {
-  if (count <= 0) return hipSuccess;
-  if (!scw_ok(q) || !steps || count > AW_GRID_MAX) return hipErrorInvalidValue;
-  return q.aw.NP == 16 ? scw_down<16>(q, steps, count, stream) : q.aw.NP == 32 ? scw_down<32>(q, steps, count, stream) : scw_down<64>(q, steps, count, stream);
-}
-
 hipError_t launch_scw_branch(const ScwParams& q, int r0, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   const int n_runs = (q.aw.n_edge + SC_RUN - 1) / SC_RUN;
   if (!scw_ok(q) || count > AW_GRID_MAX || r0 < 0 || r0 + count > n_runs) return hipErrorInvalidValue;
-  return q.aw.NP == 16 ? scw_branch<16>(q, r0, count, stream) : q.aw.NP == 32 ? scw_branch<32>(q, r0, count, stream) : scw_branch<64>(q, r0, count, stream);
+  return aw_with_lanes(q.aw.NP, [&](auto np) { return scw_branch<decltype(np)::value>(q, r0, count, stream); });
 }
 
 hipError_t launch_scw_total(const ScwParams& q, int count, hipStream_t stream) {

@@ -1,11 +1,11 @@
 // phm_scores_wide_api.cpp -- C-ABI of the exact conditional expectations for many rate matrices at 9..64 states
 // (phm_expected_stats_models_wide): phm_expected_stats_models' arguments, validation (ll_validate) and its
 // limit on mu t_b, then per device and per chunk of models P_k(t_b) and, per chunk of sites, section 23's tips / up / root
-// launches (AwLanes, phm_ancestral_wide_host.h) followed by the down pass with F, the branch stage and the run totals of
-// phm_scores_wide.hip.  stats == NULL asks for the log-likelihoods alone: the Pade launches and AwLanes' passes, no down pass and
-// no branch stage.  Which form of the branch stage a (model, edge) item takes is decided here (sw_form_terms) and uploaded as one
-// int32 per item.  An evaluation touches no other evaluation's buffers and the sums over the branches are grouped by compile-time
-// constants, so neither the chunks nor the shards change an output bit.
+// launches (AwLanes, phm_ancestral_wide_host.h; the root stores lam) and section 23's down pass with F stored, followed by the
+// branch stage and the run totals of phm_scores_wide.hip.  stats == NULL asks for the log-likelihoods alone: the Pade launches and
+// AwLanes' passes, no down pass and no branch stage.  Which form of the branch stage a (model, edge) item takes is decided here
+// (sw_form_terms) and uploaded as one int32 per item.  An evaluation touches no other evaluation's buffers and the sums over the
+// branches are grouped by compile-time constants, so neither the chunks nor the shards change an output bit.
 #include "phm_ancestral_wide_host.h"
 #include "phm_scores_wide.h"
 
@@ -117,10 +117,9 @@ int32_t scw_device(const ScwInput& sc, int32_t device, int64_t first, int64_t co
       for (int64_t k = 0; k < Kc; ++k)
         for (int b = 0; b < E; ++b) formh[(size_t)k * E + b] = phm::sw_form_terms(sc.mu[m0 + k] * in.edge_length[b], phm::SW_M_CAP);
       HIPCHK(hipMemcpy(dform.p, formh.data(), sizeof(int32_t) * (size_t)E * Kc, hipMemcpyHostToDevice));
-      p.O = dO.as<double>(); p.sO = dsO.as<int32_t>();
+      p.O = dO.as<double>(); p.sO = dsO.as<int32_t>(); p.F = dF.as<double>(); p.sF = dsF.as<int32_t>(); p.lam = dlam.as<double>();
       sp.Q = ln.dQ.as<double>(); sp.t = ln.dt.as<double>(); sp.child = dchild.as<int32_t>(); sp.mu = dmu.as<double>();
-      sp.B = dB.as<double>(); sp.form = dform.as<int32_t>(); sp.F = dF.as<double>(); sp.sF = dsF.as<int32_t>();
-      sp.lam = dlam.as<double>(); sp.runs = druns.as<double>(); sp.tot = dtot.as<double>();
+      sp.B = dB.as<double>(); sp.form = dform.as<int32_t>(); sp.runs = druns.as<double>(); sp.tot = dtot.as<double>();
     }
     HIPCHK(tm.start());
     st = ln.expm();
@@ -143,10 +142,8 @@ int32_t scw_device(const ScwInput& sc, int32_t device, int64_t first, int64_t co
       st = ln.passes(p);
       if (st) return st;
       if (full) {
-        HIPCHK(phm::launch_scw_root(sp, nullptr));
-        for (size_t l = 0; l + 1 < sc.down_off.size(); ++l)
-          for (int k0 = sc.down_off[l]; k0 < sc.down_off[l + 1]; k0 += step_max)
-            HIPCHK(phm::launch_scw_down(sp, down + k0, std::min(step_max, sc.down_off[l + 1] - k0), nullptr));
+        st = aw_level_steps(sc.down_off, step_max, [&](int k0, int cnt) { return phm::launch_aw_down(p, down + k0, cnt, nullptr); });
+        if (st) return st;
         for (int r0 = 0; r0 < n_runs; r0 += nr_max) {
           const int nr = std::min(nr_max, n_runs - r0);
           HIPCHK(phm::launch_scw_branch(sp, r0, nr, nullptr));
@@ -163,7 +160,7 @@ int32_t scw_device(const ScwInput& sc, int32_t device, int64_t first, int64_t co
         for (int64_t s = 0; s < Sc; ++s) {
           const size_t at = (size_t)k * Sc + s;
           const int64_t ev = ll_eval_of(in, s0 + s, m0 + k);
-          const bool possible = !ln.badh[k] && std::isfinite(ln.llh[at]);
+          const bool possible = ln.possible(k, at);
           loglik[ev] = possible ? ln.llh[at] : ninf;
           if (full)
             for (int col = 0; col < cols; ++col) stats[ev + sc.n_eval * col] = possible ? toth[at * cols + col] : nan;
