@@ -25,7 +25,7 @@ $(OBJDIR)/%.o: $(CSRC)/% $(HDRS)
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lhiprtc
 
-# test-only harness of the device building blocks (tests/test_gpu_device_blocks.py): the three shared headers, unchanged, under
+# test-only harness of the device building blocks (tests/test_gpu_device_blocks.py): the shared headers, unchanged, under
 # exactly the library's FLAGS; a library of its own, never linked into $(LIB)
 $(BLOCKS): tests/native/device_blocks.hip $(HDRS)
 	@mkdir -p $(dir $@)

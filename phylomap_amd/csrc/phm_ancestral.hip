@@ -16,13 +16,13 @@
 
 #include <algorithm>
 
+#include "phm_ll_device.h"
+
 namespace phm {
 
 namespace {
 
 constexpr int AN_BLOCK = 256;
-constexpr int AN_GRID_Y = 65535;
-constexpr double AN_LN2 = 0.69314718055994530942;
 
 // max-product over one edge: m[a] and the packed pointers of the N parent states
 template <int N>
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(AN_BLOCK) void an_up_kernel(AnParams p, const UpSte
     v[i] = m0[i] * m1[i];
     mx = fmax(mx, v[i]);
   }
-  int e = 0;
+  int e = 0;                                                       // ll_rescale's rule, fused with the store as in ll_up_kernel
   if (mx > 0.0) (void)frexp(mx, &e);
 #pragma unroll
   for (int i = 0; i < N; ++i) p.M[((size_t)u.parent * N + i) * Ev + ev] = mx > 0.0 ? ldexp(v[i], -e) : v[i];
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(AN_BLOCK) void an_root_kernel(AnParams p) {
     if (r > best) { best = r; at = a; }
   }
   p.x[(size_t)p.root * Ev + ev] = (uint8_t)at;
-  const double v = log(best) + p.sM[(size_t)ri * Ev + ev] * AN_LN2;
+  const double v = log(best) + p.sM[(size_t)ri * Ev + ev] * LN2;
   p.jlogp[ev] = (q.bad[k] || !(best > 0.0)) ? -INFINITY : v;
 }
 
@@ -125,50 +125,37 @@ __global__ __launch_bounds__(AN_BLOCK) void an_post_kernel(AnParams p, int j0) {
   }
 }
 
-inline dim3 model_grid(const LlParams& q, int y, int z) { return dim3((q.Kp + AN_BLOCK - 1) / AN_BLOCK, y, z); }
-
-inline bool an_ok(const AnParams& p) {
-  const LlParams& q = p.ll;
-  return q.n >= 2 && q.n <= LL_LANE_MAX && q.Kp % 64 == 0 && q.n_sites >= 1 && q.n_sites <= AN_GRID_Y && p.root >= q.n_tips;
-}
+inline bool an_ok(const AnParams& p) { return ll_ok(p.ll) && p.root >= p.ll.n_tips; }
 
 }  // namespace
 
 hipError_t launch_an_up(const AnParams& p, const UpStep* steps, int count, hipStream_t stream) {
   if (!an_ok(p) || !p.M || !p.sM || !p.ptr) return hipErrorInvalidValue;
-  for (int k0 = 0; k0 < count; k0 += AN_GRID_Y) {
-    const dim3 g = model_grid(p.ll, std::min(AN_GRID_Y, count - k0), p.ll.n_sites), blk(AN_BLOCK);
-    switch (p.ll.n) {
-      case 2: hipLaunchKernelGGL((an_up_kernel<2>), g, blk, 0, stream, p, steps, k0); break;
-      case 3: hipLaunchKernelGGL((an_up_kernel<3>), g, blk, 0, stream, p, steps, k0); break;
-      case 4: hipLaunchKernelGGL((an_up_kernel<4>), g, blk, 0, stream, p, steps, k0); break;
-      case 5: hipLaunchKernelGGL((an_up_kernel<5>), g, blk, 0, stream, p, steps, k0); break;
-      case 6: hipLaunchKernelGGL((an_up_kernel<6>), g, blk, 0, stream, p, steps, k0); break;
-      case 7: hipLaunchKernelGGL((an_up_kernel<7>), g, blk, 0, stream, p, steps, k0); break;
-      default: hipLaunchKernelGGL((an_up_kernel<8>), g, blk, 0, stream, p, steps, k0);
-    }
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y) {
+    const dim3 g = model_grid(p.ll, AN_BLOCK, std::min(LL_GRID_Y, count - k0), p.ll.n_sites);
+    ll_with_states(p.ll.n, [&](auto ns) { hipLaunchKernelGGL((an_up_kernel<decltype(ns)::value>), g, dim3(AN_BLOCK), 0, stream, p, steps, k0); });
   }
   return hipGetLastError();
 }
 
 hipError_t launch_an_root(const AnParams& p, hipStream_t stream) {
   if (!an_ok(p) || !p.M || !p.sM || !p.x || !p.jlogp) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(an_root_kernel, model_grid(p.ll, 1, p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p);
+  hipLaunchKernelGGL(an_root_kernel, model_grid(p.ll, AN_BLOCK, 1, p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p);
   return hipGetLastError();
 }
 
 hipError_t launch_an_trace(const AnParams& p, const ExDown* steps, int count, hipStream_t stream) {
   if (!an_ok(p) || !p.ptr || !p.x) return hipErrorInvalidValue;
-  for (int k0 = 0; k0 < count; k0 += AN_GRID_Y)
-    hipLaunchKernelGGL(an_trace_kernel, model_grid(p.ll, std::min(AN_GRID_Y, count - k0), p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p,
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y)
+    hipLaunchKernelGGL(an_trace_kernel, model_grid(p.ll, AN_BLOCK, std::min(LL_GRID_Y, count - k0), p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p,
                        steps, k0);
   return hipGetLastError();
 }
 
 hipError_t launch_an_post(const AnParams& p, int j0, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (!an_ok(p) || !p.O || !p.sel || !p.post || j0 < 0 || count > AN_GRID_Y) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(an_post_kernel, model_grid(p.ll, count, p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p, j0);
+  if (!an_ok(p) || !p.O || !p.sel || !p.post || j0 < 0 || count > LL_GRID_Y) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(an_post_kernel, model_grid(p.ll, AN_BLOCK, count, p.ll.n_sites), dim3(AN_BLOCK), 0, stream, p, j0);
   return hipGetLastError();
 }
 

@@ -32,7 +32,6 @@ namespace phm {
 namespace {
 
 constexpr int AW_WALK = 4;                     // sites a group walks through the staged matrices
-constexpr double AW_LN2 = 0.69314718055994530942;
 
 // doubles of LDS: two staged matrices, two vectors per group
 template <int NP> inline size_t aw_lds_doubles(int n) { return (size_t)2 * n * AwShape<NP>::LD + (size_t)2 * AwShape<NP>::G * AwShape<NP>::VS; }
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(AW_BLOCK) void aw_root_kernel(AwParams p) {
     double l = 0.0;
     for (int i = 0; i < n; ++i) l = fma(sV[(g * 2) * VS + i], sV[(g * 2 + 1) * VS + i], l);
     if (p.lam) p.lam[ev] = l;
-    p.ll[ev] = log(l) + (double)p.sL[(size_t)p.root * Ev + ev] * AW_LN2;
+    p.ll[ev] = log(l) + (double)p.sL[(size_t)p.root * Ev + ev] * LN2;
   }
 }
 
@@ -261,7 +260,7 @@ __global__ __launch_bounds__(AW_BLOCK) void aw_jroot_kernel(AwParams p) {
   for (int off = NP / 2; off >= 1; off >>= 1) at = min(at, __shfl_xor(at, off, NP));
   if (a == 0) {
     p.x[(size_t)p.root * Ev + ev] = (uint8_t)(at == NP ? 0 : at);
-    const double v = log(best) + (double)p.sM[(size_t)ri * Ev + ev] * AW_LN2;
+    const double v = log(best) + (double)p.sM[(size_t)ri * Ev + ev] * LN2;
     p.jlogp[ev] = best > 0.0 ? v : -INFINITY;
   }
 }

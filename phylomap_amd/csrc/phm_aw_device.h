@@ -1,9 +1,12 @@
 // phm_aw_device.h -- the device pieces of the one-state-per-lane kernels at 9..64 states, shared by
 // phm_ancestral_wide.hip, phm_scores_wide.hip and phm_sample_wide.hip: the shape of a 256-lane workgroup of NP-lane groups, the
-// group maximum, the rescale, the transposed staging of a matrix, and mu_k and B_k of a model.
+// group maximum, the rescale and the transposed staging of a matrix.  mu_k and the cell of B_k are phm_ll_device.h's model_mu and
+// model_b, one definition for 2..64 states.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "phm_ll_device.h"
 
 namespace phm {
 
@@ -22,7 +25,7 @@ template <int NP> __device__ __forceinline__ double aw_group_max(double v) {
   return m;
 }
 
-// the value scaled by 2^-e with the maximum in [1/2, 1); e = 0 for an all-zero vector (ex_rescale)
+// ll_rescale's rule (phm_ll_device.h) with the vector across the lanes: this lane's value and the group's maximum
 __device__ __forceinline__ double aw_rescale(double v, double mx, int& e) {
   e = 0;
   if (!(mx > 0.0)) return v;
@@ -37,15 +40,5 @@ template <int NP> __device__ __forceinline__ void aw_stage_t(double* sP, const d
     sP[j * AwShape<NP>::LD + i] = P[e];
   }
 }
-
-// mu_k = max_i(-q_ii)
-__device__ __forceinline__ double aw_model_mu(const double* __restrict__ Qk, int n) {
-  double mu = 0.0;
-  for (int i = 0; i < n; ++i) mu = fmax(mu, -Qk[(size_t)i * n + i]);
-  return mu;
-}
-
-// one cell of B_k = I + Q_k / mu_k (I when mu_k = 0): q the cell of Q_k, d the cell of I
-__device__ __forceinline__ double aw_model_b(double q, double mu, double d) { return mu > 0.0 ? d + q / mu : d; }
 
 }  // namespace phm

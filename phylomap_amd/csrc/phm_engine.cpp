@@ -303,13 +303,7 @@ int32_t upload_model(phm_engine* e) {
               out[nb - 1] = t;
             }
       };
-      const int nt = (double)ktab * n * n * n < 4e6 ? 1 : std::min<int>({8, ktab, (int)std::max(1u, std::thread::hardware_concurrency())});
-      if (nt <= 1) rows_of(0, ktab);
-      else {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nt; ++t) th.emplace_back(rows_of, (int)((int64_t)ktab * t / nt), (int)((int64_t)ktab * (t + 1) / nt));
-        for (std::thread& t : th) t.join();
-      }
+      deal_ranges(ktab, (double)ktab * n * n * n < 4e6 ? 1 : std::min<int>({8, ktab, (int)std::max(1u, std::thread::hardware_concurrency())}), rows_of);
       HIPCHK(hipMemcpy(e->d_wt_totL.p, blk.data(), sizeof(double) * blk.size(), hipMemcpyHostToDevice));
     }
     {   // transitions that can occur at all: a -> c with B2[a][c] != 0 (c != a unless self pairs are counted).  Few of them

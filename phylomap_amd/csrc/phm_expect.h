@@ -11,6 +11,10 @@ namespace phm {
 
 constexpr int EX_MAX_STATES = 64;
 constexpr int EX_LANE_MAX = 8;                 // n <= 8: one lane per (branch, site); 9..64: one lane per (branch, site, state)
+constexpr double LN2 = 0.69314718055994530942; // a log-likelihood is log(l) + e LN2, e the sum of the passes' base-2 exponents
+
+// the column of E[N_ij], i != j, behind the n dwell columns: row-major with the diagonal left out
+__device__ __forceinline__ int count_col(int n, int i, int j) { return n + i * (n - 1) + (j < i ? j : j - 1); }
 
 struct ExDown {        // one branch of the down pass, grouped by the depth of its child
   int32_t edge;        // edge row (0-based)

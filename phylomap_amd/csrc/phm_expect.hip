@@ -13,18 +13,18 @@
 // v_{m+1} is exchanged through LDS.  The branch (its M_b and weights) is uniform over the workgroup.
 #include "phm_expect.h"
 
+#include "phm_ll_device.h"
+
 namespace phm {
 
 namespace {
 
 constexpr int EX_BLOCK = 256;
-constexpr int EX_GRID_Y = 65535;
-constexpr double EX_LN2 = 0.69314718055994530942;
 
 // 2^e / lambda for the integer e held in a double
 __device__ __forceinline__ double ex_factor(double e, double lam) { return ldexp(1.0 / lam, (int)e); }
 
-// v[0 .. n) (stride Sp) scaled by 2^-e with max in [1/2, 1); returns e (0 for an all-zero vector)
+// ll_rescale's rule (phm_ll_device.h) on v[0 .. n) of stride Sp, n at run time
 __device__ __forceinline__ int ex_rescale(double* v, int n, size_t Sp, double mx) {
   if (!(mx > 0.0)) return 0;
   int e = 0;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(EX_BLOCK) void ex_root_kernel(ExPassParams p, int r
   }
   p.sO[(size_t)root * Sp + s] = 0.0;
   p.lam[s] = l;
-  p.ll[s] = log(l) + p.sL[(size_t)root * Sp + s] * EX_LN2;
+  p.ll[s] = log(l) + p.sL[(size_t)root * Sp + s] * LN2;
 }
 
 __global__ __launch_bounds__(EX_BLOCK) void ex_down_kernel(ExPassParams p, const ExDown* __restrict__ steps, int k0) {
@@ -136,8 +136,6 @@ __global__ __launch_bounds__(EX_BLOCK) void ex_post_kernel(ExPassParams p, int r
     post[((size_t)i * rows + r) * Sp + s] = p.O[x] * p.L[x] * inv;
   }
 }
-
-__device__ __forceinline__ int ex_count_col(int n, int i, int j) { return n + i * (n - 1) + (j < i ? j : j - 1); }
 
 template <int NS>
 __global__ __launch_bounds__(EX_BLOCK) void ex_branch_lane_kernel(ExBranchParams p) {
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(EX_BLOCK) void ex_branch_lane_kernel(ExBranchParams
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
       if (i == j) out[(size_t)i * ld] = I[i][i] * f;
-      else out[(size_t)ex_count_col(NS, i, j) * ld] = p.qoff[i * NS + j] * I[i][j] * f;
+      else out[(size_t)count_col(NS, i, j) * ld] = p.qoff[i * NS + j] * I[i][j] * f;
     }
 }
 
@@ -278,7 +276,7 @@ __global__ __launch_bounds__(ExWide<NP>::threads) void ex_branch_wide_kernel(ExB
     double Iij;
     if constexpr (ILDS) Iij = sI[i][j]; else Iij = I[i];
     if (i == j) out[(size_t)i * ld] = Iij * f;
-    else out[(size_t)ex_count_col(n, i, j) * ld] = p.qoff[i * n + j] * Iij * f;
+    else out[(size_t)count_col(n, i, j) * ld] = p.qoff[i * n + j] * Iij * f;
   }
 }
 
@@ -372,14 +370,14 @@ void launch_wide(const ExBranchParams& p, int count, hipStream_t stream) {
 }  // namespace
 
 hipError_t launch_ex_tips(const ExPassParams& p, const uint8_t* tips, const int32_t* obs, hipStream_t stream) {
-  for (int t0 = 0; t0 < p.n_tips; t0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_tips_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, p.n_tips - t0)), dim3(EX_BLOCK), 0, stream, p, tips, obs, t0);
+  for (int t0 = 0; t0 < p.n_tips; t0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_tips_kernel, site_grid(p.Sp, std::min(LL_GRID_Y, p.n_tips - t0)), dim3(EX_BLOCK), 0, stream, p, tips, obs, t0);
   return hipGetLastError();
 }
 
 hipError_t launch_ex_up(const ExPassParams& p, const UpStep* steps, int count, hipStream_t stream) {
-  for (int k0 = 0; k0 < count; k0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_up_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, steps, k0);
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_up_kernel, site_grid(p.Sp, std::min(LL_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, steps, k0);
   return hipGetLastError();
 }
 
@@ -389,57 +387,48 @@ hipError_t launch_ex_root(const ExPassParams& p, int root_row, const double* pid
 }
 
 hipError_t launch_ex_down(const ExPassParams& p, const ExDown* steps, int count, hipStream_t stream) {
-  for (int k0 = 0; k0 < count; k0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_down_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, steps, k0);
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_down_kernel, site_grid(p.Sp, std::min(LL_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, steps, k0);
   return hipGetLastError();
 }
 
 hipError_t launch_ex_post(const ExPassParams& p, int rows, double* post, hipStream_t stream) {
-  for (int r0 = 0; r0 < rows; r0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_post_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, rows - r0)), dim3(EX_BLOCK), 0, stream, p, rows, post, r0);
+  for (int r0 = 0; r0 < rows; r0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_post_kernel, site_grid(p.Sp, std::min(LL_GRID_Y, rows - r0)), dim3(EX_BLOCK), 0, stream, p, rows, post, r0);
   return hipGetLastError();
 }
 
 hipError_t launch_ex_branch(const ExBranchParams& p, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (count > EX_GRID_Y || p.Sp % 64 != 0) return hipErrorInvalidValue;
-  const dim3 lane_grid = site_grid(p.Sp, count);
-  switch (p.n) {
-    case 2: hipLaunchKernelGGL((ex_branch_lane_kernel<2>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 3: hipLaunchKernelGGL((ex_branch_lane_kernel<3>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 4: hipLaunchKernelGGL((ex_branch_lane_kernel<4>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 5: hipLaunchKernelGGL((ex_branch_lane_kernel<5>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 6: hipLaunchKernelGGL((ex_branch_lane_kernel<6>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 7: hipLaunchKernelGGL((ex_branch_lane_kernel<7>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    case 8: hipLaunchKernelGGL((ex_branch_lane_kernel<8>), lane_grid, dim3(EX_BLOCK), 0, stream, p); break;
-    default:
-      if (p.n <= 16) launch_wide<16>(p, count, stream);
-      else if (p.n <= 32) launch_wide<32>(p, count, stream);
-      else if (p.n <= EX_MAX_STATES) launch_wide<64>(p, count, stream);
-      else return hipErrorInvalidValue;
-  }
+  if (count > LL_GRID_Y || p.Sp % 64 != 0) return hipErrorInvalidValue;
+  if (p.n >= 2 && p.n <= EX_LANE_MAX)
+    ll_with_states(p.n, [&](auto ns) { hipLaunchKernelGGL((ex_branch_lane_kernel<decltype(ns)::value>), site_grid(p.Sp, count), dim3(EX_BLOCK), 0, stream, p); });
+  else if (p.n <= 16) launch_wide<16>(p, count, stream);
+  else if (p.n <= 32) launch_wide<32>(p, count, stream);
+  else if (p.n <= EX_MAX_STATES) launch_wide<64>(p, count, stream);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 
 hipError_t launch_ex_reduce(const double* out, int cols, int count, int Sp, double* tot, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (cols > EX_GRID_Y) return hipErrorInvalidValue;
+  if (cols > LL_GRID_Y) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ex_reduce_kernel, site_grid(Sp, cols), dim3(EX_BLOCK), 0, stream, out, count, Sp, tot);
   return hipGetLastError();
 }
 
 hipError_t launch_ex_along(const ExAlongParams& p, int count, hipStream_t stream) {
-  for (int k0 = 0; k0 < count; k0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_along_kernel, site_grid(p.Sp, std::min(EX_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, k0);
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_along_kernel, site_grid(p.Sp, std::min(LL_GRID_Y, count - k0)), dim3(EX_BLOCK), 0, stream, p, k0);
   return hipGetLastError();
 }
 
 hipError_t launch_ex_range_sum(const double* x, int cols, int count, int64_t q0, const int64_t* off, int r_begin, int r_end,
                                int n_ranges, int Sp, double* tot, hipStream_t stream) {
   if (count <= 0 || r_end <= r_begin) return hipSuccess;
-  if (cols > EX_GRID_Y) return hipErrorInvalidValue;
-  for (int r0 = r_begin; r0 < r_end; r0 += EX_GRID_Y)
-    hipLaunchKernelGGL(ex_range_sum_kernel, dim3((Sp + EX_BLOCK - 1) / EX_BLOCK, cols, std::min(EX_GRID_Y, r_end - r0)),
+  if (cols > LL_GRID_Y) return hipErrorInvalidValue;
+  for (int r0 = r_begin; r0 < r_end; r0 += LL_GRID_Y)
+    hipLaunchKernelGGL(ex_range_sum_kernel, dim3((Sp + EX_BLOCK - 1) / EX_BLOCK, cols, std::min(LL_GRID_Y, r_end - r0)),
                        dim3(EX_BLOCK), 0, stream, x, count, q0, off, r0, n_ranges, Sp, tot);
   return hipGetLastError();
 }

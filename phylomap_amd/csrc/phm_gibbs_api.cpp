@@ -8,8 +8,6 @@
 // phm_sample_histories_models with draws = 1 addresses them, rates by (ENT_RATE | parameter, chain, iteration + replica_offset).
 #include "phm_gibbs_host.h"
 
-#include <limits>
-
 namespace {
 
 using namespace phm_ex;
@@ -25,14 +23,11 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   const size_t nn = (size_t)n * n;
   const int64_t C = in.K;
   const int64_t S_eval = in.sites_per_model();           // sites per chain
-  const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
   double kernel_ms = 0.0;
-  using Clock = std::chrono::steady_clock;
   const bool q_timing = g_phm_debug.q_timing != 0;      // host clock of the phases of an iteration, printed to stderr
   double up_ms = 0.0, run_ms = 0.0, host_ms = 0.0;
   int launches = 0;
-  auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
   LlLanes ln(in);
   DevBuf ddown, dorder, derr;
   st = ln.upload_tree();
@@ -125,36 +120,17 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
 
     // the update of chains [k_lo, k_hi) of the chunk from the iteration's download
     auto update = [&](int iter, int64_t k_lo, int64_t k_hi) {
-      const bool rec = iter % g.thin == 0;
-      const int64_t r = iter / g.thin;
-      const uint32_t rep = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
       for (int64_t k = k_lo; k < k_hi; ++k) {
         const int64_t ch = m0 + k;
         double* thk = &th[(size_t)k * np];
-        double ll = 0.0;
-        for (int64_t s = 0; s < S_eval; ++s) ll += outh[(size_t)cols * npad + (size_t)(s * Kp + k)];
+        auto over_sites = [&](int c) {                   // column c of the download summed over the chain's sites, ascending
+          double v = 0.0;
+          for (int64_t s = 0; s < S_eval; ++s) v += outh[(size_t)c * npad + (size_t)(s * Kp + k)];
+          return v;
+        };
+        const double ll = over_sites(cols);
         if (!g.status[ch] && !std::isfinite(ll)) g.status[ch] = 1;
-        double* th_row = g.theta + ((size_t)r * C + ch) * np;
-        double* st_row = g.stats ? g.stats + ((size_t)r * C + ch) * cols : nullptr;
-        if (g.status[ch]) {                              // an impossible chain: NaN from here on, its lanes idle on the device
-          if (rec) {
-            std::fill_n(th_row, np, nan);
-            g.loglik[(size_t)r * C + ch] = nan;
-            if (st_row) std::fill_n(st_row, cols, nan);
-          }
-          continue;
-        }
-        if (rec) {
-          std::copy_n(thk, np, th_row);
-          g.loglik[(size_t)r * C + ch] = ll;
-          if (st_row)
-            for (int c = 0; c < cols; ++c) {
-              double v = 0.0;
-              for (int64_t s = 0; s < S_eval; ++s) v += outh[(size_t)c * npad + (size_t)(s * Kp + k)];
-              st_row[c] = v;
-            }
-        }
-        const double* pr = g.prior + (g.n_prior > 1 ? (size_t)ch * np * 2 : 0);
+        if (!gb_record(g, iter, ch, thk, ll, over_sites)) continue;   // an impossible chain: its lanes idle on the device
         for (int c = 0; c < np; ++c) {
           double Nc = 0.0, Wc = 0.0;                     // W_c: sites ascending, within a site the entries in row-major order
           for (int64_t s = 0; s < S_eval; ++s) {
@@ -166,10 +142,7 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
                 Wc += outh[(size_t)i * npad + ln];
               }
           }
-          phm::HostStream rs{g.opt.seed, phm::ENT_RATE | (uint32_t)c, (uint32_t)ch, rep};
-          const double fresh = rs.gamma(pr[2 * c] + Nc, 1 / (pr[2 * c + 1] + Wc));
-          if (fresh > g.theta_max || !(fresh > 0.0)) ++g.rejected[(size_t)ch * np + c];   // the old value stays
-          else thk[c] = fresh;
+          gb_draw(g, iter, ch, c, Nc, Wc, thk);
         }
         fill_q(g, thk, Qh + k, (size_t)Kp);
       }
@@ -178,10 +151,9 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
 
     for (int iter = 0; iter < g.iters; ++iter) {
       sc.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
-      Clock::time_point t0 = Clock::now();
+      GbLap lap;
       HIPCHK(hipMemcpy(ln.dQ.p, Qh, sizeof(double) * nn * Kp, hipMemcpyHostToDevice));
-      up_ms += since(t0);
-      t0 = Clock::now();
+      lap(up_ms);
       HIPCHK(tm.start());
       p.n_sites = 1;
       st = ln.expm(p);
@@ -194,21 +166,13 @@ int32_t gb_device(const GbInput& g, int32_t device, int64_t first, int64_t count
       HIPCHK(tm.stop());
       HIPCHK(hipMemcpy(hout.p, dout.p, sizeof(double) * out_n, hipMemcpyDeviceToHost));
       HIPCHK(tm.add_to(kernel_ms));
-      run_ms += since(t0);
-      t0 = Clock::now();
+      lap(run_ms);
       const uint32_t derrh = (uint32_t)outh[out_n - 1];
       if (derrh & phm::DERR_CAPACITY) return fail(PHM_ERR_CAPACITY, GB_FN + "a chain's jump-count series outgrew the table theta_max allows");
       const int32_t ds = device_status(derrh);
       if (ds) return ds;
-      if (n_threads <= 1) {
-        update(iter, 0, Kc);
-      } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < n_threads; ++t) pool.emplace_back(update, iter, Kc * t / n_threads, Kc * (t + 1) / n_threads);
-        update(iter, 0, Kc / n_threads);
-        for (std::thread& t : pool) t.join();
-      }
-      host_ms += since(t0);
+      deal_ranges(Kc, n_threads, [&](int64_t k_lo, int64_t k_hi) { update(iter, k_lo, k_hi); });
+      lap(host_ms);
     }
     int levels = 0;
     for (size_t l = 0; l + 1 < g.level_off.size(); ++l) levels += g.level_off[l + 1] > g.level_off[l] ? 1 : 0;

@@ -1,8 +1,12 @@
 // phm_gibbs_host.h -- what the two posterior samplers of the rates of an index model share on the host: phm_gibbs_rates
 // (phm_gibbs_api.cpp, 2..8 states) and phm_gibbs_rates_wide (phm_gibbs_wide_api.cpp, 9..64 states, section
-// 25).  The checked input, Q(theta), and the one body of both entry points' argument checks (gb_validate): pure host code, no
-// device call.
+// 25).  The checked input, Q(theta), the one body of both entry points' argument checks (gb_validate), and of a chain's update
+// after an iteration the row it records (gb_record), the draw of one rate (gb_draw) and the clock of the phases (GbLap): pure
+// host code, no device call.  The chains of a chunk are dealt to host threads by deal_ranges (phm_internal.h).
 #pragma once
+
+#include <chrono>
+#include <limits>
 
 #include "phm_ancestral_wide.h"
 #include "phm_sample_host.h"
@@ -41,6 +45,42 @@ inline void fill_q(const GbInput& g, const double* th, double* Q, size_t stride)
     Q[(size_t)(i * n + i) * stride] = -row;
   }
 }
+
+// What iteration `iter` records of chain ch, if it is one of the thinned rows: the chain's theta thk, its log-likelihood ll and the
+// statistics stat(0 .. cols) -- or NaN throughout for an impossible chain (status set).  False for such a chain: it draws nothing.
+template <class Stat>
+inline bool gb_record(const GbInput& g, int iter, int64_t ch, const double* thk, double ll, Stat&& stat) {
+  const bool live = !g.status[ch];
+  if (iter % g.thin == 0) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const size_t at = (size_t)(iter / g.thin) * g.ll.K + ch;
+    for (int c = 0; c < g.p; ++c) g.theta[at * g.p + c] = live ? thk[c] : nan;
+    g.loglik[at] = live ? ll : nan;
+    if (g.stats)
+      for (int c = 0; c < g.cols; ++c) g.stats[at * g.cols + c] = live ? stat(c) : nan;
+  }
+  return live;
+}
+
+// The draw of parameter c of chain ch in iteration `iter` from its full conditional Gamma(a + N_c, rate b + W_c), on the stream
+// (ENT_RATE | c, chain, iteration + replica_offset); a draw above theta_max (or not positive) is counted and the old value stays.
+inline void gb_draw(const GbInput& g, int iter, int64_t ch, int c, double Nc, double Wc, double* thk) {
+  const double* pr = g.prior + (g.n_prior > 1 ? (size_t)ch * g.p * 2 : 0);
+  phm::HostStream rs{g.opt.seed, phm::ENT_RATE | (uint32_t)c, (uint32_t)ch, (uint32_t)iter + (uint32_t)g.opt.replica_offset};
+  const double fresh = rs.gamma(pr[2 * c] + Nc, 1 / (pr[2 * c + 1] + Wc));
+  if (fresh > g.theta_max || !(fresh > 0.0)) ++g.rejected[(size_t)ch * g.p + c];
+  else thk[c] = fresh;
+}
+
+// host clock of the phases of an iteration (q_timing): lap(ms) adds the time since the last lap
+struct GbLap {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void operator()(double& ms) {
+    const auto t1 = std::chrono::steady_clock::now();
+    ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  }
+};
 
 // Every argument check of the two entry points, in one order, and the fill of g; fn prefixes the messages.  wide = false: 2..8
 // states (more is PHM_ERR_UNSUPPORTED); wide = true: 9..64 states (2..8 is PHM_ERR_UNSUPPORTED naming phm_gibbs_rates, anything

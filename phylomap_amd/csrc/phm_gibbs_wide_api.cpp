@@ -12,9 +12,6 @@
 #include "phm_gibbs_host.h"
 #include "phm_sample_wide.h"
 
-#include <limits>
-#include <thread>
-
 namespace {
 
 using namespace phm_ex;
@@ -34,11 +31,9 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
   const double nan = std::numeric_limits<double>::quiet_NaN();
   KernelTimer tm;
   double kernel_ms = 0.0, pade_ms = 0.0;
-  using Clock = std::chrono::steady_clock;
   const bool q_timing = g_phm_debug.q_timing != 0;      // host clock of the phases of an iteration, printed to stderr
   double up_ms = 0.0, run_ms = 0.0, host_ms = 0.0;
   int launches = 0, threads_used = 1;
-  auto since = [](Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); };
   AwLanes ln(in);
   DevBuf ddown, dorder, derr;
   st = ln.upload_tree();
@@ -138,9 +133,6 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
     // pass over the off-diagonal entries in row-major order, N_c += T[n + i (n - 1) + (j > i ? j - 1 : j)] and W_c += T[i] for
     // c = index[i, j], then the draws for c ascending.
     auto update = [&](int iter, int64_t k_lo, int64_t k_hi) {
-      const bool rec = iter % g.thin == 0;
-      const int64_t r = iter / g.thin;
-      const uint32_t rep = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
       std::vector<double> Nc(np), Wc(np);
       for (int64_t k = k_lo; k < k_hi; ++k) {
         const int64_t ch = m0 + k;
@@ -148,21 +140,7 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
         const double* T = redh + (size_t)k * (cols + 1);
         const double ll = T[cols];
         if (!g.status[ch] && (ln.badh[k] || !std::isfinite(ll))) g.status[ch] = 1;
-        double* th_row = g.theta + ((size_t)r * C + ch) * np;
-        double* st_row = g.stats ? g.stats + ((size_t)r * C + ch) * cols : nullptr;
-        if (g.status[ch]) {                              // an impossible chain: NaN from here on; its rates stay as they are
-          if (rec) {
-            std::fill_n(th_row, np, nan);
-            g.loglik[(size_t)r * C + ch] = nan;
-            if (st_row) std::fill_n(st_row, cols, nan);
-          }
-          continue;
-        }
-        if (rec) {
-          std::copy_n(thk, np, th_row);
-          g.loglik[(size_t)r * C + ch] = ll;
-          if (st_row) std::copy_n(T, cols, st_row);
-        }
+        if (!gb_record(g, iter, ch, thk, ll, [&](int c) { return T[c]; })) continue;   // an impossible chain: its rates stay as they are
         std::fill(Nc.begin(), Nc.end(), 0.0); std::fill(Wc.begin(), Wc.end(), 0.0);
         for (int i = 0; i < n; ++i)
           for (int j = 0; j < n; ++j) {
@@ -171,13 +149,7 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
             Nc[c - 1] += T[n + i * (n - 1) + (j > i ? j - 1 : j)];
             Wc[c - 1] += T[i];
           }
-        const double* pr = g.prior + (g.n_prior > 1 ? (size_t)ch * np * 2 : 0);
-        for (int c = 0; c < np; ++c) {
-          phm::HostStream rs{g.opt.seed, phm::ENT_RATE | (uint32_t)c, (uint32_t)ch, rep};
-          const double fresh = rs.gamma(pr[2 * c] + Nc[c], 1 / (pr[2 * c + 1] + Wc[c]));
-          if (fresh > g.theta_max || !(fresh > 0.0)) ++g.rejected[(size_t)ch * np + c];   // the old value stays
-          else thk[c] = fresh;
-        }
+        for (int c = 0; c < np; ++c) gb_draw(g, iter, ch, c, Nc[c], Wc[c], thk);
         stage(k);
       }
     };
@@ -187,12 +159,11 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
 
     for (int iter = 0; iter < g.iters; ++iter) {
       sc.replica = (uint32_t)iter + (uint32_t)g.opt.replica_offset;
-      Clock::time_point t0 = Clock::now();
+      GbLap lap;
       st = ln.set_models(Qh, sqh);
       if (st) return st;
       HIPCHK(hipMemcpy(md.ddepth.p, depth_h, sizeof(int32_t) * Kc, hipMemcpyHostToDevice));
-      up_ms += since(t0);
-      t0 = Clock::now();
+      lap(up_ms);
       HIPCHK(tm.start());
       st = ln.expm();
       if (st) return st;
@@ -210,21 +181,13 @@ int32_t gw_device(const GbInput& g, int32_t device, int64_t first, int64_t count
       HIPCHK(tm.stop());
       HIPCHK(hipMemcpy(hred.p, dred.p, sizeof(double) * red_n, hipMemcpyDeviceToHost));
       HIPCHK(tm.add_to(kernel_ms));
-      run_ms += since(t0);
-      t0 = Clock::now();
+      lap(run_ms);
       const uint32_t derrh = (uint32_t)redh[red_n - 1];
       if (derrh & phm::DERR_CAPACITY) return fail(PHM_ERR_CAPACITY, GW_FN + "a chain's jump-count series outgrew the table theta_max allows");
       const int32_t ds = device_status(derrh);
       if (ds) return ds;
-      if (n_threads <= 1) {
-        update(iter, 0, Kc);
-      } else {
-        std::vector<std::thread> pool;
-        for (int t = 1; t < n_threads; ++t) pool.emplace_back(update, iter, Kc * t / n_threads, Kc * (t + 1) / n_threads);
-        update(iter, 0, Kc / n_threads);
-        for (std::thread& t : pool) t.join();
-      }
-      host_ms += since(t0);
+      deal_ranges(Kc, n_threads, [&](int64_t k_lo, int64_t k_hi) { update(iter, k_lo, k_hi); });
+      lap(host_ms);
     }
     int levels = 0;
     for (size_t l = 0; l + 1 < g.level_off.size(); ++l) levels += g.level_off[l + 1] > g.level_off[l] ? 1 : 0;

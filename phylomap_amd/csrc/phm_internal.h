@@ -200,6 +200,17 @@ inline void host_chain_matTvec(const double* M, int n, const double* x, double* 
   }
 }
 
+// f(lo, hi) over the n_threads ranges [count t / n_threads, count (t + 1) / n_threads) of 0 .. count: the first on the calling
+// thread, every other on a host thread of its own.  The ranges must be independent of one another.
+template <class F>
+inline void deal_ranges(int64_t count, int n_threads, F&& f) {
+  if (n_threads <= 1) { f((int64_t)0, count); return; }
+  std::vector<std::thread> pool;
+  for (int t = 1; t < n_threads; ++t) pool.emplace_back([&f, count, n_threads, t] { f(count * t / n_threads, count * (t + 1) / n_threads); });
+  f((int64_t)0, count / n_threads);
+  for (std::thread& t : pool) t.join();
+}
+
 // chain tables: col[k][j][:] = Bc^k e_j  (v <- Bc v), row[k][j][:] = (Bc^T)^k e_j (w <- Bc^T w);
 // the same sums as the kernels' own chains, so entries are bit-identical to running the chain.  `fused`: the MCMC sweep with
 // n > 4; the sumstatEXP path (newunifSample :127) keeps the unfused left-to-right sums for every n.
@@ -219,11 +230,7 @@ inline void build_chain_tables(const double* Bc, int n, int ktab, std::vector<do
       }
   };
   const double work = (double)ktab * n * n * n * (want_row ? 2 : 1);
-  const int nt = work < 4e6 ? 1 : std::min<int>({8, n, (int)std::max(1u, std::thread::hardware_concurrency())});
-  if (nt <= 1) { chains(0, n); return; }
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) th.emplace_back(chains, (int)((int64_t)n * t / nt), (int)((int64_t)n * (t + 1) / nt));
-  for (std::thread& t : th) t.join();
+  deal_ranges(n, work < 4e6 ? 1 : std::min<int>({8, n, (int)std::max(1u, std::thread::hardware_concurrency())}), chains);
 }
 
 inline int32_t validate_tree_paths(const phm_tree* x, int n, int n_tip_vectors) {

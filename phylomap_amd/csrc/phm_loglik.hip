@@ -17,13 +17,13 @@
 
 #include <algorithm>
 
+#include "phm_ll_device.h"
+
 namespace phm {
 
 namespace {
 
 constexpr int LL_BLOCK = 256;
-constexpr int LL_GRID_Y = 65535;
-constexpr double LL_LN2 = 0.69314718055994530942;
 
 // squarings of expm(Q t): phm_ex::ex_squarings on this lane's Q (stride st between entries)
 __device__ __forceinline__ int ll_squarings(const double* __restrict__ q, size_t st, int n, double t) {
@@ -140,10 +140,9 @@ __device__ __forceinline__ bool ll_expm_reg(const double (&q)[N * N], double tb,
 
 template <int N>
 __global__ __launch_bounds__(LL_BLOCK) void ll_expm_reg_kernel(LlParams p, int e0) {
-  const int k = blockIdx.x * LL_BLOCK + threadIdx.x;
-  if (k >= p.Kc) return;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<LL_BLOCK>(p);
+  if (idle) return;
   const int b = e0 + blockIdx.y;
-  const size_t Kp = p.Kp;
   double q[N * N], X[N * N];
 #pragma unroll
   for (int e = 0; e < N * N; ++e) q[e] = p.Q[(size_t)e * Kp + k];
@@ -166,11 +165,10 @@ __device__ __forceinline__ void ll_gemm_ws(const double* A, const double* B, dou
 
 // 5..8 states: the same steps as ll_expm_reg on [matrix][entry][model] rows of `work`; X is the lane's column of P itself
 __global__ __launch_bounds__(LL_BLOCK) void ll_expm_ws_kernel(LlParams p, int e0) {
-  const int k = blockIdx.x * LL_BLOCK + threadIdx.x;
-  if (k >= p.Kc) return;
+  const auto [k, st, Ev, ev, idle] = ll_lane<LL_BLOCK>(p);
+  if (idle) return;
   const int n = p.n, nn = n * n;
   const int b = e0 + blockIdx.y;
-  const size_t st = p.Kp;
   const double* __restrict__ q = p.Q + k;
   double* A = p.work + (size_t)blockIdx.y * 4 * nn * st + k;
   double *Em = A + (size_t)nn * st, *Dm = A + (size_t)2 * nn * st, *T2 = A + (size_t)3 * nn * st;
@@ -237,21 +235,19 @@ __global__ __launch_bounds__(LL_BLOCK) void ll_expm_ws_kernel(LlParams p, int e0
 }
 
 __global__ __launch_bounds__(LL_BLOCK) void ll_tips_kernel(LlParams p, int t0) {
-  const int k = blockIdx.x * LL_BLOCK + threadIdx.x;
-  if (k >= p.Kc) return;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<LL_BLOCK>(p);
+  if (idle) return;
   const int t = t0 + blockIdx.y, site = blockIdx.z;
-  const size_t Ev = (size_t)p.n_sites * p.Kp, ev = (size_t)site * p.Kp + k;
-  const int y = p.paired ? p.tips[(size_t)t * p.Kp + k] : p.tips[(size_t)site * p.n_tips + t];
+  const int y = p.paired ? p.tips[(size_t)t * Kp + k] : p.tips[(size_t)site * p.n_tips + t];
   for (int i = 0; i < p.n; ++i) p.L[((size_t)t * p.n + i) * Ev + ev] = (y == 0 || p.obs[i] == y) ? 1.0 : 0.0;
   p.sL[(size_t)t * Ev + ev] = 0.0;
 }
 
 template <int N>
 __global__ __launch_bounds__(LL_BLOCK) void ll_up_kernel(LlParams p, const UpStep* __restrict__ steps, int k0) {
-  const int k = blockIdx.x * LL_BLOCK + threadIdx.x;
-  if (k >= p.Kc) return;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<LL_BLOCK>(p);
+  if (idle) return;
   const UpStep u = steps[k0 + blockIdx.y];
-  const size_t Kp = p.Kp, Ev = (size_t)p.n_sites * Kp, ev = (size_t)blockIdx.z * Kp + k;
   const int r0 = u.child[0] >= 0 ? p.n_tips + u.child[0] : ~u.child[0];
   const int r1 = u.child[1] >= 0 ? p.n_tips + u.child[1] : ~u.child[1];
   const int rp = p.n_tips + u.parent;
@@ -275,31 +271,28 @@ __global__ __launch_bounds__(LL_BLOCK) void ll_up_kernel(LlParams p, const UpSte
     v[i] = a * b;
     mx = fmax(mx, v[i]);
   }
-  int e = 0;
-  if (mx > 0.0) (void)frexp(mx, &e);
+  int e = 0;                                                       // ll_rescale's rule, fused with the store: with its call form a
+  if (mx > 0.0) (void)frexp(mx, &e);                               // call at 8 states timed 1.3 to 3 % slower (docs/MEASUREMENTS.md)
 #pragma unroll
   for (int i = 0; i < N; ++i) p.L[((size_t)rp * N + i) * Ev + ev] = mx > 0.0 ? ldexp(v[i], -e) : v[i];
   p.sL[(size_t)rp * Ev + ev] = p.sL[(size_t)r0 * Ev + ev] + p.sL[(size_t)r1 * Ev + ev] + e;
 }
 
 __global__ __launch_bounds__(LL_BLOCK) void ll_root_kernel(LlParams p, int root) {
-  const int k = blockIdx.x * LL_BLOCK + threadIdx.x;
-  if (k >= p.Kc) return;
-  const size_t Kp = p.Kp, Ev = (size_t)p.n_sites * Kp, ev = (size_t)blockIdx.z * Kp + k;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<LL_BLOCK>(p);
+  if (idle) return;
   double l = 0.0;
   for (int i = 0; i < p.n; ++i) l = fma(p.pid[(size_t)i * Kp + k], p.L[((size_t)root * p.n + i) * Ev + ev], l);
-  const double v = log(l) + p.sL[(size_t)root * Ev + ev] * LL_LN2;
+  const double v = log(l) + p.sL[(size_t)root * Ev + ev] * LN2;
   p.ll[ev] = (p.bad[k] || !(l > 0.0)) ? -INFINITY : v;
 }
-
-inline dim3 model_grid(const LlParams& p, int y, int z) { return dim3((p.Kp + LL_BLOCK - 1) / LL_BLOCK, y, z); }
 
 }  // namespace
 
 hipError_t launch_ll_expm(const LlParams& p, int e0, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (count > LL_GRID_Y || p.Kp % 64 != 0 || p.n < 2 || p.n > LL_LANE_MAX) return hipErrorInvalidValue;
-  const dim3 g = model_grid(p, count, 1), blk(LL_BLOCK);
+  if (count > LL_GRID_Y || p.Kp % 64 != 0 || !ll_states_ok(p)) return hipErrorInvalidValue;
+  const dim3 g = model_grid(p, LL_BLOCK, count, 1), blk(LL_BLOCK);
   switch (p.n) {
     case 2: hipLaunchKernelGGL((ll_expm_reg_kernel<2>), g, blk, 0, stream, p, e0); break;
     case 3: hipLaunchKernelGGL((ll_expm_reg_kernel<3>), g, blk, 0, stream, p, e0); break;
@@ -312,32 +305,24 @@ hipError_t launch_ll_expm(const LlParams& p, int e0, int count, hipStream_t stre
 }
 
 hipError_t launch_ll_tips(const LlParams& p, hipStream_t stream) {
-  if (p.n_sites < 1 || p.n_sites > LL_GRID_Y) return hipErrorInvalidValue;
+  if (!ll_sites_ok(p)) return hipErrorInvalidValue;
   for (int t0 = 0; t0 < p.n_tips; t0 += LL_GRID_Y)
-    hipLaunchKernelGGL(ll_tips_kernel, model_grid(p, std::min(LL_GRID_Y, p.n_tips - t0), p.n_sites), dim3(LL_BLOCK), 0, stream, p, t0);
+    hipLaunchKernelGGL(ll_tips_kernel, model_grid(p, LL_BLOCK, std::min(LL_GRID_Y, p.n_tips - t0), p.n_sites), dim3(LL_BLOCK), 0, stream, p, t0);
   return hipGetLastError();
 }
 
 hipError_t launch_ll_up(const LlParams& p, const UpStep* steps, int count, hipStream_t stream) {
-  if (p.n_sites < 1 || p.n_sites > LL_GRID_Y || p.n < 2 || p.n > LL_LANE_MAX) return hipErrorInvalidValue;
+  if (!ll_sites_ok(p) || !ll_states_ok(p)) return hipErrorInvalidValue;
   for (int k0 = 0; k0 < count; k0 += LL_GRID_Y) {
-    const dim3 g = model_grid(p, std::min(LL_GRID_Y, count - k0), p.n_sites), blk(LL_BLOCK);
-    switch (p.n) {
-      case 2: hipLaunchKernelGGL((ll_up_kernel<2>), g, blk, 0, stream, p, steps, k0); break;
-      case 3: hipLaunchKernelGGL((ll_up_kernel<3>), g, blk, 0, stream, p, steps, k0); break;
-      case 4: hipLaunchKernelGGL((ll_up_kernel<4>), g, blk, 0, stream, p, steps, k0); break;
-      case 5: hipLaunchKernelGGL((ll_up_kernel<5>), g, blk, 0, stream, p, steps, k0); break;
-      case 6: hipLaunchKernelGGL((ll_up_kernel<6>), g, blk, 0, stream, p, steps, k0); break;
-      case 7: hipLaunchKernelGGL((ll_up_kernel<7>), g, blk, 0, stream, p, steps, k0); break;
-      default: hipLaunchKernelGGL((ll_up_kernel<8>), g, blk, 0, stream, p, steps, k0);
-    }
+    const dim3 g = model_grid(p, LL_BLOCK, std::min(LL_GRID_Y, count - k0), p.n_sites);
+    ll_with_states(p.n, [&](auto ns) { hipLaunchKernelGGL((ll_up_kernel<decltype(ns)::value>), g, dim3(LL_BLOCK), 0, stream, p, steps, k0); });
   }
   return hipGetLastError();
 }
 
 hipError_t launch_ll_root(const LlParams& p, int root_row, hipStream_t stream) {
-  if (p.n_sites < 1 || p.n_sites > LL_GRID_Y) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ll_root_kernel, model_grid(p, 1, p.n_sites), dim3(LL_BLOCK), 0, stream, p, root_row);
+  if (!ll_sites_ok(p)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ll_root_kernel, model_grid(p, LL_BLOCK, 1, p.n_sites), dim3(LL_BLOCK), 0, stream, p, root_row);
   return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include <algorithm>
 
 #include "phm_history.h"
+#include "phm_ll_device.h"
 #include "phm_sample_branch.h"
 
 namespace phm {
@@ -41,13 +42,12 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_table_kernel(SmParams p) {
   if (k >= q.Kp) return;
   const int n = q.n, nn = n * n;
   const size_t Kp = q.Kp;
-  double mu = 0.0;
-  for (int i = 0; i < n; ++i) mu = fmax(mu, -q.Q[(size_t)(i * n + i) * Kp + k]);
+  const double mu = model_mu(q.Q + k, Kp, n);
   p.mu[k] = mu;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j) {
       const double d = i == j ? 1.0 : 0.0;
-      p.B[(size_t)(i * n + j) * Kp + k] = mu > 0.0 ? d + q.Q[(size_t)(i * n + j) * Kp + k] / mu : d;
+      p.B[(size_t)(i * n + j) * Kp + k] = model_b(q.Q[(size_t)(i * n + j) * Kp + k], mu, d);
       p.beta[(size_t)(i * n + j) * Kp + k] = d;
     }
   int depth;

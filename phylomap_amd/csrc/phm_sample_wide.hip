@@ -40,7 +40,7 @@ __global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
   double* next = prev + nn;
   const double* __restrict__ Qk = p.Q + (size_t)k * nn;
   if (threadIdx.x == 0) {
-    s_mu = aw_model_mu(Qk, n);
+    s_mu = model_mu(Qk, 1, n);
     p.mu[k] = s_mu;
   }
   __syncthreads();
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(SW_TABLE_BLOCK) void sw_table_kernel(SwParams p) {
   for (int cell = threadIdx.x; cell < nn; cell += SW_TABLE_BLOCK) {
     const int i = cell / n, j = cell - i * n;
     const double d = i == j ? 1.0 : 0.0;
-    const double b = aw_model_b(Qk[cell], mu, d);
+    const double b = model_b(Qk[cell], mu, d);
     p.B[(size_t)k * nn + cell] = b;
     sB[i * LD + j] = b;
     prev[cell] = d;                                                  // beta_0 = I (symmetric: [e][c] as well)

@@ -22,24 +22,14 @@
 
 #include <algorithm>
 
+#include "phm_ll_device.h"
+
 namespace phm {
 
 namespace {
 
 constexpr int SC_BLOCK = 256;                  // passes
 constexpr int SC_BRANCH_BLOCK = 64;            // branch stage: one wave per block (register-heavy, and K is often small)
-constexpr int SC_GRID_Y = 65535;
-
-// v[0 .. N) scaled by 2^-e with max in [1/2, 1); returns e (0 for an all-zero vector)
-template <int N>
-__device__ __forceinline__ int sc_rescale(double (&v)[N], double mx) {
-  if (!(mx > 0.0)) return 0;
-  int e = 0;
-  (void)frexp(mx, &e);
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = ldexp(v[i], -e);
-  return e;
-}
 
 __global__ __launch_bounds__(SC_BLOCK) void sc_model_kernel(ScParams p) {
   const LlParams& q = p.ll;
@@ -47,22 +37,17 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_model_kernel(ScParams p) {
   if (k >= q.Kp) return;
   const int n = q.n;
   const size_t Kp = q.Kp;
-  double mu = 0.0;
-  for (int i = 0; i < n; ++i) mu = fmax(mu, -q.Q[(size_t)(i * n + i) * Kp + k]);
+  const double mu = model_mu(q.Q + k, Kp, n);
   p.mu[k] = mu;
   if (!p.B) return;
   for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) {
-      const double d = i == j ? 1.0 : 0.0;
-      p.B[(size_t)(i * n + j) * Kp + k] = mu > 0.0 ? d + q.Q[(size_t)(i * n + j) * Kp + k] / mu : d;
-    }
+    for (int j = 0; j < n; ++j) p.B[(size_t)(i * n + j) * Kp + k] = model_b(q.Q[(size_t)(i * n + j) * Kp + k], mu, i == j ? 1.0 : 0.0);
 }
 
 __global__ __launch_bounds__(SC_BLOCK) void sc_root_kernel(ScParams p) {
   const LlParams& q = p.ll;
-  const int k = blockIdx.x * SC_BLOCK + threadIdx.x;
-  if (k >= q.Kc) return;
-  const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp, ev = (size_t)blockIdx.z * Kp + k;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<SC_BLOCK>(q);
+  if (idle) return;
   double l = 0.0;
   for (int i = 0; i < q.n; ++i) {
     const double pi = q.pid[(size_t)i * Kp + k];
@@ -77,10 +62,9 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_root_kernel(ScParams p) {
 template <int N>
 __global__ __launch_bounds__(SC_BLOCK) void sc_down_kernel(ScParams p, const ExDown* __restrict__ steps, int k0) {
   const LlParams& q = p.ll;
-  const int k = blockIdx.x * SC_BLOCK + threadIdx.x;
-  if (k >= q.Kc) return;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<SC_BLOCK>(q);
+  if (idle) return;
   const ExDown d = steps[k0 + blockIdx.y];
-  const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp, ev = (size_t)blockIdx.z * Kp + k;
   const double* __restrict__ Ps = q.P + (size_t)d.sib_edge * N * N * Kp + k;
   const double* __restrict__ Pb = q.P + (size_t)d.edge * N * N * Kp + k;
   double ls[N], f[N], o[N];
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_down_kernel(ScParams p, const ExD
     f[i] = p.O[((size_t)d.parent * N + i) * Ev + ev] * a;
     mx = fmax(mx, f[i]);
   }
-  const double sF = p.sO[(size_t)d.parent * Ev + ev] + q.sL[(size_t)d.sib_child * Ev + ev] + sc_rescale<N>(f, mx);
+  const double sF = p.sO[(size_t)d.parent * Ev + ev] + q.sL[(size_t)d.sib_child * Ev + ev] + ll_rescale<N>(f, mx);
   p.sF[(size_t)d.edge * Ev + ev] = sF;
   mx = 0.0;
 #pragma unroll
@@ -107,12 +91,10 @@ __global__ __launch_bounds__(SC_BLOCK) void sc_down_kernel(ScParams p, const ExD
     o[i] = a;
     mx = fmax(mx, a);
   }
-  p.sO[(size_t)d.child * Ev + ev] = sF + sc_rescale<N>(o, mx);
+  p.sO[(size_t)d.child * Ev + ev] = sF + ll_rescale<N>(o, mx);
 #pragma unroll
   for (int i = 0; i < N; ++i) p.O[((size_t)d.child * N + i) * Ev + ev] = o[i];
 }
-
-__device__ __forceinline__ int sc_count_col(int n, int i, int j) { return n + i * (n - 1) + (j < i ? j : j - 1); }
 
 template <int N>
 __global__ __launch_bounds__(SC_BRANCH_BLOCK) void sc_branch_kernel(ScParams p, int r0) {
@@ -131,7 +113,7 @@ __global__ __launch_bounds__(SC_BRANCH_BLOCK) void sc_branch_kernel(ScParams p, 
   double Breg[REG ? NN : 1];
   if constexpr (REG) {
 #pragma unroll
-    for (int e = 0; e < NN; ++e) {
+    for (int e = 0; e < NN; ++e) {                                 // model_b's cell, in this kernel's own spelling (its code is pinned)
       const double d = e / N == e % N ? 1.0 : 0.0;
       Breg[e] = still ? d : d + Qk[(size_t)e * Kp] / mu;
     }
@@ -206,7 +188,7 @@ __global__ __launch_bounds__(SC_BRANCH_BLOCK) void sc_branch_kernel(ScParams p, 
     for (int i = 0; i < N; ++i)
 #pragma unroll
       for (int j = 0; j < N; ++j) {
-        const int col = i == j ? i : sc_count_col(N, i, j);
+        const int col = i == j ? i : count_col(N, i, j);
         const double val = i == j ? (I[i][i] * inv) * f : (Qk[(size_t)(i * N + j) * Kp] * (I[i][j] * inv)) * f;
         if constexpr (REG) {
           tot[col] += val;
@@ -224,21 +206,15 @@ __global__ __launch_bounds__(SC_BRANCH_BLOCK) void sc_branch_kernel(ScParams p, 
 
 __global__ __launch_bounds__(SC_BLOCK) void sc_total_kernel(ScParams p, int count) {
   const LlParams& q = p.ll;
-  const int k = blockIdx.x * SC_BLOCK + threadIdx.x;
-  if (k >= q.Kc) return;
-  const size_t Kp = q.Kp, Ev = (size_t)q.n_sites * Kp, ev = (size_t)blockIdx.z * Kp + k;
+  const auto [k, Kp, Ev, ev, idle] = ll_lane<SC_BLOCK>(q);
+  if (idle) return;
   const int cols = q.n * q.n, col = blockIdx.y;
   double acc = p.tot[(size_t)col * Ev + ev];
   for (int r = 0; r < count; ++r) acc += p.runs[((size_t)r * cols + col) * Ev + ev];
   p.tot[(size_t)col * Ev + ev] = acc;
 }
 
-inline dim3 model_grid(const LlParams& q, int block, int y, int z) { return dim3((q.Kp + block - 1) / block, y, z); }
-
-inline bool sc_ok(const ScParams& p) {
-  const LlParams& q = p.ll;
-  return q.n >= 2 && q.n <= LL_LANE_MAX && q.Kp % 64 == 0 && q.n_sites >= 1 && q.n_sites <= SC_GRID_Y;
-}
+inline bool sc_ok(const ScParams& p) { return ll_ok(p.ll); }
 
 }  // namespace
 
@@ -256,17 +232,9 @@ hipError_t launch_sc_root(const ScParams& p, hipStream_t stream) {
 
 hipError_t launch_sc_down(const ScParams& p, const ExDown* steps, int count, hipStream_t stream) {
   if (!sc_ok(p)) return hipErrorInvalidValue;
-  for (int k0 = 0; k0 < count; k0 += SC_GRID_Y) {
-    const dim3 g = model_grid(p.ll, SC_BLOCK, std::min(SC_GRID_Y, count - k0), p.ll.n_sites), blk(SC_BLOCK);
-    switch (p.ll.n) {
-      case 2: hipLaunchKernelGGL((sc_down_kernel<2>), g, blk, 0, stream, p, steps, k0); break;
-      case 3: hipLaunchKernelGGL((sc_down_kernel<3>), g, blk, 0, stream, p, steps, k0); break;
-      case 4: hipLaunchKernelGGL((sc_down_kernel<4>), g, blk, 0, stream, p, steps, k0); break;
-      case 5: hipLaunchKernelGGL((sc_down_kernel<5>), g, blk, 0, stream, p, steps, k0); break;
-      case 6: hipLaunchKernelGGL((sc_down_kernel<6>), g, blk, 0, stream, p, steps, k0); break;
-      case 7: hipLaunchKernelGGL((sc_down_kernel<7>), g, blk, 0, stream, p, steps, k0); break;
-      default: hipLaunchKernelGGL((sc_down_kernel<8>), g, blk, 0, stream, p, steps, k0);
-    }
+  for (int k0 = 0; k0 < count; k0 += LL_GRID_Y) {
+    const dim3 g = model_grid(p.ll, SC_BLOCK, std::min(LL_GRID_Y, count - k0), p.ll.n_sites);
+    ll_with_states(p.ll.n, [&](auto ns) { hipLaunchKernelGGL((sc_down_kernel<decltype(ns)::value>), g, dim3(SC_BLOCK), 0, stream, p, steps, k0); });
   }
   return hipGetLastError();
 }
@@ -274,17 +242,9 @@ hipError_t launch_sc_down(const ScParams& p, const ExDown* steps, int count, hip
 hipError_t launch_sc_branch(const ScParams& p, int r0, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   const int n_runs = (p.n_edge + SC_RUN - 1) / SC_RUN;
-  if (!sc_ok(p) || count > SC_GRID_Y || r0 < 0 || r0 + count > n_runs || (p.ll.n > LL_REG_MAX && !p.B)) return hipErrorInvalidValue;
-  const dim3 g = model_grid(p.ll, SC_BRANCH_BLOCK, count, p.ll.n_sites), blk(SC_BRANCH_BLOCK);
-  switch (p.ll.n) {
-    case 2: hipLaunchKernelGGL((sc_branch_kernel<2>), g, blk, 0, stream, p, r0); break;
-    case 3: hipLaunchKernelGGL((sc_branch_kernel<3>), g, blk, 0, stream, p, r0); break;
-    case 4: hipLaunchKernelGGL((sc_branch_kernel<4>), g, blk, 0, stream, p, r0); break;
-    case 5: hipLaunchKernelGGL((sc_branch_kernel<5>), g, blk, 0, stream, p, r0); break;
-    case 6: hipLaunchKernelGGL((sc_branch_kernel<6>), g, blk, 0, stream, p, r0); break;
-    case 7: hipLaunchKernelGGL((sc_branch_kernel<7>), g, blk, 0, stream, p, r0); break;
-    default: hipLaunchKernelGGL((sc_branch_kernel<8>), g, blk, 0, stream, p, r0);
-  }
+  if (!sc_ok(p) || count > LL_GRID_Y || r0 < 0 || r0 + count > n_runs || (p.ll.n > LL_REG_MAX && !p.B)) return hipErrorInvalidValue;
+  const dim3 g = model_grid(p.ll, SC_BRANCH_BLOCK, count, p.ll.n_sites);
+  ll_with_states(p.ll.n, [&](auto ns) { hipLaunchKernelGGL((sc_branch_kernel<decltype(ns)::value>), g, dim3(SC_BRANCH_BLOCK), 0, stream, p, r0); });
   return hipGetLastError();
 }
 

@@ -51,12 +51,11 @@ __global__ __launch_bounds__(SCW_BLOCK) void scw_model_kernel(ScwParams q) {
   const int n = q.aw.n, k = blockIdx.x;
   const size_t nn = (size_t)n * n;
   const double* __restrict__ Qk = q.Q + (size_t)k * nn;
-  const double mu = aw_model_mu(Qk, n);
+  const double mu = model_mu(Qk, 1, n);
   if (threadIdx.x == 0) q.mu[k] = mu;
-  for (int e = threadIdx.x; e < n * n; e += SCW_BLOCK) q.B[(size_t)k * nn + e] = aw_model_b(Qk[e], mu, e / n == e % n ? 1.0 : 0.0);
+  for (int e = threadIdx.x; e < n * n; e += SCW_BLOCK) q.B[(size_t)k * nn + e] = model_b(Qk[e], mu, e / n == e % n ? 1.0 : 0.0);
 }
 
-__device__ __forceinline__ int scw_count_col(int n, int i, int j) { return n + i * (n - 1) + (j < i ? j : j - 1); }
 
 // grid: (run, model, site tile)
 template <int NP>
@@ -222,12 +221,12 @@ __global__ __launch_bounds__(ScwBranch<NP>::threads) void scw_branch_kernel(ScwP
         for (int i0 = 0; i0 < NP; i0 += 16) {
           double prev[16];
 #pragma unroll
-          for (int i = i0; i < i0 + 16; ++i) prev[i - i0] = (i < n && b != b_begin) ? oz[i == a ? i : scw_count_col(n, i, a)] : 0.0;
+          for (int i = i0; i < i0 + 16; ++i) prev[i - i0] = (i < n && b != b_begin) ? oz[i == a ? i : count_col(n, i, a)] : 0.0;
 #pragma unroll
           for (int i = i0; i < i0 + 16; ++i) {
             if (i < n) {
               const double val = i == a ? (I[i] * inv) * f : (Qz[(size_t)i * n + a] * (I[i] * inv)) * f;
-              oz[i == a ? i : scw_count_col(n, i, a)] = prev[i - i0] + val;
+              oz[i == a ? i : count_col(n, i, a)] = prev[i - i0] + val;
             }
           }
         }

@@ -353,3 +353,33 @@ def stat_reordered(case):
     for k in ("dcol", "dx", "ccol"):
         out[k] = np.ascontiguousarray(case[k][:, perm])
     return out
+
+
+# ---- phm_ll_device.h --------------------------------------------------------------------------------------------------------------------
+LL_N = (2, 3, 4, 5, 6, 7, 8)
+RESCALE_KINDS = ("all zero", "maximum exactly 1", "subnormal maximum", "2^1000", "maximum last", "random")
+
+
+def rescale_vectors(n):
+    """[kind, n] in the order of RESCALE_KINDS; every scaled entry stays a normal number or zero, so the scaling is exact"""
+    rs = np.random.default_rng(7000 + n)
+    one = rs.uniform(0.0, 1.0, n)
+    one[rs.integers(n)] = 1.0                                          # frexp(1.0) = (0.5, 1): e = 1
+    sub = np.array([_d(int(b)) for b in rs.integers(1, 1 << 40, n)])   # subnormals: the scaling by 2^-e goes UP
+    big = rs.uniform(0.5, 1.0, n) * 2.0 ** rs.integers(960, 1000, n)
+    big[0] = 2.0 ** 1000
+    big[n - 1] = 0.0
+    last = np.sort(rs.uniform(1e-3, 40.0, n))                          # the largest entry in the last position
+    return np.stack([np.zeros(n), one, sub, big, last, np.abs(_mixed(rs, n))])
+
+
+def model_matrices(n):
+    """[3, n, n]: two non-symmetric generators (rows sum to zero; the second with one state that is never left) and the zero matrix"""
+    rs = np.random.default_rng(7100 + n)
+    Qs = rs.uniform(0.05, 3.0, (3, n, n))
+    Qs[1, n - 1] = 0.0
+    for Q in Qs:
+        np.fill_diagonal(Q, 0.0)
+        np.fill_diagonal(Q, -Q.sum(axis=1))
+    Qs[2] = 0.0
+    return Qs

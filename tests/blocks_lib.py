@@ -31,6 +31,8 @@ ENTRIES = {
     "phmtb_coop_sample": [_int, _int, _f64p, _f64p, _i32p, _u32p, _int],
     "phmtb_wave_max": [_int, _i32p, _i32p, _int],
     "phmtb_statlanes": [_int, _int, _int, _int, _i32p, _f64p, _i32p, _i32p, _u8p, _int, _f64, _f64, _u64p, _u32p, _f64p, _int],
+    "phmtb_ll_rescale": [_int, _f64p, _f64p, _i32p, _int],
+    "phmtb_model": [_int, _f64p, _f64p, _f64p, _int],
 }
 
 _PTR_DTYPE = {_u32p: np.uint32, _i32p: np.int32, _f64p: np.float64, _u64p: np.uint64, _u8p: np.uint8}
@@ -214,3 +216,22 @@ def statlanes(ns, n, ncount, dcol, dx, ccol, cell, live, ncell, fx_scale, fx_inv
     vals = np.zeros((n + ncount, ncell))
     _call("phmtb_statlanes", ns, n, ncount, nseg, dcol, dx, ccol, cell, live, ncell, float(fx_scale), float(fx_inv), dw, ct, vals, N)
     return dw, ct, vals
+
+
+def ll_rescale(V):
+    """V [vector, n], n = 2 .. 8 -> (rescaled vectors, exponents): ll_rescale<n> reached through ll_with_states"""
+    V = _in(V, np.float64)
+    cnt, n = V.shape
+    out, e = np.zeros_like(V), np.zeros(cnt, np.int32)
+    _call("phmtb_ll_rescale", n, V, out, e, cnt)
+    return out, e
+
+
+def model(Qs):
+    """Qs [K, n, n] -> (mu [K], B [K, n, n]): model_mu and model_b on the model-fastest layout of the lane kernels"""
+    Qs = _in(Qs, np.float64)
+    K, n, _ = Qs.shape
+    q = np.ascontiguousarray(Qs.reshape(K, n * n).T)
+    mu, B = np.zeros(K), np.zeros_like(q)
+    _call("phmtb_model", n, q, mu, B, K)
+    return mu, np.ascontiguousarray(B.T).reshape(K, n, n)

@@ -167,6 +167,25 @@ def statlanes(n, ncount, dcol, dx, ccol, cell, live, ncell, fx_scale, dw_init, c
     return dw, ct
 
 
+# ---- phm_ll_device.h: the rescale rule, mu_k and B_k ---------------------------------------------------------------------------------
+def ll_rescale(v):
+    """-> (v * 2^-e, e) with max(v) * 2^-e in [1/2, 1), by numpy's frexp / ldexp; e = 0 and v untouched when no entry is positive"""
+    v = np.asarray(v, dtype=np.float64)
+    mx = max(0.0, float(v.max()))
+    if not mx > 0.0:
+        return v.copy(), 0
+    e = int(np.frexp(mx)[1])
+    return np.ldexp(v, -e), e
+
+
+def model_mu_b(Q):
+    """-> (mu = max_i(-q_ii) from 0, B = I + Q / mu with the quotient and the sum rounded one after the other; B = I when mu = 0)"""
+    Q = np.asarray(Q, dtype=np.float64)
+    mu = max(0.0, float((-np.diag(Q)).max()))
+    eye = np.eye(len(Q))
+    return mu, (eye + Q / mu if mu > 0.0 else eye)
+
+
 # ---- the oracle's exported scalar functions, elementwise ----------------------------------------------------------------------------
 def _oracle():
     import oracle_lib as O

@@ -1,5 +1,5 @@
-// device_blocks.hip -- TEST INFRASTRUCTURE ONLY: one small kernel per device building block of phm_device.h, phm_coop.h and
-// phm_history.h, each behind an extern "C" entry that uploads its inputs, launches, synchronises, copies back and returns the
+// device_blocks.hip -- TEST INFRASTRUCTURE ONLY: one small kernel per device building block of phm_device.h, phm_coop.h,
+// phm_history.h and phm_ll_device.h, each behind an extern "C" entry that uploads its inputs, launches, synchronises, copies back and returns the
 // hipError_t as an int (tests/blocks_lib.py, tests/test_gpu_device_blocks.py).  Built with the library's own flags into
 // build/tests/libphm_device_blocks.so; never linked into libphylomap_hip.so.
 //
@@ -15,6 +15,7 @@
 #include "phm_device.h"
 #include "phm_coop.h"
 #include "phm_history.h"
+#include "phm_ll_device.h"
 
 using namespace phm;
 
@@ -267,6 +268,27 @@ __global__ __launch_bounds__(TB) void k_stat_value(const unsigned long long* dwf
   out[i] = stat_cell_value(dwfx, cnt, n, c, pad, (size_t)cellno, fx_inv);
 }
 
+// ---- phm_ll_device.h ------------------------------------------------------------------------------------------------------------
+// One vector of N doubles per lane, its maximum taken as the passes take it (fmax from 0).
+template <int N>
+__global__ __launch_bounds__(TB) void k_ll_rescale(const double* v, double* out, int32_t* e, int cnt) {
+  const int i = blockIdx.x * TB + threadIdx.x;
+  if (i >= cnt) return;
+  double x[N], mx = 0.0;
+  for (int j = 0; j < N; ++j) { x[j] = v[(size_t)i * N + j]; mx = fmax(mx, x[j]); }
+  e[i] = ll_rescale<N>(x, mx);
+  for (int j = 0; j < N; ++j) out[(size_t)i * N + j] = x[j];
+}
+
+// One model per lane in the model-fastest layout: entry e of model k at Q[e * K + k]
+__global__ __launch_bounds__(TB) void k_model(int n, const double* Q, double* mu, double* B, int K) {
+  const int k = blockIdx.x * TB + threadIdx.x;
+  if (k >= K) return;
+  const double m = model_mu(Q + k, (size_t)K, n);
+  mu[k] = m;
+  for (int e = 0; e < n * n; ++e) B[(size_t)e * K + k] = model_b(Q[(size_t)e * K + k], m, e / n == e % n ? 1.0 : 0.0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +487,28 @@ int phmtb_statlanes(int ns, int n, int ncount, int nseg, const int32_t* dcol, co
   k_stat_value<<<blocks_for((long long)ncol * ncell), TB>>>(ddw.p, dcnt.p, n, (int)ncol, (size_t)ncell, fx_inv, dval.p, ncell);
   if (int e = finish()) return e;
   CK(ddw.down(dwfx)); CK(dcnt.down(cnt)); CK(dval.down(values));
+  return 0;
+}
+
+// cnt vectors of n doubles, n = 2 .. 8 through ll_with_states: out = the rescaled vectors, e = the exponents
+int phmtb_ll_rescale(int n, const double* v, double* out, int32_t* e, int cnt) {
+  if (cnt < 0 || n < 2 || n > LL_LANE_MAX) return PHMTB_BAD_ARG;
+  Buf<double> dv, dout; Buf<int32_t> de;
+  CK(dv.up(v, (size_t)cnt * n)); CK(dout.zero((size_t)cnt * n)); CK(de.zero(cnt));
+  if (cnt) ll_with_states(n, [&](auto ns) { k_ll_rescale<decltype(ns)::value><<<blocks_for(cnt), TB>>>(dv.p, dout.p, de.p, cnt); });
+  if (int err = finish()) return err;
+  CK(dout.down(out)); CK(de.down(e));
+  return 0;
+}
+
+// Q, B: [n * n][K] model-fastest; mu: [K]
+int phmtb_model(int n, const double* Q, double* mu, double* B, int K) {
+  if (K < 0 || n < 1 || n > 64) return PHMTB_BAD_ARG;
+  Buf<double> dq, dmu, db;
+  CK(dq.up(Q, (size_t)n * n * K)); CK(dmu.zero(K)); CK(db.zero((size_t)n * n * K));
+  if (K) k_model<<<blocks_for(K), TB>>>(n, dq.p, dmu.p, db.p, K);
+  if (int err = finish()) return err;
+  CK(dmu.down(mu)); CK(db.down(B));
   return 0;
 }
 

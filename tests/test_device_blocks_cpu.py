@@ -4,6 +4,7 @@ results on them), the oracle functions it compares with are within their ulp bou
 library exists and exports every entry the loader declares."""
 import ctypes as C
 import math
+from fractions import Fraction
 import os
 
 import mpmath
@@ -200,6 +201,30 @@ def test_orc_neglog_u32_within_its_bound_on_the_gpu_inputs():
         worst = max(worst, float(abs((mpmath.mpf(gi) - want) / want)))
     print(f"orc_neglog_u32: worst relative error {worst / 2.0 ** -52:.3f} * 2^-52 on {len(k)} words")
     assert worst < 1.5 * 2.0 ** -52
+
+
+# ---- phm_ll_device.h ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", Cs.LL_N)
+def test_rescale_inputs_hold_every_case_and_scale_exactly(n):
+    V = Cs.rescale_vectors(n)
+    assert len(V) == len(Cs.RESCALE_KINDS) and not V[0].any() and V[1].max() == 1.0 and V[3].max() == 2.0 ** 1000
+    assert 0.0 < V[2].max() < 2.0 ** -1022 and V[4].argmax() == n - 1 and (V >= 0.0).all()
+    for v in V:
+        got, e = R.ll_rescale(v)
+        assert [Fraction(float(x)) for x in got] == [Fraction(float(x)) / Fraction(2) ** e for x in v]     # nothing rounds
+        assert not v.any() or 0.5 <= got.max() < 1.0
+
+
+@pytest.mark.parametrize("n", [3, 8])
+def test_model_inputs_and_their_reference(n):
+    Qs = Cs.model_matrices(n)
+    assert not Qs[2].any() and (np.abs(Qs[:2].sum(axis=2)) < 1e-12).all() and Qs[1, n - 1, n - 1] == 0.0
+    for Q in Qs:
+        mu, Bm = R.model_mu_b(Q)
+        assert mu == max(0.0, max(-Q[i, i] for i in range(n)))
+        want = [[(1.0 if i == j else 0.0) + (Q[i, j] / mu if mu > 0.0 else 0.0) for j in range(n)] for i in range(n)]
+        assert Bm.tolist() == want
+    assert np.array_equal(R.model_mu_b(Qs[2])[1], np.eye(n))
 
 
 # ---- the built harness ------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The device building blocks of phm_device.h, phm_coop.h and phm_history.h, each run on its own through the test-only harness
+"""The device building blocks of phm_device.h, phm_coop.h, phm_history.h and phm_ll_device.h, each run on its own through the test-only harness
 tests/native/device_blocks.hip (built with the library's flags, the headers unchanged) and compared BIT FOR BIT with the
 references of tests/blocksref.py and with the oracle's exported functions.  The inputs (tests/blockcases.py) are the ones
 tests/test_device_blocks_cpu.py proves sharp and measures the oracle on, so equality with the oracle here inherits the ulp
@@ -252,3 +252,28 @@ def test_statlanes_fixed_point_cells(ns, fx_exp):
                                                     "dw_init", "ct_init")])
     assert np.array_equal(dw2, dw) and np.array_equal(ct2, ct)
     same_bits(vals2, vals, "stat_cell_value after reordering")
+
+
+# ---- phm_ll_device.h: the rescale rule through the state-count dispatch, mu_k and B_k ------------------------------------------------
+@pytest.mark.parametrize("n", Cs.LL_N)
+def test_ll_rescale_through_ll_with_states(n):
+    V = Cs.rescale_vectors(n)
+    got, e = B.ll_rescale(V)
+    want = [R.ll_rescale(v) for v in V]
+    for i, kind in enumerate(Cs.RESCALE_KINDS):
+        assert e[i] == want[i][1], f"ll_rescale<{n}> ({kind}): exponent {e[i]}, want {want[i][1]}"
+        same_bits(got[i], want[i][0], f"ll_rescale<{n}> ({kind})")
+    assert e[0] == 0 and e[1] == 1 and e[2] < -1021 and e[3] == 1001
+    same_bits(got[0], V[0], "an all-zero vector is left as it is")
+    assert 0.5 <= got[1:].max(axis=1).min() and got[1:].max() < 1.0 and got[4].argmax() == n - 1
+
+
+@pytest.mark.parametrize("n", [3, 8])
+def test_model_mu_and_b(n):
+    Qs = Cs.model_matrices(n)
+    mu, Bs = B.model(Qs)
+    for k, Q in enumerate(Qs):
+        want_mu, want_B = R.model_mu_b(Q)
+        same_bits(mu[k], want_mu, f"model_mu, n = {n}, matrix {k}")
+        same_bits(Bs[k], want_B, f"model_b, n = {n}, matrix {k}")
+    assert mu[2] == 0.0 and np.array_equal(Bs[2], np.eye(n))
