@@ -19,7 +19,9 @@ def akaike_weights(loglik, n_params):
 def model_average(node_post, weights=None, axis=0):
     """Weighted mean of ``node_post`` over its model axis.  ``weights``: one non-negative value per model, normalised here
     (``akaike_weights``); None: equal weights, as for a posterior sample of Q.  A model of weight 0 is left out, so it may hold
-    NaN (an impossible evaluation)."""
+    NaN (an impossible evaluation).  Nothing here is particular to node posteriors: any array with a model axis is averaged the
+    same way, ``api.expected_branch_stats_models``' ``branch`` ([K, S, n_sel, C] or [K, n_sel, C]) included -- the per-branch
+    expectations under rate uncertainty."""
     post = np.moveaxis(np.asarray(node_post, dtype=np.float64), axis, 0)
     K = post.shape[0]
     w = np.full(K, 1.0) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)

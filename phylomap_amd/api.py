@@ -475,6 +475,43 @@ def expected_sumstat_models(z, Qs, pid, sites=None, observe=None, site_of_model=
     return np.moveaxis(stats, 0, -1), ll
 
 
+def expected_branch_stats_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, edges=None, labels=None, **opt):
+    """Exact E[dwell_i | tips_s, Q_k] and E[N_ij | tips_s, Q_k] PER BRANCH for K rate matrices in one call
+    -> phm_expected_branch_stats_models, 2..64 states: where on the tree the changes happened under the models of a fit and its
+    uncertainty (``fit.sample_thetas``) or of a posterior sample of Q -- ``expected_sumstat(per_branch=True)`` with the models
+    batched.  ``Qs``, ``pid``, ``z``, ``sites``, ``observe``, ``site_of_model`` and the options are ``loglik_models``'.
+    ``edges``: 0-based edge rows of ``z['edge']`` in any order, repeats allowed (default: every row in row order); the output
+    follows the list.  ``labels``: None for full rows, or [L, n, n] (or one [n, n]) weight matrices in natural (from, to)
+    orientation -- entry (i, i) weighs E[dwell_i], entry (i, j) E[N_ij] -- for L labelled sums per branch, reduced on the device
+    (``ratemodel.count_labels``, ``ratemodel.observed_change_labels``): what a codon or hidden-rates model is asked for, where a
+    full row is thousands of values.  Returns ``(branch, loglik)``: [K, S, n_sel, C] and [K, S] ("cross"), or [K, n_sel, C] and
+    [K] with ``site_of_model`` ("paired"); C = n + n(n-1) in ``expected_sumstat``'s columns, or L.  ``loglik`` is
+    ``loglik_models``' value bit for bit; an impossible evaluation is ``-inf`` with NaN rows.  The rows of all edges, added in
+    runs of 16 edge rows, are ``expected_sumstat_models``' totals bit for bit, and a labelled sum is the plain double sum
+    ``acc = acc + w[col] * row[col]`` over the full row's columns bit for bit.  ``ancestral.model_average`` averages ``branch``
+    over the models."""
+    L = _lib.load()
+    n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
+    sel = None
+    if edges is not None:
+        sel = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+    n_sel = a.E if sel is None else sel.size
+    lab = None
+    if labels is not None:
+        lab = np.asarray(labels, dtype=np.float64)
+        if lab.ndim == 2:
+            lab = lab[None]
+        if lab.ndim != 3 or lab.shape[1:] != (n, n):
+            raise ValueError("labels must be [L, n, n]")
+        lab = np.ascontiguousarray(lab.transpose(0, 2, 1))           # column-major per matrix, as Qs
+    cols = _lib.stat_cols(n) if lab is None else lab.shape[0]
+    ll = np.zeros(shape)
+    br = np.zeros((cols, max(n_sel, 1)) + shape)                     # column slowest, evaluation (site fastest) within an entry
+    _lib.check(L.phm_expected_branch_stats_models(*head, C.byref(a.opt), n_sel, _lib._p(sel, C.c_int32), 0 if lab is None else lab.shape[0],
+                                                  _lib._p(lab, C.c_double), _lib._p(br, C.c_double), _lib._p(ll, C.c_double)))
+    return np.moveaxis(br, (0, 1), (-1, -2)), ll
+
+
 def sample_histories(z, Qs, pid, draws, sites=None, observe=None, site_of_model=None, nodes=False, maps=False, **opt):
     """``draws`` exact, independent histories given the tips for each of K rate matrices (and each site) in one call (DESIGN.md
     sections 19 and 24) -> phm_sample_histories_models (2..8 states, the models across the lanes of the tree passes) or

@@ -3,6 +3,8 @@
 Builders: ``er(n)`` (one rate), ``sym(n)`` (q_ij = q_ji), ``ard(n)`` (every off-diagonal entry its own rate, row-major order),
 ``index_model(index_matrix)`` (corHMM's ``rate.mat`` convention: 0 = structurally zero, c >= 1 = parameter c) and
 ``hidden_rates(k)`` (``synth.make2sQ``'s l01, l10, rkappas, lkappas, gammas: 2 + 3k parameters, n = 2k + 2).
+
+Labels for ``api.expected_branch_stats_models``: ``count_labels(n, pairs)`` and ``observed_change_labels(observe)``.
 """
 from __future__ import annotations
 
@@ -127,3 +129,23 @@ def hidden_rates(k):
     names = ["l01", "l10"] + [f"rkappa{i}" for i in range(1, k + 1)] + [f"lkappa{i}" for i in range(1, k + 1)] + \
             [f"gamma{i}" for i in range(1, k + 1)]
     return RateModel(2 * k + 2, names, lambda th: make2sQ(th[0], th[1], th[2:2 + k], th[2 + k:2 + 2 * k], th[2 + 2 * k:2 + 3 * k]))
+
+
+def count_labels(n, pairs):
+    """A 0/1 label for ``api.expected_branch_stats_models``: [n, n] with 1 at every (from, to) of ``pairs`` (0-based states), so
+    that the labelled sum is the expected number of those transitions on a branch.  A pair (i, i) counts E[dwell_i]."""
+    w = np.zeros((int(n), int(n)))
+    for i, j in pairs:
+        if not (0 <= int(i) < n and 0 <= int(j) < n):
+            raise ValueError("pairs must name states in 0..n-1")
+        w[int(i), int(j)] = 1.0
+    return w
+
+
+def observed_change_labels(observe):
+    """One label that counts the changes between different OBSERVED classes of a hidden-state or codon model: [n, n] with 1 at
+    (i, j) where ``observe[i] != observe[j]`` (a non-synonymous change when ``observe`` maps codons to amino acids; a change of the
+    observed character, not of the hidden regime, in a hidden-rates model).  ``observe``: the n 1-based observations of the states,
+    as given to ``api.expected_branch_stats_models``."""
+    obs = np.asarray(observe, dtype=np.int64).reshape(-1)
+    return (obs[:, None] != obs[None, :]).astype(np.float64)
