@@ -170,7 +170,9 @@ typedef struct phm_debug_options {
                                   2 = dependency-driven (same bits) */
   int32_t phase_timing;        /* 1 = record HIP events between the phases of a sweep (phm_engine_phase_ms) */
   int32_t fail_recovery;       /* 1 = every capacity recovery "does not fit" (exercises the dead-handle path) */
-  int32_t branch_group;        /* > 0: branches per wave of the 5..64-state branch kernel (clamped to 1..64); 0 = automatic */
+  int32_t branch_group;        /* (tile, branch) mapping, 2..64 states: > 0 = branches per wave of the branch kernel (clamped to
+                                  1..64); 0 = automatic (tiles x branches / 65 536, at most 16 for 2..4 states and 8 beyond).  Counts
+                                  and integer columns do not depend on it; dwell sums are rounded per group */
   int32_t level_groups;        /* (tile, branch) mapping, n <= 4 (5..32 states: 2 / 3 = the node draws and the band pruning kernel over
                                   subtree clusters; automatic on a deep tree): tree passes over clusters of tree levels (one launch per tier of eight
                                   levels) instead of one launch per level: 0 = automatic (tiles x internal nodes <= 65 536; a deep, ladder-like

@@ -280,7 +280,8 @@ MAPPING = {"auto": 0, "replicas": 1, "branches": 2, "tiles": 3}
 
 def set_debug_options(**kw):
     """Install this thread's phm_debug_options (measurement / test aids; no arguments = defaults): pruning_form, phase_timing,
-    fail_recovery, branch_group, level_groups, q_timing, pade_pivot_min, expect_chunk, sweep_parts."""
+    fail_recovery, branch_group (branches per wave of the (tile, branch) branch kernel, 2..64 states, clamped to 1..64), level_groups,
+    q_timing, pade_pivot_min, expect_chunk, sweep_parts."""
     d = DebugOptions()
     for k, v in kw.items():
         setattr(d, k, float(v) if k == "pade_pivot_min" else int(v))

@@ -628,13 +628,19 @@ inline int tiles_cnt_copies(int tiles) {
 // branches per wave of the (tile, branch) kernel for n <= 4: one while waves are scarce, up to 16 once there are 65 536 of them anyway
 int32_t tiles_branch_group(int tiles, int n_edge) { return (int32_t)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)tiles * n_edge / 65536)); }
 
+// the same with phm_debug_options.branch_group honoured (test aid: up to 64 branches per wave on a tree of any size); every user of
+// the group for n <= 4 -- TileParams::group, the segment rows of tiles_setup, the automatic sweep parts -- asks here
+inline int32_t tiles_group(const phm_engine* e, int tiles, int n_edge) {
+  return e->dbg.branch_group > 0 ? std::min(64, (int)e->dbg.branch_group) : tiles_branch_group(tiles, n_edge);
+}
+
 // Engine state of the wave-per-(tile, branch) mapping (phm_tiles.hip).
 template <int NS>
 void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& o) {
   fill_common(e, o, p);
   p.klong = e->nw_klong;
   p.tile0 = 0; p.tiles_part = e->tiles;              // phm_engine_run narrows its copies to the parts of a sweep
-  p.group = tiles_branch_group(e->tiles, p.n_edge);
+  p.group = tiles_group(e, e->tiles, p.n_edge);
   p.n_groups = (p.n_edge + p.group - 1) / p.group;
   p.n_chunks = (p.n_groups + phm::TILES_CHUNK - 1) / phm::TILES_CHUNK;
   p.rows = e->nw_total_cap;
@@ -689,7 +695,7 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   const size_t ms_bytes = long_paths ? (size_t)tiles * rows * 64 : 0;
   size_t free_b = 0, total_b = 0;
   HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const int group = tiles_branch_group(tiles, E);      // as fill_tile_params sets it; one branch per wave: no segment rows (phm_tiles.h)
+  const int group = tiles_group(e, tiles, E);      // as fill_tile_params sets it; one branch per wave: no segment rows (phm_tiles.h)
   const size_t gseg_bytes = group > 1 ? sizeof(uint32_t) * (size_t)tiles * ((E + group - 1) / group) * 64 : 0;
   const size_t need = 2 * dw_bytes + ms_bytes + pdw_bytes + gseg_bytes + pl_bytes + stats_bytes(e) + sizeof(double) * 3 * tab + (size_t)tiles * (4 * (size_t)E + Nn) * 64;
   if (int32_t st = check_hbm(need, free_b)) return st;
@@ -1242,7 +1248,7 @@ static int tiles_sweep_parts(const phm_engine* e, int n_iters) {
   int parts = e->dbg.sweep_parts;
   if (parts <= 0) {
     const int E = e->sched.n_edge;
-    const int g = tiles_branch_group(e->tiles, E);
+    const int g = tiles_group(e, e->tiles, E);
     const int64_t waves = (int64_t)e->tiles * ((E + g - 1) / g);      // of one branch-kernel launch over all tiles
     parts = (int)std::min<int64_t>(TILES_AUTO_PARTS, waves / (TILES_PART_MIN_ROUNDS * TILES_RESIDENT_WAVES));
   }
