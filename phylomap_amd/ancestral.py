@@ -37,6 +37,13 @@ def model_average(node_post, weights=None, axis=0):
     return out
 
 
+def average_over_models(values, weights=None):
+    """``model_average`` over the leading K axis, under the name the through-time results use: any part of
+    ``api.expected_through_time_models`` (``occupancy``, ``bins``, ``point_post``; [K, S, ...] or [K, ...]) averaged with
+    ``akaike_weights`` or, ``weights`` None, equally as for a posterior sample of Q.  One function: this is ``model_average``."""
+    return model_average(values, weights, axis=0)
+
+
 def collapse_states(node_post, observe):
     """Node posteriors of the OBSERVED character: ``node_post`` [..., n] summed over the states that share an observation -- the
     amino acid behind the codons, the observed character behind hidden-rate classes.  ``observe``: the n 1-based observations of
