@@ -33,8 +33,8 @@ extern "C" {
  * is its length on the posterior state.
  * 2..8 states: the models across the lanes, one plan of depths, crossings and sub-branches for every model.  9..64 states: the
  * call is accepted and served one model after another through phm_expected_through_time itself, so each model's values are that
- * entry point's bit for bit and its limits hold (a model that leaves no state is refused there); a state-per-lane form batched
- * over the models is not built yet.
+ * entry point's bit for bit and its limits hold (a model that leaves no state is refused there); the state-per-lane form batched
+ * over the models is phm_expected_through_time_models_wide of phylomap_hip_ext6.h.
  * Refusals, every one before any device call: phm_loglik_models' (ll_validate) under this entry point's name; x, Q or pid NULL,
  * every output NULL, n_states outside 2..64, and phm_expected_through_time's checks of the counts, of bounds (finite, >= 0,
  * strictly increasing; the 0-based index is named) and of the points (edge row in 0..n_edge-1, position in [0, t_b]; the 0-based

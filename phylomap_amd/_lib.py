@@ -40,6 +40,8 @@ EXT3_EXPORTS = ["phm_expected_stats_models_wide"]
 EXT4_EXPORTS = ["phm_expected_branch_stats_models"]
 # include/phylomap_hip_ext5.h: entry points added after EXT4_EXPORTS was pinned in its turn
 EXT5_EXPORTS = ["phm_expected_through_time_models"]
+# include/phylomap_hip_ext6.h: entry points added after EXT5_EXPORTS was pinned in its turn
+EXT6_EXPORTS = ["phm_expected_through_time_models_wide"]
 
 
 class PhmError(RuntimeError):
@@ -98,7 +100,7 @@ _lib = None
 
 
 def _argtypes():
-    """{symbol: argtypes} of include/phylomap_hip.h, phylomap_hip_ext.h, phylomap_hip_ext2.h, phylomap_hip_ext3.h, phylomap_hip_ext4.h and phylomap_hip_ext5.h, from the argument runs that the entry points share"""
+    """{symbol: argtypes} of include/phylomap_hip.h, phylomap_hip_ext.h, phylomap_hip_ext2.h, phylomap_hip_ext3.h, phylomap_hip_ext4.h, phylomap_hip_ext5.h and phylomap_hip_ext6.h, from the argument runs that the entry points share"""
     i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
     pi, pl, pd, pt, po = (C.POINTER(t) for t in (C.c_int32, C.c_int64, C.c_double, Tree, Options))
     sweep = [pt, i32, pd, pd, pd, f64, pi, pi, i32, i32]     # tree, n, Q, pid, B, Omega, nen, nodelist, root, N
@@ -144,6 +146,8 @@ def _argtypes():
          "phm_expected_branch_stats_models": models + [po, i32, pi, i32, pd, pd, pd],   # .., n_edges, edges, n_labels, labels, branch, loglik
          # .., n_bounds, bounds, occupancy, bin_stats, n_points, point_edge, point_pos, point_post, loglik
          "phm_expected_through_time_models": models + [po, i32, pd, pd, pd, i64, pi, pd, pd, pd],
+         # the same with n_labels, labels after bounds
+         "phm_expected_through_time_models_wide": models + [po, i32, pd, i32, pd, pd, pd, i64, pi, pd, pd, pd],
          "phm_sample_histories_models": models + [i32, po, pd, pd, pi] + maps,
          "phm_gibbs_rates": [pt, i32, pi, i32, i32, pd, pd, i32, f64, pd, i32, pi, pi, i32, i32, po, pd, pd, pd, pi, pi],
          "phm_ancestral_models": ancestral,

@@ -515,23 +515,44 @@ def expected_branch_stats_models(z, Qs, pid, sites=None, observe=None, site_of_m
 ThroughTimeModels = namedtuple("ThroughTimeModels", ["loglik", "occupancy", "bins", "point_post"])
 
 
-def expected_through_time_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, bounds=None, points=None, **opt):
-    """Exact state probabilities and expected statistics through time for K rate matrices in one call
-    -> phm_expected_through_time_models, 2..64 states: WHEN the changes happened under the models of a fit and its uncertainty
-    (``fit.sample_thetas``) or of a posterior sample of Q -- ``expected_through_time`` with the models batched (2..8 states: the
-    models across the lanes and one plan of depths, crossings and sub-branches for all of them; 9..64 states: served one model
-    after another).  ``Qs``, ``pid``, ``z``, ``sites``, ``observe``, ``site_of_model`` and the options are ``loglik_models``';
-    ``bounds`` and ``points`` are ``expected_through_time``'s.  Returns the named tuple
+def expected_through_time_models(z, Qs, pid, sites=None, observe=None, site_of_model=None, bounds=None, points=None, labels=None,
+                                 batched=False, **opt):
+    """Exact state probabilities and expected statistics through time for K rate matrices in one call (DESIGN.md sections 28
+    and 29) -> phm_expected_through_time_models, 2..64 states: WHEN the changes happened under the models of a fit and its
+    uncertainty (``fit.sample_thetas``) or of a posterior sample of Q -- ``expected_through_time`` with the models batched (2..8
+    states: the models across the lanes and one plan of depths, crossings and sub-branches for all of them; 9..64 states: served
+    one model after another).  ``batched=True`` sends a call at 9..64 states to phm_expected_through_time_models_wide instead:
+    one state per lane, batched over models, sites and items, one plan for all, a model that leaves no state served; its values
+    agree with the default's within ``expected_through_time``'s bars.  The default stays model by model so that recorded values
+    hold bit for bit; at 2..8 states ``batched`` changes nothing.  ``Qs``, ``pid``, ``z``, ``sites``, ``observe``,
+    ``site_of_model`` and the options are ``loglik_models``'; ``bounds`` and ``points`` are ``expected_through_time``'s.
+    ``labels``: None, or [L, n, n] (or one [n, n]) weight matrices in natural (from, to) orientation, as
+    ``expected_branch_stats_models`` takes them, for L labelled sums per bin reduced on the device; it needs ``batched=True`` at
+    9..64 states (labelled bins are not built for 2..8 states).  Returns the named tuple
     ``(loglik, occupancy, bins, point_post)``: [K, S] (``loglik_models``' values bit for bit), [K, S, n_bounds, n],
-    [K, S, n_bounds - 1, n + n(n-1)] in ``expected_sumstat``'s columns and [K, S, n_points, n]; with ``site_of_model`` the S axis
-    is absent; a part that was not asked for (no ``bounds``, fewer than two, no ``points``) is ``None``.  An impossible
-    evaluation is ``-inf`` with NaN rows.  ``ancestral.average_over_models`` averages any of them over the models."""
+    [K, S, n_bounds - 1, n + n(n-1)] in ``expected_sumstat``'s columns ([K, S, n_bounds - 1, L] with ``labels``) and
+    [K, S, n_points, n]; with ``site_of_model`` the S axis is absent; a part that was not asked for (no ``bounds``, fewer than
+    two, no ``points``) is ``None``.  An impossible evaluation is ``-inf`` with NaN rows.  ``ancestral.average_over_models``
+    averages any of them over the models."""
     L = _lib.load()
     n, a, shape, head = _models_on_tips(z, Qs, pid, sites, observe, site_of_model, opt)
+    wide = bool(batched) and n > 8
+    lab = None
+    if labels is not None:
+        if n <= 8:
+            raise ValueError("labels: labelled bins are not built for 2..8 states")
+        if not wide:
+            raise ValueError("labels needs batched=True at 9..64 states")
+        lab = np.asarray(labels, dtype=np.float64)
+        if lab.ndim == 2:
+            lab = lab[None]
+        if lab.ndim != 3 or lab.shape[1:] != (n, n):
+            raise ValueError("labels must be [L, n, n]")
+        lab = np.ascontiguousarray(lab.transpose(0, 2, 1))           # column-major per matrix, as Qs
     bnd = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1)
     nb = 0 if bnd is None else bnd.size
     occ = np.zeros((n, nb) + shape) if nb >= 1 else None             # column slowest, evaluation (site fastest) within a row
-    bins = np.zeros((_lib.stat_cols(n), nb - 1) + shape) if nb >= 2 else None
+    bins = np.zeros((_lib.stat_cols(n) if lab is None else lab.shape[0], nb - 1) + shape) if nb >= 2 else None
     pe = pp = post = None
     if points is not None:
         pe = np.ascontiguousarray(points[0], dtype=np.int32).reshape(-1)
@@ -540,9 +561,13 @@ def expected_through_time_models(z, Qs, pid, sites=None, observe=None, site_of_m
             raise ValueError("points: as many edge rows as positions")
         post = np.zeros((n, pe.size) + shape)
     ll = np.zeros(shape)
-    _lib.check(L.phm_expected_through_time_models(*head, C.byref(a.opt), nb, _lib._p(bnd, C.c_double), _lib._p(occ, C.c_double),
-                                                  _lib._p(bins, C.c_double), 0 if pe is None else pe.size, _lib._p(pe, C.c_int32),
-                                                  _lib._p(pp, C.c_double), _lib._p(post, C.c_double), _lib._p(ll, C.c_double)))
+    tail = (_lib._p(occ, C.c_double), _lib._p(bins, C.c_double), 0 if pe is None else pe.size, _lib._p(pe, C.c_int32),
+            _lib._p(pp, C.c_double), _lib._p(post, C.c_double), _lib._p(ll, C.c_double))
+    if wide:
+        _lib.check(L.phm_expected_through_time_models_wide(*head, C.byref(a.opt), nb, _lib._p(bnd, C.c_double),
+                                                           0 if lab is None else lab.shape[0], _lib._p(lab, C.c_double), *tail))
+    else:
+        _lib.check(L.phm_expected_through_time_models(*head, C.byref(a.opt), nb, _lib._p(bnd, C.c_double), *tail))
 
     def rows_last(x):
         return None if x is None else np.moveaxis(x, (0, 1), (-1, -2))
