@@ -403,6 +403,13 @@ int32_t upload_model(phm_engine* e) {
       HIPCHK(hipMemcpyAsync(e->d_nw_rowL.p, stage + nc, sizeof(double) * nr, hipMemcpyHostToDevice, e->last_stream));
       HIPCHK(hipMemcpyAsync(e->d_nw_maskL.p, stage + nc + nr, sizeof(double) * nm, hipMemcpyHostToDevice, e->last_stream));
     }
+    if (e->mapping == PHM_MAP_TILES && !e->wide()) {      // phm_tiles.hip: the draw thresholds of this model, from the rows of colL just enqueued
+      const double* col_dev = e->d_nw_colL.as<double>();
+      uint4* tab = e->d_tl_draw_tab.as<uint4>();
+      HIPCHK(n == 2   ? phm::launch_tiles_draw_tab<2>(e->hB2.data(), col_dev, e->nw_klong, tab, e->last_stream)
+             : n == 3 ? phm::launch_tiles_draw_tab<3>(e->hB2.data(), col_dev, e->nw_klong, tab, e->last_stream)
+                      : phm::launch_tiles_draw_tab<4>(e->hB2.data(), col_dev, e->nw_klong, tab, e->last_stream));
+    }
     HIPCHK(wait_stream(e->last_stream));               // one wait for the three: the next sweep may be enqueued on another stream
   }
   if (e->wide()) {      // 5..64 states: the model matrices live in global memory
@@ -650,6 +657,7 @@ void fill_tile_params(phm_engine* e, phm::TileParams<NS>& p, const phm_options& 
   p.cl_nodes = e->d_nw_cl_nodes.as<phm::ClusterNode>();      // NULL unless tiles_setup chose the subtree clusters
   p.cl_lvl_ptr = e->d_nw_cl_lvl_ptr.as<int32_t>(); p.cl_lvl_off = e->d_nw_cl_lvl_off.as<int32_t>();
   p.colL = e->d_nw_colL.as<double>(); p.rowL = e->d_nw_rowL.as<double>(); p.maskL = e->d_nw_maskL.as<double>();
+  p.draw_tab = e->d_tl_draw_tab.as<uint4>();
   p.tips = e->d_tips.as<uint8_t>(); p.mcount = e->d_mcount.as<uint16_t>();
   p.dw[0] = e->d_dw0.as<double>(); p.dw[1] = e->d_dw1.as<double>();
   p.estate = e->d_tl_estate.as<uint8_t>(); p.PL = e->d_PL.as<double>(); p.nstate = e->d_nstate.as<uint8_t>();
@@ -704,6 +712,7 @@ int32_t tiles_setup(phm_engine* e, const phm_tree* x, const phm_model* model, co
   HIPCHK(upload(e->d_nw_border, sp.order)); HIPCHK(upload(e->d_tl_slot, e->tl_slot));
   HIPCHK(e->d_nw_colL.alloc(sizeof(double) * tab)); HIPCHK(e->d_nw_rowL.alloc(sizeof(double) * tab));
   HIPCHK(e->d_nw_maskL.alloc(sizeof(double) * (size_t)e->nw_klong * 2 * n));
+  HIPCHK(e->d_tl_draw_tab.alloc(sizeof(uint4) * (size_t)std::min(e->nw_klong, phm::DRAW_TAB_ROWS) * n * n));
   HIPCHK(upload(e->d_tips, e->tips_host));
   HIPCHK(e->d_mcount.alloc(sizeof(uint16_t) * (size_t)tiles * E * 64));
   HIPCHK(e->d_dw0.alloc(dw_bytes)); HIPCHK(e->d_dw1.alloc(dw_bytes));
@@ -1643,6 +1652,22 @@ int32_t phm_engine_phase_ms(phm_engine* e, double* out4) {
   if (e->dead) return dead_engine();
   if (!e->phase_timing || e->mapping != PHM_MAP_TILES) return fail(PHM_ERR_STATE, "phase timing needs phm_options.phase_timing = 1 and a (tile, item) mapping");
   for (int i = 0; i < 4; ++i) out4[i] = e->phase_ms[i];
+  return PHM_OK;
+}
+
+int32_t phm_engine_debug_draw_table(phm_engine* e, uint32_t* out, int32_t cap_words, int32_t* rows_out) {
+  e = live(e);
+  if (!e || !rows_out) return fail(PHM_ERR_STATE, "engine/rows_out is NULL");
+  if (e->dead) return dead_engine();
+  if (e->mapping != PHM_MAP_TILES || e->wide() || !e->d_tl_draw_tab.p) return fail(PHM_ERR_STATE, "the draw-threshold table belongs to the (tile, branch) mapping at 2 to 4 states");
+  const int rows = std::min(e->nw_klong, phm::DRAW_TAB_ROWS);
+  *rows_out = rows;
+  const size_t words = (size_t)rows * e->n * e->n * 4;
+  if (!out) return PHM_OK;
+  if (cap_words < 0 || (size_t)cap_words < words) return fail(PHM_ERR_BAD_INPUT, "draw-threshold table: the output holds fewer than rows * n * n * 4 words");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(out, e->d_tl_draw_tab.p, sizeof(uint32_t) * words, hipMemcpyDeviceToHost));
   return PHM_OK;
 }
 

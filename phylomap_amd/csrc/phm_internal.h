@@ -35,6 +35,12 @@ inline thread_local phm_debug_options g_phm_debug = {};     // phm_set_debug_opt
 
 inline int32_t fail(int32_t st, const std::string& msg) { g_phm_err = msg; return st; }
 
+// Test aid outside the public interface (tests/test_gpu_draw_thresholds.py binds it by name): the thresholds of the segment-state draw
+// as the device built them for the model in force, (tile, branch) mapping at 2 to 4 states -- rows x n x n entries of four 32-bit words
+// (phm_draw_tab.h), entry (row * n + end state) * n + previous state; *rows_out = min(rows of the chain tables, DRAW_TAB_ROWS).  out may
+// be NULL (rows only); cap_words: the words out holds.
+extern "C" int32_t phm_engine_debug_draw_table(phm_engine* e, uint32_t* out, int32_t cap_words, int32_t* rows_out);
+
 #define HIPCHK(call)                                                                              \
   do {                                                                                            \
     hipError_t _e = (call);                                                                       \
@@ -379,6 +385,7 @@ struct phm_engine {
   // wave per (tile, branch) mapping for 10^2 .. 10^5 replicas (phm_tiles.hip); shares the level schedules and long tables
   std::vector<int32_t> tl_slot;                    // first row of every branch slot
   DevBuf d_tl_slot, d_tl_pdw, d_tl_pchunk, d_tl_cnt, d_tl_estate, d_tl_pseg, d_tl_segprev, d_tl_gseg;
+  DevBuf d_tl_draw_tab;                            // n <= 4: thresholds of the segment-state draw (phm_draw_tab.h), rebuilt on the device by every upload_model
   // Sweep parts (phm_engine_run): contiguous groups of tiles, part 0 on the caller's stream, part p > 0 on
   // part_stream[p - 1].  Forked from ev0 and joined before ev1 inside every run: nothing outside phm_engine_run sees these streams.
   static constexpr int MAX_PARTS = 4;
@@ -428,7 +435,7 @@ struct phm_engine {
                      &d_nw_up_order, &d_nw_down_order, &d_nw_node_order, &d_nw_border, &d_nw_off, &d_nw_colL, &d_nw_rowL, &d_nw_maskL, &d_nw_mcount,
                      &d_nw_dwA, &d_nw_dwB, &d_nw_mstate, &d_nw_mlen, &d_nw_estate, &d_nw_part, &d_nw_rowbuf, &d_nw_down_lv, &d_nw_dmap, &d_nw_dmap_edge, &d_nw_walk_off, &d_nw_edge_parent, &d_nw_cl_nodes, &d_nw_cl_item_off, &d_nw_cl_lvl_ptr, &d_nw_cl_lvl_off, &d_ell_col, &d_ell_val,
                      &d_ell2_col, &d_ell2_val, &d_wb_cnt, &d_tl_slot, &d_tl_pdw, &d_tl_pchunk, &d_tl_cnt, &d_tl_estate, &d_tl_pseg,
-                     &d_tl_segprev, &d_tl_gseg, &d_wt_dwfx, &d_wt_segacc, &d_wt_B2, &d_wt_totL, &d_wt_pair_slot, &d_wt_slot_col, &d_wt_B2band, &d_wt_mstate, &d_wt_dwfx_tile, &d_wt_cnt_tile, &d_wt_coef};
+                     &d_tl_segprev, &d_tl_gseg, &d_tl_draw_tab, &d_wt_dwfx, &d_wt_segacc, &d_wt_B2, &d_wt_totL, &d_wt_pair_slot, &d_wt_slot_col, &d_wt_B2band, &d_wt_mstate, &d_wt_dwfx_tile, &d_wt_cnt_tile, &d_wt_coef};
     for (DevBuf* b : all) b->reset();
     release_parts();
   }

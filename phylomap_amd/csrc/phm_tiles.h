@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "phm_device.h"
+#include "phm_draw_tab.h"
 #include "phm_sched.h"
 
 namespace phm {
@@ -32,7 +33,10 @@ namespace phm {
 constexpr int TILES_BLOCK = 256;          // four waves = four (tile, item) pairs per workgroup
 constexpr int TILES_CHUNK = 64;           // group partials per second-stage sum of the dwell reduction
 constexpr int TILES_PERSISTENT_WGS = 2048;      // workgroups of a node-draw launch: 256 CUs x 8 (four waves each: eight waves per SIMD)
-constexpr int TILES_KTAB = 24;            // chain-table rows staged in LDS by the branch kernel (longer chains: full table in L2)
+constexpr int TILES_KTAB = 24;            // chain-table rows staged in LDS by the LONG form of the branch kernel (longer chains: full table in L2)
+constexpr int TILES_TTAB = 15;            // rows of the draw-threshold table (phm_draw_tab.h) the packed form keeps in LDS, chain rows 1 .. 15: 15 x 256 B at 4 states,
+                                          //   the most that leaves <4, false, false> under 20 480 B of LDS (8 waves per SIMD); rows 16 up to
+                                          //   DRAW_TAB_ROWS - 1 come from the global table, longer chains draw arithmetically
 constexpr int TILES_CL_BLOCK = 512;       // cluster kernels: eight waves walk the levels of one (cluster, tile) with workgroup barriers
 constexpr int TILES_CL_NODES = 256;       // internal nodes per cluster when cut by subtree size (build_cluster_plan; measurement only)
 #ifndef TILES_CL_BAND
@@ -67,6 +71,8 @@ struct TileParams {
   const double* colL;                        // [klong][NS][NS]
   const double* rowL;                        // [klong][NS][NS]
   const double* maskL;                       // [klong][2][NS]
+  const uint4* draw_tab;                     // [min(klong, DRAW_TAB_ROWS)][NS][NS] thresholds of the segment-state draw (phm_draw_tab.h), entry
+                                             //   (kk * NS + end state) * NS + previous state; built by launch_tiles_draw_tab from colL and B2
   const uint8_t* tips;                       // [n_tips] or [tile][n_tips][64]
   uint16_t* mcount;                          // [tile][n_edge][64]
   double* dw[2];                             // [tile][rows][64]; sweep `it` reads dw[it & 1], writes the other
@@ -92,6 +98,11 @@ struct TileParams {
 // initial paths -> slot rows of buffer 0 and the segment counts, every lane of every tile
 hipError_t launch_tiles_init(int n_edge, int n_tiles, int64_t rows, const int32_t* slot, const int32_t* map_off,
                              const double* maps, double* dw0, uint16_t* mcount, hipStream_t stream);
+
+// the threshold table of the model (B2, colL) -> draw_tab: rows 0 .. min(klong, DRAW_TAB_ROWS) - 1, a thread per 32-bit word.  Enqueued
+// after the upload of colL on the same stream, once per model.
+template <int NS>
+hipError_t launch_tiles_draw_tab(const double* B2_host, const double* colL, int klong, uint4* draw_tab, hipStream_t stream);
 
 struct McmcMapsLaunch;      // phm_mcmc_maps.h
 

@@ -431,14 +431,27 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
   __shared__ double s_dw_all[(TILES_BLOCK / 64) * NS * 64];
   __shared__ uint16_t s_cnt_all[(TILES_BLOCK / 64) * NCNT * 64];      // counts of ONE branch (<= 65 535 segments): 16 bits keep the block under 20 KB of LDS, 8 waves per SIMD
   __shared__ double s_B2[NS * NS], s_scale[NS];      // indexed by a per-lane state: LDS, not the kernarg segment
-  __shared__ double s_col[TILES_KTAB * NS * NS];     // B^k e_j for the short chains (most draws); longer ones go to L2
+  // LONG: B^k e_j for the short chains (most draws); longer ones go to L2.  The packed form draws from integer thresholds instead
+  // (phm_draw_tab.h): the entries of chain rows 1 .. TILES_TTAB (no step draws from row 0: the last segment's state is the end state's)
+  // and, last, one entry with the fallback bit that every index outside them is clamped to, so that one test of the entry sends a
+  // lane to draw_state_far
+  constexpr int TTAB_N = TILES_TTAB * NS * NS;
+  __shared__ double s_col[LONG ? TILES_KTAB * NS * NS : 1];
+  __shared__ uint4 s_tab[LONG ? 1 : TTAB_N + 1];
   __shared__ __align__(16) double s_ltab[2 * PHM_LOGTAB_N];        // (1/c_j, log c_j) of the exponential variates (neglog_u32)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform: slot bases live in scalar registers
   const int item = blockIdx.x * (TILES_BLOCK / 64) + wave;
   const uint32_t lane8 = (uint32_t)lane * 8u;
   const int ktab = min(TILES_KTAB, p.klong);
-  for (int i = threadIdx.x; i < ktab * NS * NS; i += TILES_BLOCK) s_col[i] = p.colL[i];
+  const int rtab = min(DRAW_TAB_ROWS, p.klong);      // rows of p.draw_tab
+  if (LONG) {
+    for (int i = threadIdx.x; i < ktab * NS * NS; i += TILES_BLOCK) s_col[i] = p.colL[i];
+  } else {
+    const int n_lds = min(TILES_TTAB, rtab - 1) * NS * NS;      // rows 1 .. of the global table
+    for (int i = threadIdx.x; i <= TTAB_N; i += TILES_BLOCK)
+      s_tab[i] = i < n_lds ? p.draw_tab[i + NS * NS] : make_uint4(DRAW_TAB_NEVER, DRAW_TAB_NEVER, DRAW_TAB_NEVER, DRAW_TAB_FALLBACK);
+  }
   for (int i = threadIdx.x; i < 2 * PHM_LOGTAB_N; i += TILES_BLOCK) s_ltab[i] = logtab_entry(i);
   if (threadIdx.x < NS * NS) s_B2[threadIdx.x] = p.B2[threadIdx.x];
   if (threadIdx.x < NS) s_scale[threadIdx.x] = p.scale[threadIdx.x];
@@ -495,23 +508,30 @@ __global__ __launch_bounds__(TILES_BLOCK, LONG ? 5 : (KS ? 7 : 8)) void tiles_br
   int mnew = 0;
 
   // s_i ~ B[s_{i-1},:] (.) B^(m-i-1) e_end          (resamplebranchstates :290, :301-304)
-  auto draw_state_w = [&](int i, int sprev, uint32_t word) -> int {
-    int kk = m - i - 1;
+  // Packed form: NS - 1 unsigned compares of the raw word with the thresholds of entry (kk, cs, s_prev), kk = m - i - 1 -- the index
+  // sample_cat returns, without a floating-point operation (phm_draw_tab.h).  One 16-byte LDS read; an index past the rows kept in
+  // LDS (row 0, which no step asks for, wraps round to one) lands on the entry that carries the fallback bit.
+  const uint32_t tab_base = (uint32_t)(((m - 2) * NS + cs) * NS);      // LDS entry index of (i = 0, s_prev = 0): row kk sits at kk - 1
+  // ... and what that bit sends here: rows TILES_TTAB + 1 .. rtab - 1 from the global table, and beyond them, or where an entry cannot be
+  // tabulated (a zero or non-finite total: sample_cat flags it), the arithmetic draw from colL
+  auto draw_state_far = [&](int kk, int sprev, uint32_t word) -> int {
     if (kk >= p.klong) { err |= DERR_CAPACITY; kk = p.klong - 1; }
+    if (kk < rtab) {
+      const uint4 e = p.draw_tab[(kk * NS + cs) * NS + sprev];
+      if (!(e.w & DRAW_TAB_FALLBACK)) return draw_tab_index<NS>(e.x, e.y, e.z, e.w, word);
+    }
+    const double* __restrict__ beta = p.colL + ((size_t)kk * NS + cs) * NS;
     double pr[NS];
-    {                                          // always an LDS read (ds_read); the rare long chain overwrites it from global
-      const double* beta = s_col + ((kk < ktab ? kk : ktab - 1) * NS + cs) * NS;
 #pragma unroll
-      for (int c = 0; c < NS; ++c) pr[c] = beta[c];
-    }
-    if (kk >= ktab) {
-      const double* __restrict__ beta = p.colL + ((size_t)kk * NS + cs) * NS;
-#pragma unroll
-      for (int c = 0; c < NS; ++c) pr[c] = beta[c];
-    }
-#pragma unroll
-    for (int c = 0; c < NS; ++c) pr[c] = s_B2[sprev * NS + c] * pr[c];
+    for (int c = 0; c < NS; ++c) pr[c] = s_B2[sprev * NS + c] * beta[c];
     return sample_cat<NS>(pr, u01(word), err);
+  };
+  auto draw_state_w = [&](int i, int sprev, uint32_t word) -> int {
+    const uint32_t idx = tab_base - (uint32_t)(i * NS * NS) + (uint32_t)sprev;      // modulo 2^32: i = m - 1 (row 0) gives an index past the table
+    const uint4 e = s_tab[min(idx, (uint32_t)TTAB_N)];
+    int s = draw_tab_index<NS>(e.x, e.y, e.z, e.w, word);      // before the test: the four words in ONE ds_read_b128, not the last one first
+    if ((int32_t)e.w < 0) s = draw_state_far(m - i - 1, sprev, word);
+    return s;
   };
   auto draw_state = [&](int i, int sprev) -> int { return draw_state_w(i, sprev, su.draw_word((uint32_t)(i - 1))); };
 
@@ -841,6 +861,36 @@ hipError_t launch_tiles_init(int n_edge, int n_tiles, int64_t rows, const int32_
                      maps, dw0, mcount);
   return hipGetLastError();
 }
+
+// The thresholds of the segment-state draw for one model: a thread per 32-bit word of every entry (kk, end state, previous state), each
+// threshold by 32 halvings on sample_cat's own comparison (phm_draw_tab.h).
+template <int NS>
+struct DrawTabModel { double B2[NS * NS]; };
+
+template <int NS>
+__global__ __launch_bounds__(256) void tiles_draw_tab_kernel(DrawTabModel<NS> mdl, const double* __restrict__ colL, int rows, uint32_t* __restrict__ out) {
+  __shared__ double s_B2[NS * NS];                   // indexed by a per-thread state
+  if (threadIdx.x < NS * NS) s_B2[threadIdx.x] = mdl.B2[threadIdx.x];
+  __syncthreads();
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= rows * NS * NS * 4) return;
+  const int entry = t >> 2, sprev = entry % NS, kc = entry / NS;      // kc = kk * NS + end state: a row of colL
+  out[t] = draw_tab_word<NS>(s_B2 + sprev * NS, colL + (size_t)kc * NS, t & 3);
+}
+
+template <int NS>
+hipError_t launch_tiles_draw_tab(const double* B2_host, const double* colL, int klong, uint4* draw_tab, hipStream_t stream) {
+  DrawTabModel<NS> mdl;
+  for (int i = 0; i < NS * NS; ++i) mdl.B2[i] = B2_host[i];
+  const int rows = std::min(klong, DRAW_TAB_ROWS);
+  hipLaunchKernelGGL(tiles_draw_tab_kernel<NS>, dim3((unsigned)((rows * NS * NS * 4 + 255) / 256)), dim3(256), 0, stream, mdl, colL, rows,
+                     reinterpret_cast<uint32_t*>(draw_tab));
+  return hipGetLastError();
+}
+
+template hipError_t launch_tiles_draw_tab<2>(const double*, const double*, int, uint4*, hipStream_t);
+template hipError_t launch_tiles_draw_tab<3>(const double*, const double*, int, uint4*, hipStream_t);
+template hipError_t launch_tiles_draw_tab<4>(const double*, const double*, int, uint4*, hipStream_t);
 
 template <int NS>
 hipError_t launch_tiles_sweep(const TileParams<NS>& p, const std::vector<int32_t>& up_off,
